@@ -3,7 +3,7 @@
 (BASELINE.json configs[1], "C2"): a batch of 8 volumes per GPU, device-resident in,
 device-resident out.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 without WORLD_SIZE in the environment: this process (which never touches the GPU) starts N
 ranks of itself -- one process per GPU, RCCL -- relays rank 0's JSON line and exits with the worst
@@ -14,6 +14,12 @@ are sharded over the ranks along the pass's slice axis and an RCCL all-gather re
 between the passes (weak scaling: 8 volumes per GPU); the exchange-free alternative (whole volumes
 per rank) is timed in the same job and reported as `value_replicas`.
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path returned in its last step as float32
+DIR/<name>.npy (c2: volume0 .. volumeV-1, the final [z,y,x] volumes; c4: volume).  An output larger than its share of
+DUMP_BYTES is replaced by the same fixed sample of its elements in every run (flat indices drawn by numpy
+default_rng(DUMP_SEED), sorted).  Inputs and weights are seeded, so two builds run with the same arguments can be
+compared file for file.
 """
 import argparse
 import json
@@ -38,6 +44,8 @@ PARITY_TOL = 1e-3                        # BASELINE.json north_star: relative L2
 PREC_NAME = {3: "f16x3", 2: "f16f6", 1: "f16x1"}
 DTYPE_NAME = {3: "f16x3->f32", 2: "f16+2xbf6->f32", 1: "f16->f32"}
 ROUND = "r03"
+DUMP_BYTES = 60 * 2 ** 20                # --dump-outputs: the whole dump stays under 64 MB
+DUMP_SEED = 2024
 
 
 def parse_args(argv=None):
@@ -67,7 +75,30 @@ def parse_args(argv=None):
                     help="c2 (default, the headline): BASELINE configs[1]; c4: BASELINE configs[3], one 64^3 x 4 -> 512^3 "
                          "volume through the three 8x generators, slices sharded over the ranks")
     ap.add_argument("--launch-timeout", type=float, default=3000.0)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, named):
+    """named: [(name, device tensor)], the outputs of the last timed step.  Writes path/<name>.npy as float32; a tensor
+    with more elements than its share of DUMP_BYTES is written as the elements at fixed, seeded flat indices."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(len(named), 1)
+    picks = {}
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            if flat.numel() not in picks:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), share, replace=False))
+                picks[flat.numel()] = torch.as_tensor(idx, device=flat.device)
+            flat = flat[picks[flat.numel()]]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
 
 
 def gen_resnet_flops_per_slice(c=1, hw=256 * 256):
@@ -400,6 +431,8 @@ def main_c4(args):
             sys.stdout.flush()
         sys.stderr.flush()
         os._exit(3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("volume", out)])
     extra = {}
     if world > 1 and args.mode == "both":
         other = "all_to_all" if args.exchange == "all_gather" else "all_gather"
@@ -505,6 +538,8 @@ def main(argv=None):
     else:
         dt, outs = timed(g1, g2, replicas=not sharded_first)
     checksum = float(outs[0].double().sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("volume%d" % i, o) for i, o in enumerate(outs)])
     del outs
     if world > 1 and args.mode == "both":
         dt_r, o = timed(g1, g2, replicas=True)
