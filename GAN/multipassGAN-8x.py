@@ -155,9 +155,6 @@ if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or 
     fail("vorticity / flag / k-eps inputs and premade tiles are not supported")
 if int(P["usePixelShuffle"]) or int(P["gDrop"]) or int(P["useVelInTDisc"]):
     fail("usePixelShuffle / gDrop / useVelInTDisc are 0 in the reference runs and not built")
-if (int(P["batchNorm"]) or int(P["use_mb_stddev"])) and int(P["use_wgan_gp"]):
-    fail("batchNorm / use_mb_stddev (8x.py:85,149) train with use_wgan_gp 0 (LSGAN or sigmoid cross entropy): the gradient "
-         "penalty would need second derivatives of the batch statistics, which are not built")
 upRes = int(P["upRes"])
 if upRes != 8:
     fail("the growing networks are built for upRes 8")

@@ -213,6 +213,11 @@ int mpg_minibatch_stddev(mpg_stream_t stream, const float* x, int n, int h, int 
  * every member of the group); dstat: M floats of scratch. */
 int mpg_minibatch_stddev_bwd(mpg_stream_t stream, const float* x, const float* dy, int n, int h, int w, int c,
                              int group_size, float* dstat, float* dx);
+/* second derivative of GAN.minibatch_stddev_layer (GAN.py:476-488) for the WGAN-GP penalty (multipassGAN-8x.py:1123-1140
+ * with use_mb_stddev, :847-848 and :907-908): given the upstream gradient ggx [n,h,w,c] of mpg_minibatch_stddev_bwd's dx,
+ * g_x [n,h,w,c] and g_dy [n,h,w,c+1].  Per-group sums in a fixed order; partials: >= 514 * M floats (M = n / G). */
+int mpg_minibatch_stddev_bwd2(mpg_stream_t stream, const float* x, const float* dy, const float* ggx, int n, int h, int w,
+                              int c, int group_size, float* g_x, float* g_dy, float* partials, size_t partials_floats);
 /* y = act(a + b) elementwise (tf.nn.relu(tf.add(..)), multipassGAN-4x.py:523); b may be NULL */
 int mpg_add_act(mpg_stream_t stream, const float* a, const float* b, size_t n, int act, float leak, float* y);
 
@@ -334,6 +339,15 @@ int mpg_bn_train_bwd(mpg_stream_t stream, const float* dy, const float* x, size_
 int mpg_bn_train_bwd_ordered(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c,
                              const float* batch_mean, const float* batch_var, const float* gamma, float eps,
                              float* dx, float* dgamma, float* dbeta, float* amax, float* partials, size_t partials_floats);
+/* second derivative of the normalisation above, for the WGAN-GP penalty through a batch-normalised critic
+ * (tf.gradients at y_gp, multipassGAN-8x.py:1123-1140, differentiating batch_norm(is_training=True) of GAN.py:108-110 twice).
+ * The first backward maps (dz, x, gamma) -> (dx, dgamma, dbeta); given the upstream gradients gdx [npix,c], gdgamma [c],
+ * gdbeta [c] (each may be NULL = zero) it returns g_dz [npix,c], g_x [npix,c] and g_gamma [c].  The per-channel sums are
+ * block sums in `partials` (mpg_bn_partials_floats(c) floats) added in a fixed order: the same bits on every run. */
+int mpg_bn_train_bwd2_ordered(mpg_stream_t stream, const float* dz, const float* x, size_t npix, int c,
+                              const float* batch_mean, const float* batch_var, const float* gamma, float eps,
+                              const float* gdx, const float* gdgamma, const float* gdbeta, float* g_dz, float* g_x,
+                              float* g_gamma, float* partials, size_t partials_floats);
 /* dx = dy * act'(.) written through the activation OUTPUT y (relu, lrelu GAN.py:733-737, tanh); amax as above */
 int mpg_act_bwd(mpg_stream_t stream, const float* dy, const float* y, size_t n, int act, float leak, float* dx,
                 float* amax);

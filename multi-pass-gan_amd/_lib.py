@@ -121,6 +121,7 @@ PROTOTYPES = {
     "mpg_pixel_norm": (_I, [_P, _P, _Z, _I, _F, _P]),
     "mpg_minibatch_stddev": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mpg_minibatch_stddev_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "mpg_minibatch_stddev_bwd2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z]),
     "mpg_add_act": (_I, [_P, _P, _P, _Z, _I, _F, _P]),
     "mpg_axis_zoom_linear": (_I, [_P, _P, _Z, _I, _Z, _P, _I]),
     "mpg_volume_transpose": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _F, _P]),
@@ -143,6 +144,7 @@ PROTOTYPES = {
     "mpg_bn_train_fwd_ordered": (_I, [_P, _P, _Z, _I, _P, _P, _F, _I, _F, _P, _P, _P, _P, _P, _F, _P, _Z]),
     "mpg_bn_train_bwd": (_I, [_P, _P, _P, _Z, _I, _P, _P, _P, _F, _P, _P, _P, _P]),
     "mpg_bn_train_bwd_ordered": (_I, [_P, _P, _P, _Z, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _Z]),
+    "mpg_bn_train_bwd2_ordered": (_I, [_P, _P, _P, _Z, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _Z]),
     "mpg_act_bwd": (_I, [_P, _P, _P, _Z, _I, _F, _P, _P]),
     "mpg_pixel_norm_bwd": (_I, [_P, _P, _P, _Z, _I, _F, _P]),
     "mpg_resize_nearest_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),

@@ -1261,3 +1261,372 @@ extern "C" int mpg_maccormack(mpg_stream_t stream, const float* source, const fl
                        flags, vel, n, h, w, strength, out, keep);
     MPG_LAUNCH_CHECK("maccormack_kernel");
 }
+
+// ---------------------------------------------------------------- second derivatives (WGAN-GP through BN / minibatch stddev)
+namespace {
+
+// Double backward of training-mode batch norm.  Per channel over the M pixels, x^ = (x - mean) r, r = rsqrt(var + eps):
+// one reduction pass for the five sums Sdz, Sdzx (= dbeta, dgamma of the first backward), Sg, Sgx, Sgdz; the blocks' sums go
+// to `partials` ([block][channel][5]) and bn_bwd2_finalize_kernel adds them in block order (no atomics), then folds them with
+// gamma, gdgamma, gdbeta into eight per-channel coefficients of the elementwise pass and writes g_gamma.
+constexpr int BN2_NS = 5;
+constexpr int BN2_MAX_BLOCKS = 256;
+constexpr int BN2_NCOEF = 9;                    // mean, r, then g_dz = a0 gdx + a1 + a2 x^, g_x = b0 x^ + b1 gdx + b2 dz + b3
+
+template <int V>
+__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&o)[V]) {
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = p[j];
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void stv(float* __restrict__ p, const float (&o)[V]) {
+    if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) p[j] = o[j];
+    }
+}
+
+// V channels per thread (V = 4: c % 4 == 0 and 16-byte aligned tensors); `lanes` threads across the channels, BLK / lanes
+// pixel rows; block x = one slice of the pixel range, block y = one group of lanes * V channels
+template <int V>
+__global__ __launch_bounds__(256) void bn_bwd2_sum_kernel(const float* __restrict__ dz, const float* __restrict__ x,
+                                                          const float* __restrict__ gdx, size_t npix, int c, int lanes,
+                                                          const float* __restrict__ mean, const float* __restrict__ var,
+                                                          float eps, size_t pix_per_block, float* __restrict__ partials) {
+    __shared__ float red[BN2_NS][BLK * V];
+    const int tid = threadIdx.x;
+    const int ppi = BLK / lanes;
+    const int lane = tid % lanes, row = tid / lanes;
+    const int ch = (blockIdx.y * lanes + lane) * V;
+    const size_t p_begin = (size_t)blockIdx.x * pix_per_block;
+    const size_t p_end = min(npix, p_begin + pix_per_block);
+    float s[BN2_NS][V];
+#pragma unroll
+    for (int k = 0; k < BN2_NS; ++k)
+#pragma unroll
+        for (int j = 0; j < V; ++j) s[k][j] = 0.f;
+    if (ch < c) {
+        float m[V], r[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) { m[j] = mean[ch + j]; r[j] = rsqrtf(var[ch + j] + eps); }
+        for (size_t p = p_begin + row; p < p_end; p += ppi) {
+            float d[V], xv[V], g[V];
+            ldv<V>(dz + p * c + ch, d);
+            ldv<V>(x + p * c + ch, xv);
+            if (gdx != nullptr) ldv<V>(gdx + p * c + ch, g);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const float xh = (xv[j] - m[j]) * r[j];
+                s[0][j] += d[j];
+                s[1][j] = fmaf(d[j], xh, s[1][j]);
+                if (gdx != nullptr) {
+                    s[2][j] += g[j];
+                    s[3][j] = fmaf(g[j], xh, s[3][j]);
+                    s[4][j] = fmaf(g[j], d[j], s[4][j]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < BN2_NS; ++k)
+#pragma unroll
+        for (int j = 0; j < V; ++j) red[k][tid * V + j] = s[k][j];
+    __syncthreads();
+    if (row == 0 && ch < c) {
+        for (int rr = 1; rr < ppi; ++rr)            // rows added in order: the block's sums do not depend on timing
+#pragma unroll
+            for (int k = 0; k < BN2_NS; ++k)
+#pragma unroll
+                for (int j = 0; j < V; ++j) s[k][j] += red[k][(rr * lanes + lane) * V + j];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (ch + j >= c) break;
+            float* pp = partials + ((size_t)blockIdx.x * c + ch + j) * BN2_NS;
+#pragma unroll
+            for (int k = 0; k < BN2_NS; ++k) pp[k] = s[k][j];
+        }
+    }
+}
+
+// 16 channels per block, 16 interleaved runs of blocks per channel (eight loads in flight), then the runs in sequence: the
+// order of sum_partials_kernel, fixed
+__global__ __launch_bounds__(256) void bn_bwd2_finalize_kernel(const float* __restrict__ partials, int nblocks, int c,
+                                                               float inv_n, const float* __restrict__ mean,
+                                                               const float* __restrict__ var, float eps,
+                                                               const float* __restrict__ gamma,
+                                                               const float* __restrict__ gdgamma,
+                                                               const float* __restrict__ gdbeta, float* __restrict__ coef,
+                                                               float* __restrict__ g_gamma) {
+    __shared__ float red[BN2_NS][256];
+    const int tid = threadIdx.x, cl = tid & 15, seg = tid >> 4;
+    const int ch = blockIdx.x * 16 + cl;
+    float S[BN2_NS] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (ch < c) {
+        int b = seg;
+        for (; b + 7 * 16 < nblocks; b += 8 * 16) {
+            float p[8][BN2_NS];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int k = 0; k < BN2_NS; ++k) p[u][k] = partials[((size_t)(b + 16 * u) * c + ch) * BN2_NS + k];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+#pragma unroll
+                for (int k = 0; k < BN2_NS; ++k) S[k] += p[u][k];
+        }
+        for (; b < nblocks; b += 16)
+#pragma unroll
+            for (int k = 0; k < BN2_NS; ++k) S[k] += partials[((size_t)b * c + ch) * BN2_NS + k];
+    }
+#pragma unroll
+    for (int k = 0; k < BN2_NS; ++k) red[k][tid] = S[k];
+    __syncthreads();
+    if (seg != 0 || ch >= c) return;
+    for (int r = 1; r < 16; ++r)
+#pragma unroll
+        for (int k = 0; k < BN2_NS; ++k) S[k] += red[k][r * 16 + cl];
+    const float sdz = S[0], sdzx = S[1], sg = S[2], sgx = S[3], sgdz = S[4];
+    const float r = rsqrtf(var[ch] + eps), gm = gamma[ch];
+    const float gdg = gdgamma != nullptr ? gdgamma[ch] : 0.f, gdb = gdbeta != nullptr ? gdbeta[ch] : 0.f;
+    const float A = sgdz - sg * sdz * inv_n;
+    const float gr = gm * r, k = gm * r * r * inv_n;
+    g_gamma[ch] = r * (A - sgx * sdzx * inv_n);
+    coef[0 * (size_t)c + ch] = mean[ch];
+    coef[1 * (size_t)c + ch] = r;
+    coef[2 * (size_t)c + ch] = gr;                                                   // a0
+    coef[3 * (size_t)c + ch] = gdb - gr * sg * inv_n;                               // a1
+    coef[4 * (size_t)c + ch] = gdg - gr * sgx * inv_n;                              // a2
+    coef[5 * (size_t)c + ch] = k * (3.f * sgx * sdzx * inv_n - A) - gdg * r * sdzx * inv_n;   // b0
+    coef[6 * (size_t)c + ch] = -k * sdzx;                                            // b1
+    coef[7 * (size_t)c + ch] = gdg * r - k * sgx;                                    // b2
+    coef[8 * (size_t)c + ch] = k * (sdzx * sg + sgx * sdz) * inv_n - gdg * r * sdz * inv_n;   // b3
+}
+
+// g_dz = a0 gdx + a1 + a2 x^,  g_x = b0 x^ + b1 gdx + b2 dz + b3.  V = 4: the coefficients staged in LDS (c <= BN4_CMAX)
+template <int V>
+__global__ __launch_bounds__(256) void bn_bwd2_apply_kernel(const float* __restrict__ dz, const float* __restrict__ x,
+                                                            const float* __restrict__ gdx, size_t totalv, int c,
+                                                            const float* __restrict__ coef, float* __restrict__ g_dz,
+                                                            float* __restrict__ g_x) {
+    __shared__ __attribute__((aligned(16))) float par[V == 4 ? BN2_NCOEF : 1][V == 4 ? BN4_CMAX : 1];
+    if constexpr (V == 4) {
+        for (int i = threadIdx.x; i < c; i += BLK)
+#pragma unroll
+            for (int k = 0; k < BN2_NCOEF; ++k) par[k][i] = coef[(size_t)k * c + i];
+        __syncthreads();
+    }
+    for (size_t iv = (size_t)blockIdx.x * BLK + threadIdx.x; iv < totalv; iv += (size_t)gridDim.x * BLK) {
+        const size_t e = iv * V;
+        const int ch = (int)(e % (size_t)c);
+        float d[V], xv[V], g[V], q[BN2_NCOEF][V];
+        ldv<V>(dz + e, d);
+        ldv<V>(x + e, xv);
+        if (gdx != nullptr) ldv<V>(gdx + e, g);
+        else
+#pragma unroll
+            for (int j = 0; j < V; ++j) g[j] = 0.f;
+#pragma unroll
+        for (int k = 0; k < BN2_NCOEF; ++k) {
+            if constexpr (V == 4) ldv<V>(&par[k][ch], q[k]);
+            else q[k][0] = coef[(size_t)k * c + ch];
+        }
+        float od[V], ox[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float xh = (xv[j] - q[0][j]) * q[1][j];
+            od[j] = fmaf(q[2][j], g[j], fmaf(q[4][j], xh, q[3][j]));
+            ox[j] = fmaf(q[5][j], xh, fmaf(q[6][j], g[j], fmaf(q[7][j], d[j], q[8][j])));
+        }
+        stv<V>(g_dz + e, od);
+        stv<V>(g_x + e, ox);
+    }
+}
+
+// Double backward of GAN.minibatch_stddev_layer.  G members per group, M = n / G groups, K = h w c features; per (m, f):
+// u = x - mean_g x, s_f = sqrt(mean_g u^2 + 1e-8).  Pass 1 (grid: slices x M): per group the block sums of
+// D_m = sum over members and pixels of dy[.., c] and of sum_{g,f} ggx u / s_f, into `partials` ([m][block][2]);
+// pass 2 adds them in block order; pass 3 is elementwise over (m, f) with a loop over the members.
+constexpr int MBSTD2_MAX_BLOCKS = 256;
+
+__global__ __launch_bounds__(256) void mbstd_bwd2_sum_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                             const float* __restrict__ ggx, int g, int m, size_t npix_per,
+                                                             int c, float* __restrict__ partials) {
+    __shared__ float red0[BLK];
+    __shared__ float red1[BLK];
+    const int mi = blockIdx.y;
+    const size_t hwc = npix_per * (size_t)c;
+    const size_t stride = (size_t)gridDim.x * BLK;
+    float t = 0.f, dsum = 0.f;
+    for (size_t i = (size_t)blockIdx.x * BLK + threadIdx.x; i < hwc; i += stride) {
+        float mean = 0.f;
+        for (int k = 0; k < g; ++k) mean += x[((size_t)k * m + mi) * hwc + i];
+        mean /= (float)g;
+        float var = 0.f, q = 0.f;
+        for (int k = 0; k < g; ++k) {
+            const size_t o = ((size_t)k * m + mi) * hwc + i;
+            const float u = x[o] - mean;
+            var = fmaf(u, u, var);
+            q = fmaf(ggx[o], u, q);
+        }
+        t += q / sqrtf(var / (float)g + 1e-8f);
+    }
+    const size_t per_group = (size_t)g * npix_per;
+    for (size_t i = (size_t)blockIdx.x * BLK + threadIdx.x; i < per_group; i += stride) {
+        const size_t k = i / npix_per, p = i - k * npix_per;
+        dsum += dy[(((size_t)k * m + mi) * npix_per + p) * (c + 1) + c];
+    }
+    red0[threadIdx.x] = t;
+    red1[threadIdx.x] = dsum;
+    __syncthreads();
+    for (int st = BLK / 2; st > 0; st >>= 1) {
+        if (threadIdx.x < st) {
+            red0[threadIdx.x] += red0[threadIdx.x + st];
+            red1[threadIdx.x] += red1[threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partials[((size_t)mi * gridDim.x + blockIdx.x) * 2] = red1[0];
+        partials[((size_t)mi * gridDim.x + blockIdx.x) * 2 + 1] = red0[0];
+    }
+}
+
+// stats[2 m] = D_m / (K G), stats[2 m + 1] = T_m = sum_{g,f} ggx u / (K G s_f); one block per group, the nblocks
+// (<= BLK) block sums added in a fixed tree
+__global__ __launch_bounds__(256) void mbstd_bwd2_finalize_kernel(const float* __restrict__ partials, int nblocks, float inv_kg,
+                                                                  float* __restrict__ stats) {
+    __shared__ float red0[BLK];
+    __shared__ float red1[BLK];
+    const int mi = blockIdx.x, b = threadIdx.x;
+    red0[b] = b < nblocks ? partials[((size_t)mi * nblocks + b) * 2] : 0.f;
+    red1[b] = b < nblocks ? partials[((size_t)mi * nblocks + b) * 2 + 1] : 0.f;
+    __syncthreads();
+    for (int st = BLK / 2; st > 0; st >>= 1) {
+        if (b < st) {
+            red0[b] += red0[b + st];
+            red1[b] += red1[b + st];
+        }
+        __syncthreads();
+    }
+    if (b == 0) {
+        stats[2 * mi] = red0[0] * inv_kg;
+        stats[2 * mi + 1] = red1[0] * inv_kg;
+    }
+}
+
+// g_x = D_m / (K G) ((ggx - mean_g ggx) / s_f - Q_f u / (G s_f^3)),  Q_f = sum_g ggx u;
+// g_dy = (ggx, T_m) -- the statistic channel written by the thread of feature channel 0
+__global__ void mbstd_bwd2_apply_kernel(const float* __restrict__ x, const float* __restrict__ ggx,
+                                        const float* __restrict__ stats, int g, int m, size_t hwc, int c,
+                                        float* __restrict__ g_x, float* __restrict__ g_dy) {
+    const size_t i = (size_t)blockIdx.x * BLK + threadIdx.x;
+    const int mi = blockIdx.y;
+    if (i >= hwc) return;
+    float mx = 0.f, mg = 0.f;
+    for (int k = 0; k < g; ++k) {
+        const size_t o = ((size_t)k * m + mi) * hwc + i;
+        mx += x[o];
+        mg += ggx[o];
+    }
+    mx /= (float)g;
+    mg /= (float)g;
+    float var = 0.f, q = 0.f;
+    for (int k = 0; k < g; ++k) {
+        const size_t o = ((size_t)k * m + mi) * hwc + i;
+        const float u = x[o] - mx;
+        var = fmaf(u, u, var);
+        q = fmaf(ggx[o], u, q);
+    }
+    const float is = 1.f / sqrtf(var / (float)g + 1e-8f);
+    const float dk = stats[2 * mi], tm = stats[2 * mi + 1];
+    const float qc = q * is * is * is / (float)g;
+    const size_t pix = i / c;
+    const int ch = (int)(i - pix * c);
+    for (int k = 0; k < g; ++k) {
+        const int nn = k * m + mi;
+        const size_t o = (size_t)nn * hwc + i;
+        const float gg = ggx[o];
+        g_x[o] = dk * ((gg - mg) * is - qc * (x[o] - mx));
+        const size_t oy = ((size_t)nn * (hwc / c) + pix) * (c + 1);
+        g_dy[oy + ch] = gg;
+        if (ch == 0) g_dy[oy + c] = tm;
+    }
+}
+
+}  // namespace
+
+extern "C" int mpg_bn_train_bwd2_ordered(mpg_stream_t stream, const float* dz, const float* x, size_t npix, int c,
+                                         const float* batch_mean, const float* batch_var, const float* gamma, float eps,
+                                         const float* gdx, const float* gdgamma, const float* gdbeta, float* g_dz, float* g_x,
+                                         float* g_gamma, float* partials, size_t partials_floats) {
+    MPG_REQUIRE(dz && x && batch_mean && batch_var && gamma && g_dz && g_x && g_gamma && partials,
+                "mpg_bn_train_bwd2_ordered: null pointer");
+    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_bn_train_bwd2_ordered: bad shape");
+    MPG_REQUIRE(partials_floats >= mpg_bn_partials_floats(c), "mpg_bn_train_bwd2_ordered: partials buffer too small");
+    hipStream_t s = (hipStream_t)stream;
+    float* coef = partials + (size_t)BN2_MAX_BLOCKS * c * BN2_NS;       // BN2_NCOEF * c floats behind the block sums
+    const uintptr_t al = (uintptr_t)dz | (uintptr_t)x | (uintptr_t)gdx | (uintptr_t)g_dz | (uintptr_t)g_x;
+    const bool v4 = (c % 4) == 0 && (al & 15) == 0;
+    const int cv = v4 ? c / 4 : c;
+    int lanes = 1;
+    while (lanes < cv && lanes < BLK) lanes <<= 1;
+    const int cblocks = (cv + lanes - 1) / lanes;
+    const int ppi = BLK / lanes;
+    size_t blocks = (npix + (size_t)ppi * 16 - 1) / ((size_t)ppi * 16);
+    if (blocks > (size_t)BN2_MAX_BLOCKS) blocks = BN2_MAX_BLOCKS;
+    if (blocks < 1) blocks = 1;
+    const size_t ppb = (npix + blocks - 1) / blocks;
+    blocks = (npix + ppb - 1) / ppb;
+    if (v4)
+        hipLaunchKernelGGL(bn_bwd2_sum_kernel<4>, dim3((unsigned)blocks, cblocks), dim3(BLK), 0, s, dz, x, gdx, npix, c, lanes,
+                           batch_mean, batch_var, eps, ppb, partials);
+    else
+        hipLaunchKernelGGL(bn_bwd2_sum_kernel<1>, dim3((unsigned)blocks, cblocks), dim3(BLK), 0, s, dz, x, gdx, npix, c, lanes,
+                           batch_mean, batch_var, eps, ppb, partials);
+    hipLaunchKernelGGL(bn_bwd2_finalize_kernel, dim3((c + 15) / 16), dim3(BLK), 0, s, (const float*)partials, (int)blocks, c,
+                       1.f / (float)npix, batch_mean, batch_var, eps, gamma, gdgamma, gdbeta, coef, g_gamma);
+    const size_t total = npix * c;
+    if (v4 && c <= BN4_CMAX) {
+        unsigned g = grid_for(total / 4);
+        if (g > 4096) g = 4096;
+        hipLaunchKernelGGL(bn_bwd2_apply_kernel<4>, dim3(g), dim3(BLK), 0, s, dz, x, gdx, total / 4, c, (const float*)coef,
+                           g_dz, g_x);
+    } else {
+        unsigned g = grid_for(total);
+        if (g > 8192) g = 8192;
+        hipLaunchKernelGGL(bn_bwd2_apply_kernel<1>, dim3(g), dim3(BLK), 0, s, dz, x, gdx, total, c, (const float*)coef, g_dz,
+                           g_x);
+    }
+    MPG_LAUNCH_CHECK("bn_train_bwd2");
+}
+
+extern "C" int mpg_minibatch_stddev_bwd2(mpg_stream_t stream, const float* x, const float* dy, const float* ggx, int n, int h,
+                                         int w, int c, int group_size, float* g_x, float* g_dy, float* partials,
+                                         size_t partials_floats) {
+    MPG_REQUIRE(x && dy && ggx && g_x && g_dy && partials, "mpg_minibatch_stddev_bwd2: null pointer");
+    MPG_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1 && group_size >= 1, "mpg_minibatch_stddev_bwd2: bad shape");
+    const int g = group_size < n ? group_size : n;
+    MPG_REQUIRE(n % g == 0, "mpg_minibatch_stddev_bwd2: batch %d is not divisible by the group size %d", n, g);
+    const int m = n / g;
+    MPG_REQUIRE(partials_floats >= (size_t)m * (2 * MBSTD2_MAX_BLOCKS + 2), "mpg_minibatch_stddev_bwd2: partials buffer too small");
+    const size_t npix_per = (size_t)h * w, hwc = npix_per * c;
+    hipStream_t s = (hipStream_t)stream;
+    size_t span = hwc > (size_t)g * npix_per ? hwc : (size_t)g * npix_per;
+    unsigned bx = (unsigned)((span + BLK * 4 - 1) / (BLK * 4));
+    if (bx > MBSTD2_MAX_BLOCKS) bx = MBSTD2_MAX_BLOCKS;
+    float* stats = partials + (size_t)m * 2 * MBSTD2_MAX_BLOCKS;
+    hipLaunchKernelGGL(mbstd_bwd2_sum_kernel, dim3(bx, m), dim3(BLK), 0, s, x, dy, ggx, g, m, npix_per, c, partials);
+    hipLaunchKernelGGL(mbstd_bwd2_finalize_kernel, dim3(m), dim3(BLK), 0, s, (const float*)partials, (int)bx,
+                       1.f / ((float)hwc * (float)g), stats);
+    hipLaunchKernelGGL(mbstd_bwd2_apply_kernel, dim3(grid_for(hwc), m), dim3(BLK), 0, s, x, ggx, (const float*)stats, g, m, hwc,
+                       c, g_x, g_dy);
+    MPG_LAUNCH_CHECK("mbstd backward-of-backward kernels");
+}

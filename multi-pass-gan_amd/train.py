@@ -365,6 +365,79 @@ class Lerp2Fn(torch.autograd.Function):
         return dx, dyy, None
 
 
+class BNTrain2Fn(torch.autograd.Function):
+    """batch_norm(is_training=True) without its activation (GAN.py:108-110), differentiable twice; like the first-order
+    path (ConvLayerFn) every evaluation advances the moving averages once"""
+
+    @staticmethod
+    def forward(ctx, lin, gamma, beta, cfg):
+        mm, mv = cfg.get("moving", (None, None))
+        y, mean, var = train_ops.bn_train_fwd(lin.detach(), gamma.detach(), beta.detach(), cfg["eps"], None, 0.2, mm, mv,
+                                              cfg.get("decay", 0.999))
+        ctx.save_for_backward(lin, gamma, mean, var)
+        ctx.eps = cfg["eps"]
+        return y
+
+    @staticmethod
+    def backward(ctx, dz):
+        lin, gamma, mean, var = ctx.saved_tensors
+        dx, dgamma, dbeta = BNTrainBwd2Fn.apply(dz, lin, gamma, mean, var, ctx.eps)
+        return dx, dgamma, dbeta, None
+
+
+class BNTrainBwd2Fn(torch.autograd.Function):
+    """(dz, x, gamma) -> (dx, dgamma, dbeta) of the normalisation (mean, var: the forward's batch statistics, constants
+    here: the formulas of mpg_bn_train_bwd2_ordered already carry their dependence on x)"""
+
+    @staticmethod
+    def forward(ctx, dz, lin, gamma, mean, var, eps):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(dz, lin, gamma, mean, var)
+        ctx.eps = eps
+        dx, dgamma, dbeta = train_ops.bn_train_bwd(dz.detach(), lin.detach(), mean, var, gamma.detach(), eps)
+        return dx, dgamma.clone(), dbeta.clone()        # separate storages, not two views of one [2, C] buffer
+
+    @staticmethod
+    def backward(ctx, gdx, gdgamma, gdbeta):
+        if gdx is None and gdgamma is None and gdbeta is None:
+            return None, None, None, None, None, None
+        dz, lin, gamma, mean, var = ctx.saved_tensors
+        g_dz, g_x, g_gamma = train_ops.bn_train_bwd2(dz.detach(), lin.detach(), mean, var, gamma.detach(), ctx.eps,
+                                                     gdx, gdgamma, gdbeta)
+        return g_dz, g_x, g_gamma, None, None, None
+
+
+class MinibatchStddev2Fn(torch.autograd.Function):
+    """GAN.minibatch_stddev_layer (GAN.py:476-488), differentiable twice"""
+
+    @staticmethod
+    def forward(ctx, x, group_size):
+        ctx.save_for_backward(x)
+        ctx.group_size = group_size
+        return ops.minibatch_stddev(x.detach().contiguous(), group_size)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return MinibatchStddevBwd2Fn.apply(dy, x, ctx.group_size), None
+
+
+class MinibatchStddevBwd2Fn(torch.autograd.Function):
+    """dx = dy[..., :C] + D_m u / (K G s_f): linear in dy, the statistic's second derivative in x"""
+
+    @staticmethod
+    def forward(ctx, dy, x, group_size):
+        ctx.save_for_backward(dy, x)
+        ctx.group_size = group_size
+        return train_ops.minibatch_stddev_bwd(dy.detach(), x.detach(), group_size)
+
+    @staticmethod
+    def backward(ctx, ggx):
+        dy, x = ctx.saved_tensors
+        g_dy, g_x = train_ops.minibatch_stddev_bwd2(ggx, dy.detach(), x.detach(), ctx.group_size)
+        return g_dy, g_x, None
+
+
 def space_to_depth2(x):
     """[N,H,W,C] -> [N,H/2,W/2,4C], channel (r*2+s)*C + c holds x[2Y+r, 2X+s, c]"""
     n, h, w, c = x.shape
@@ -677,8 +750,7 @@ class TrainSession(object):
         if op == "minibatch_stddev":
             x = ev(n.inputs[0])
             if x.requires_grad and self._higher(n):
-                raise NotImplementedError("second-order gradient of minibatch_stddev_layer (use_mb_stddev with the "
-                                          "WGAN-GP penalty; 0 in every reference run)")
+                return MinibatchStddev2Fn.apply(x, n.attrs["group_size"])
             return MinibatchStddevFn.apply(x, n.attrs["group_size"])
         if op == "resize":
             x = ev(n.inputs[0])
@@ -709,9 +781,13 @@ class TrainSession(object):
                "eps": bn.attrs["eps"] if bn is not None else 0.0}
         wname = conv.inputs[1].attrs["var"]
         if any(wname.startswith(p) for p in self.higher_order_scopes):
-            if bn is not None:
-                raise G.GraphError("batch norm inside a gradient-penalty network is not built (the 8x discriminators have none)")
             y = ConvFn.apply(x, w4, b, cfg)
+            if bn is not None:      # the tail convolutions d_cA1 / d_cB1, t_cA1 / t_cB1 with batchNorm 1 (-8x.py:850-854,910-913)
+                if not bn.attrs["training"]:
+                    raise G.GraphError("TrainSession needs batch_norm(training=True) nodes (build the nets with train=True)")
+                bcfg = {"eps": bn.attrs["eps"], "decay": self.bn_decay,
+                        "moving": (self.params[bn.inputs[3].attrs["var"]], self.params[bn.inputs[4].attrs["var"]])}
+                y = BNTrain2Fn.apply(y, self.params[bn.inputs[1].attrs["var"]], self.params[bn.inputs[2].attrs["var"]], bcfg)
             if act is not None:
                 if act == "tanh":
                     raise G.GraphError("tanh has no higher-order lowering")
@@ -1170,12 +1246,9 @@ class Trainer8x(object):
         self.cfg = cfg
         self.k, self.k2, self.weight_dld = lambda_l1, lambda2, weight_dld
         self.use_wgan_gp, self.use_LSGAN = use_wgan_gp, use_LSGAN
-        # `batchNorm 1` / `use_mb_stddev 1` (multipassGAN-8x.py:85,149,847,907; both 0 in the reference runs): the kernels
-        # and their gradients exist, but the WGAN-GP penalty differentiates the critic twice and the second derivative of
-        # batch statistics / of the minibatch standard deviation is not built: LSGAN and sigmoid-CE losses only
-        if use_wgan_gp and (batch_norm or cfg.use_mb_stddev):
-            raise _lib.MpgError("batchNorm / use_mb_stddev with use_wgan_gp 1: the gradient penalty needs second derivatives "
-                                "of the batch statistics, which are not built -- train with use_wgan_gp 0")
+        # `batchNorm 1` / `use_mb_stddev 1` (multipassGAN-8x.py:85,149,847,907; both 0 in the reference runs) with the WGAN-GP
+        # penalty: the critic is differentiated twice through BNTrain2Fn / MinibatchStddev2Fn (mpg_bn_train_bwd2_ordered,
+        # mpg_minibatch_stddev_bwd2)
         self.batch_norm = bool(batch_norm)
         if use_wgan_gp:
             self.wgan_lambda, self.wgan_target, self.wgan_epsilon = (150.0, 30.0, 1e-3) if use_LSGAN else (10.0, 1.0, 1e-3)

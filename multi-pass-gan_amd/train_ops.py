@@ -149,6 +149,26 @@ def bn_train_bwd(dy, x, mean, var, gamma, eps=1e-3, want_amax=False):
     return (dx, dgamma, dbeta, amax) if want_amax else (dx, dgamma, dbeta)
 
 
+def bn_train_bwd2(dz, x, mean, var, gamma, eps=1e-3, gdx=None, gdgamma=None, gdbeta=None):
+    """second derivative of the normalisation: the upstream gradients (gdx, gdgamma, gdbeta) of bn_train_bwd's outputs
+    (None = zero) -> (g_dz, g_x, g_gamma); dbeta does not depend on beta, so there is no g_beta"""
+    lib = _lib.load()
+    dz, x = _cont(dz, "dz"), _cont(x, "x")
+    c = x.shape[-1]
+    gdx = _cont(gdx, "gdx") if gdx is not None else None
+    gdgamma = _cont(gdgamma, "gdgamma") if gdgamma is not None else None
+    gdbeta = _cont(gdbeta, "gdbeta") if gdbeta is not None else None
+    g_dz, g_x = torch.empty_like(x), torch.empty_like(x)
+    g_gamma = torch.empty((c,), dtype=torch.float32, device=x.device)
+    nfl = lib.mpg_bn_partials_floats(c)
+    partials = torch.empty((nfl,), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mpg_bn_train_bwd2_ordered(_stream(), _ptr(dz), _ptr(x), x.numel() // c, c, _ptr(_cont(mean, "mean")),
+                                             _ptr(_cont(var, "var")), _ptr(_cont(gamma, "gamma")), float(eps), _ptr(gdx),
+                                             _ptr(gdgamma), _ptr(gdbeta), _ptr(g_dz), _ptr(g_x), _ptr(g_gamma), _ptr(partials),
+                                             nfl), "mpg_bn_train_bwd2_ordered")
+    return g_dz, g_x, g_gamma
+
+
 def act_bwd(dy, y, act, leak=0.2, want_amax=False):
     """dx = dy * act'(.) [, max |dx| as a 0-dim tensor]"""
     lib = _lib.load()
@@ -341,6 +361,22 @@ def minibatch_stddev_bwd(dy, x, group_size):
     _lib.check(lib.mpg_minibatch_stddev_bwd(_stream(), _ptr(x), _ptr(dy), n, h, w, c, group_size, _ptr(dstat), _ptr(dx)),
                "mpg_minibatch_stddev_bwd")
     return dx
+
+
+def minibatch_stddev_bwd2(ggx, dy, x, group_size):
+    """second derivative of GAN.minibatch_stddev_layer: the upstream gradient ggx of minibatch_stddev_bwd's dx
+    -> (g_dy [N,H,W,C+1], g_x [N,H,W,C])"""
+    lib = _lib.load()
+    ggx, dy, x = _cont(ggx, "ggx"), _cont(dy, "dy"), _cont(x, "x")
+    n, h, w, c = x.shape
+    m = n // min(group_size, n)
+    g_x = torch.empty_like(x)
+    g_dy = torch.empty((n, h, w, c + 1), dtype=torch.float32, device=x.device)
+    nfl = 514 * m
+    partials = torch.empty((nfl,), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mpg_minibatch_stddev_bwd2(_stream(), _ptr(x), _ptr(dy), _ptr(ggx), n, h, w, c, group_size, _ptr(g_x),
+                                             _ptr(g_dy), _ptr(partials), nfl), "mpg_minibatch_stddev_bwd2")
+    return g_dy, g_x
 
 
 def pair_reduce(a, b, mode):
