@@ -79,8 +79,8 @@ def output_main():
     mode, upsampled = int(P["upsamplingMode"]), int(P["upsampledData"])
     if (mode, upsampled) not in ((2, 0), (1, 1), (3, 1)) or int(P["dataDim"]) != 2 or not int(P["upsampleFirst"]):
         fail("output mode: upsamplingMode 2 (upsampledData 0) or 1 / 3 (upsampledData 1), dataDim 2, upsampleFirst 1")
-    if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["usePixelShuffle"]):
-        fail("vorticity / flag / k-eps inputs and pixel shuffle are not supported")
+    if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]):
+        fail("vorticity / flag / k-eps inputs are not supported")
     ta = int(P["transposeAxis"])
     if ta not in (0, 1, 2, 3):
         fail("transposeAxis %d (0..3)" % ta)
@@ -110,7 +110,7 @@ def output_main():
                start_fms=int(P["startFms"]), max_fms=int(P["maxFms"]), add_adj=int(P["add_adj_idcs"]) > 0 and first,
                first_nn_arch=int(P["firstNNArch"]) > 0 and first, use_res_net=int(P["use_res_net"]) > 0,
                pixel_norm=int(P["pixelNorm"]) > 0, batch_norm=int(P["batchNorm"]) > 0, upsample_mode=int(P["upsampleMode"]),
-               add_bicubic=int(P["addBicubicUpsample"]) > 0)
+               add_bicubic=int(P["addBicubicUpsample"]) > 0, pixel_shuffle=int(P["usePixelShuffle"]) > 0 and first)
     path = checkpoint.model_path(base, test_no, model_no, ema=int(P["loadEmas"]) > 0)
     try:
         params = checkpoint.load(path)
@@ -153,8 +153,8 @@ if (upsampling_mode, upsampled_data) not in ((2, 0), (1, 1), (3, 1)) or int(P["d
 later_net = upsampling_mode != 2
 if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["premadeTiles"]):
     fail("vorticity / flag / k-eps inputs and premade tiles are not supported")
-if int(P["usePixelShuffle"]) or int(P["gDrop"]) or int(P["useVelInTDisc"]):
-    fail("usePixelShuffle / gDrop / useVelInTDisc are 0 in the reference runs and not built")
+if int(P["gDrop"]) or int(P["useVelInTDisc"]):
+    fail("gDrop / useVelInTDisc are 0 in the reference runs and not built")
 upRes = int(P["upRes"])
 if upRes != 8:
     fail("the growing networks are built for upRes 8")
@@ -260,7 +260,8 @@ cfg = Cfg8x(tileSizeLow=tileSizeLow, upRes=upRes, n_inputChannels=n_inputChannel
             upsampleMode=int(P["upsampleMode"]), filterSize=int(P["filterSize"]), start_fms=int(P["startFms"]),
             max_fms=int(P["maxFms"]), first_nn_arch=int(P["firstNNArch"]) > 0, use_res_net=int(P["use_res_net"]) > 0,
             pixel_norm=int(P["pixelNorm"]) > 0, addBicubicUpsample=int(P["addBicubicUpsample"]) > 0,
-            use_mb_stddev=int(P["use_mb_stddev"]) > 0, bn_decay=float(P["bnDecay"]))
+            use_mb_stddev=int(P["use_mb_stddev"]) > 0, bn_decay=float(P["bnDecay"]),
+            usePixelShuffle=int(P["usePixelShuffle"]) > 0)        # read by the first network only (growBlockGen)
 learning_rate = float(P["learningRate"])
 trainer = Trainer8x(cfg, device=device, learning_rate=learning_rate, beta1=float(P["adam_beta1"]),
                     beta2=float(P["adam_beta2"]), lambda_l1=float(P["lambda"]), lambda2=float(P["lambda2"]),

@@ -70,8 +70,8 @@ ph.checkUnusedParams()
 from mpgan_amd import ops as _ops  # noqa: E402
 prec = _ops.parse_prec(prec)
 
-if useVorticities or useFlags or useK_Eps_Turb or usePixelShuffle:
-    print("ERROR: vorticity / flag / turbulence channels and pixel shuffle are not part of the multi-pass hot path")
+if useVorticities or useFlags or useK_Eps_Turb:
+    print("ERROR: vorticity / flag / turbulence channels are not part of the multi-pass hot path")
     exit(1)
 if transposeAxis not in (0, 1, 2, 3):
     print("ERROR: transposeAxis %d (0..3)" % transposeAxis)
@@ -103,7 +103,8 @@ for k, n in enumerate(nets):
     cfg = dict(tile_low=simSizeLow, up_res=upRes, channels=n_ch, first_gen=(k == 0), filter_size=n["filter_size"],
                start_fms=n["start_fms"], max_fms=n["max_fms"], add_adj=n["add_adj"] and k == 0,
                first_nn_arch=bool(firstNNArch) and k == 0, use_res_net=n["use_res_net"], pixel_norm=pixel_norm,
-               batch_norm=batch_norm, upsample_mode=upsampleMode, add_bicubic=bool(addBicubicUpsample))
+               batch_norm=batch_norm, upsample_mode=upsampleMode, add_bicubic=bool(addBicubicUpsample),
+               pixel_shuffle=bool(usePixelShuffle) and k == 0)     # growBlockGen applies it in the first network only
     try:
         params = checkpoint.load(path)
         print("Model %d restored from %s." % (k + 1, path))

@@ -134,6 +134,17 @@ int mpg_conv_pack_weights(mpg_stream_t stream, const float* w_hwio, int kh, int 
 
 int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* desc);
 
+/* GAN.pixel_shuffle (GAN.py:554-560: a linear 1x1 convolution to 4C channels, then tf.depth_to_space(., 2)) with the
+ * shuffle in the convolution's store: the launch mpg_conv2d_fused(desc) would run, with output channel co of the
+ * (h, w) grid taken as channel co_off + co of a c_total-channel tensor and written to its depth-to-space position,
+ *     y[n, 2h + i, 2w + j, c] = conv[n, h, w, (2i + j) * c_total/4 + c],
+ * in desc->y (fp32 [N, 2H, 2W, c_total/4]) and / or desc->y_g8 (G8 with c_total/32 groups).  Outputs wider than
+ * 128 channels are several launches with their co_off.  r must be 2; no pixel norm, no post-add; MPG_PREC_F16X3 or
+ * MPG_PREC_F16X1 (MPG_PREC_F16F6: MPG_ERR_UNSUPPORTED, its kernel has no such store).  The G8 output
+ * requires c_total/4, co_off and desc->cout to be multiples of 8 (an 8-channel group stays in one parity): otherwise
+ * MPG_ERR_ARG, and the caller runs mpg_conv2d_fused and mpg_depth_to_space. */
+int mpg_conv2d_fused_d2s(mpg_stream_t stream, const mpg_conv_desc* desc, int r, int c_total, int co_off);
+
 /* A whole residual block whose three convolutions have <= 8 channels on either side, as ONE launch:
  *     y = act_b( conv_b( act_a( conv_a(up(x)) + bias_a ) ) + conv_s(up(x)) + bias_b )
  * (resBlock 0 and 3 of gen_resnet, 1 -> 2 -> 8 and 8 -> 2 -> 1 channels: GAN/multipassGAN-4x.py:505-526,560,564).
@@ -266,6 +277,9 @@ int mpg_conv2d_transpose(mpg_stream_t stream, const float* x, int n, int h, int 
                          int act, float leak, float* y);
 /* tf.depth_to_space(x, r) (GAN.pixel_shuffle, GAN.py:554-560): x[n,h,w,c] -> y[n, h*r, w*r, c / r^2] */
 int mpg_depth_to_space(mpg_stream_t stream, const float* x, int n, int h, int w, int c, int r, float* y);
+/* its adjoint, the gradient of GAN.pixel_shuffle's shuffle (GAN.py:554-560): x[n,h,w,c] -> y[n, h/r, w/r, c * r^2],
+ * y[n, q, p, (i*r + j)*c + k] = x[n, r*q + i, r*p + j, k]; h and w multiples of r */
+int mpg_space_to_depth(mpg_stream_t stream, const float* x, int n, int h, int w, int c, int r, float* y);
 
 /* ------------------------------------------------------------------------
  * Training step: what tf.gradients produces for

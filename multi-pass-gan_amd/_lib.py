@@ -110,6 +110,7 @@ PROTOTYPES = {
     "mpg_conv_pack_size": (_Z, [_I, _I, _I, _I, _I]),
     "mpg_conv_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _Z]),
     "mpg_conv2d_fused": (_I, [_P, ctypes.POINTER(ConvDesc)]),
+    "mpg_conv2d_fused_d2s": (_I, [_P, ctypes.POINTER(ConvDesc), _I, _I, _I]),
     "mpg_conv2d_small_pair": (_I, [_P, ctypes.POINTER(SmallPairDesc)]),
     "mpg_conv2d_direct": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _F, _P]),
     "mpg_resize_nearest": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
@@ -130,6 +131,7 @@ PROTOTYPES = {
     "mpg_channel_gather": (_I, [_P, _P, _I, _P, _I, _Z, _P, _P, _P, _I, _P]),
     "mpg_conv2d_transpose": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _I, _F, _P]),
     "mpg_depth_to_space": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "mpg_space_to_depth": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     # training step
     "mpg_conv2d_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "mpg_conv2d_wgrad_mfma_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),

@@ -192,7 +192,7 @@ class Cfg8x(object):
 
     def __init__(self, tileSizeLow=16, upRes=8, n_inputChannels=4, upsampling_mode=2, upsampleMode=1, filterSize=3,
                  start_fms=256, max_fms=256, first_nn_arch=True, use_res_net=True, pixel_norm=True,
-                 addBicubicUpsample=True, use_mb_stddev=False, useVelInTDisc=False, bn_decay=0.999):
+                 addBicubicUpsample=True, use_mb_stddev=False, useVelInTDisc=False, bn_decay=0.999, usePixelShuffle=False):
         self.tileSizeLow, self.upRes = tileSizeLow, upRes
         self.tileSizeHigh = tileSizeLow * upRes
         self.n_inputChannels = n_inputChannels
@@ -201,6 +201,7 @@ class Cfg8x(object):
         self.first_nn_arch, self.use_res_net, self.pixel_norm = first_nn_arch, use_res_net, pixel_norm
         self.addBicubicUpsample, self.use_mb_stddev, self.useVelInTDisc = addBicubicUpsample, use_mb_stddev, useVelInTDisc
         self.bn_decay = bn_decay
+        self.usePixelShuffle = bool(usePixelShuffle)     # only the first network reads it (growBlockGen, -out.py:239-247)
         if upsampling_mode not in (1, 2, 3):
             raise NotImplementedError("upsampling_mode %d (only 1, 2, 3 are used by the example runs)" % upsampling_mode)
         self.n_input = tileSizeLow ** 2 * n_inputChannels            # -8x.py:402-416 (modes 1, 2, 3)
@@ -262,7 +263,10 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
         for j, (up, units) in enumerate(blocks, start=1):
             last = j == len(blocks)
             with tf.variable_scope("genBlock%d" % up, reuse=reuse):
-                if c.first_gen:
+                if c.first_gen and c.usePixelShuffle:
+                    # g_cPS<up>: 1x1 linear conv to 4C, depth_to_space(2), on the block input (-out.py:241, GAN.py:554-560)
+                    x = gan.pixel_shuffle(x, upres=2, stage="%d" % up)
+                elif c.first_gen:
                     x = gan.avg_depool(mode=c.upsampleMode)      # acts on gan.layer (-out.py:243)
                 x = em.units(x, units, use_batch_norm)
                 if not output or last:

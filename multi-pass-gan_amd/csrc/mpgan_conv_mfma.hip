@@ -128,6 +128,37 @@ struct ConvArgs {
 
 typedef const __attribute__((address_space(4))) ConvArgs* KArgs;
 
+// mpg_conv2d_fused_d2s: the launch's arguments followed by the geometry of the depth-to-space output (block size 2,
+// tf.depth_to_space of GAN.pixel_shuffle, GAN.py:554-560).  Only the D2S instantiations take this larger argument
+// block; the kernels of mpg_conv2d_fused keep theirs.
+struct ConvArgsD2S {
+    ConvArgs a;
+    int cs;               // channels of the shuffled tensor (c_total / 4)
+    int coff;             // pre-shuffle channel of this launch's output channel 0
+    int cg;               // G8 groups of the shuffled tensor (cs / 8)
+};
+typedef const __attribute__((address_space(4))) ConvArgsD2S* KArgsD2S;
+
+template <bool D2S>
+struct KernelArgs { typedef ConvArgs type; };
+template <>
+struct KernelArgs<true> { typedef ConvArgsD2S type; };
+
+// pre-shuffle channel coff + c of pixel (py, px) -> channel cc of pixel `pix` (row-major in the 2H x 2W image) of the
+// shuffled tensor: coff + c = (2 i + j) cs + cc, pix = (2 py + i) 2W + 2 px + j
+struct D2SPos {
+    int cc;
+    size_t pix;
+};
+__device__ __forceinline__ D2SPos d2s_pos(const KArgsD2S dp, int py, int px, int c) {
+    const int gc = dp->coff + c;
+    const int k = gc / dp->cs;
+    D2SPos p;
+    p.cc = gc - k * dp->cs;
+    p.pix = (size_t)(2 * py + (k >> 1)) * (2 * dp->a.w) + 2 * px + (k & 1);
+    return p;
+}
+
 // Per (NT, PREC) pipeline shape (host mirror: pipe_shape()).
 template <int NT, int PREC>
 struct Pipe {
@@ -171,10 +202,13 @@ __device__ __forceinline__ void dma16(const char* src, char* lds_wave_base) {
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-template <int NT, int PT>
+// D2S: every output goes to its depth-to-space position (ConvArgsD2S; no pixel norm, no post-add); only the store
+// addresses differ
+template <int NT, int PT, bool D2S = false>
 __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs ap, char* smem, int n, int y0, int x0,
                                               int wave, int lane) {
     const auto& a = *ap;
+    const KArgsD2S dp = reinterpret_cast<KArgsD2S>(ap);
     const int r = lane & 31;
     const int hh = lane >> 5;
     // accumulator element i of n-tile nt: output channel nt*32 + 8*(i>>2) + 4*hh + (i&3), pixel r.
@@ -237,7 +271,15 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                         }
                         const int cg = nt * 4 + 2 * qp + hh;
                         if (cg < cg_out) {
-                            char* dst = a.y_g8 + ((((size_t)n * cg_out + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
+                            char* dst;
+                            size_t plane_out = plane_px;
+                            if constexpr (D2S) {
+                                const D2SPos q = d2s_pos(dp, py, x0 + r, 8 * cg);
+                                plane_out = 4 * plane_px;
+                                dst = a.y_g8 + ((((size_t)n * dp->cg + (q.cc >> 3)) * 2) * plane_out + q.pix) * 16;
+                            } else {
+                                dst = a.y_g8 + ((((size_t)n * cg_out + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
+                            }
                             half8 hi, lo;
 #pragma unroll
                             for (int j = 0; j < 8; ++j) {
@@ -245,7 +287,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                                 lo[j] = (_Float16)(v[j] - (float)hi[j]);
                             }
                             __builtin_nontemporal_store(hi, reinterpret_cast<half8*>(dst));
-                            __builtin_nontemporal_store(lo, reinterpret_cast<half8*>(dst + plane_px * 16));
+                            __builtin_nontemporal_store(lo, reinterpret_cast<half8*>(dst + plane_out * 16));
                         }
                     }
             }
@@ -273,7 +315,26 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                     stg[p * ROWF + c] += pa[(size_t)p * a.pa_stride + c];
                 }
             }
-            if (a.y != nullptr) {
+            if (D2S && a.y != nullptr) {
+                // runs of up to cs channels per shuffled pixel; float4 when no run boundary splits a quad
+                float* img = a.y + (size_t)n * 4 * a.h * a.w * dp->cs;
+                const int total = npx * a.cout;
+                if (((dp->cs | dp->coff | a.cout) & 3) == 0) {
+                    for (int f = lane * 4; f < total; f += 256) {
+                        const int p = f / a.cout;
+                        const int c = f - p * a.cout;
+                        const D2SPos q = d2s_pos(dp, py, x0 + p, c);
+                        *reinterpret_cast<float4*>(img + q.pix * dp->cs + q.cc) = *reinterpret_cast<const float4*>(stg + p * ROWF + c);
+                    }
+                } else {
+                    for (int f = lane; f < total; f += 64) {
+                        const int p = f / a.cout;
+                        const int c = f - p * a.cout;
+                        const D2SPos q = d2s_pos(dp, py, x0 + p, c);
+                        img[q.pix * dp->cs + q.cc] = stg[p * ROWF + c];
+                    }
+                }
+            } else if (a.y != nullptr) {
                 float* dst = a.y + pix0 * a.cout;
                 const int total = npx * a.cout;
                 if ((a.cout & 3) == 0) {
@@ -299,7 +360,15 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                         const float4 v0 = *reinterpret_cast<const float4*>(stg + r * ROWF + cg * 8);
                         const float4 v1 = *reinterpret_cast<const float4*>(stg + r * ROWF + cg * 8 + 4);
                         const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                        char* dst = a.y_g8 + ((((size_t)n * cg_out + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
+                        char* dst;
+                        size_t plane_out = plane_px;
+                        if constexpr (D2S) {
+                            const D2SPos q = d2s_pos(dp, py, x0 + r, 8 * cg);
+                            plane_out = 4 * plane_px;
+                            dst = a.y_g8 + ((((size_t)n * dp->cg + (q.cc >> 3)) * 2) * plane_out + q.pix) * 16;
+                        } else {
+                            dst = a.y_g8 + ((((size_t)n * cg_out + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
+                        }
                         half8 hi, lo;
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
@@ -307,7 +376,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                             lo[j] = (_Float16)(v[j] - (float)hi[j]);
                         }
                         __builtin_nontemporal_store(hi, reinterpret_cast<half8*>(dst));
-                        __builtin_nontemporal_store(lo, reinterpret_cast<half8*>(dst + plane_px * 16));
+                        __builtin_nontemporal_store(lo, reinterpret_cast<half8*>(dst + plane_out * 16));
                     }
                 }
             }
@@ -315,8 +384,10 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
     }
 }
 
-template <int NT, int PREC>
-__global__ __launch_bounds__(256, (NT >= 2 ? 2 : 3)) void conv_mfma_kernel(const ConvArgs a_unused) {
+// D2S: the launch of mpg_conv2d_fused_d2s (ConvArgsD2S, depth-to-space store); the instantiations with D2S false are
+// those of mpg_conv2d_fused
+template <int NT, int PREC, bool D2S = false>
+__global__ __launch_bounds__(256, (NT >= 2 ? 2 : 3)) void conv_mfma_kernel(const typename KernelArgs<D2S>::type a_unused) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const KArgs ap = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
     const auto& a = *ap;
@@ -460,7 +531,7 @@ __global__ __launch_bounds__(256, (NT >= 2 ? 2 : 3)) void conv_mfma_kernel(const
         __syncthreads();
     }
 
-    conv_epilogue<NT, PT>(acc, ap, smem, n, y0, x0, wave, lane);
+    conv_epilogue<NT, PT, D2S>(acc, ap, smem, n, y0, x0, wave, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1763,24 +1834,43 @@ hipError_t launch_f6(dim3 grid, size_t lds, hipStream_t st, const ConvArgs& a) {
     return hipSuccess;
 }
 
-template <int NT, int PREC>
-hipError_t launch_one(dim3 grid, size_t lds, hipStream_t st, const ConvArgs& a) {
+template <int NT, int PREC, bool D2S>
+hipError_t launch_one(dim3 grid, size_t lds, hipStream_t st, const typename KernelArgs<D2S>::type& a) {
     static int lds_limit[64] = {0};
     if (lds > 48 * 1024) {
-        hipError_t e = mpg::ensure_dyn_lds(reinterpret_cast<const void*>(&conv_mfma_kernel<NT, PREC>), (int)lds, lds_limit);
+        hipError_t e = mpg::ensure_dyn_lds(reinterpret_cast<const void*>(&conv_mfma_kernel<NT, PREC, D2S>), (int)lds, lds_limit);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((conv_mfma_kernel<NT, PREC>), grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL((conv_mfma_kernel<NT, PREC, D2S>), grid, dim3(256), lds, st, a);
     return hipSuccess;
 }
 
-template <int PREC>
-hipError_t launch_nt(int nt, dim3 grid, size_t lds, hipStream_t st, const ConvArgs& a) {
+// one launch of the fused convolution: prec (MPG_PREC_*) and cout tiles pick the instantiation
+template <bool D2S>
+hipError_t launch_conv(int prec, int nt, dim3 grid, size_t lds, hipStream_t st, const typename KernelArgs<D2S>::type& a) {
+    if constexpr (!D2S) {
+        if (prec == MPG_PREC_F16F6) {
+            switch (nt) {
+                case 1: return launch_f6<1>(grid, lds, st, a);
+                case 2: return launch_f6<2>(grid, lds, st, a);
+                case 3: return launch_f6<3>(grid, lds, st, a);
+                default: return launch_f6<4>(grid, lds, st, a);
+            }
+        }
+    }
+    if (prec == MPG_PREC_F16X3) {
+        switch (nt) {
+            case 1: return launch_one<1, 3, D2S>(grid, lds, st, a);
+            case 2: return launch_one<2, 3, D2S>(grid, lds, st, a);
+            case 3: return launch_one<3, 3, D2S>(grid, lds, st, a);
+            default: return launch_one<4, 3, D2S>(grid, lds, st, a);
+        }
+    }
     switch (nt) {
-        case 1: return launch_one<1, PREC>(grid, lds, st, a);
-        case 2: return launch_one<2, PREC>(grid, lds, st, a);
-        case 3: return launch_one<3, PREC>(grid, lds, st, a);
-        default: return launch_one<4, PREC>(grid, lds, st, a);
+        case 1: return launch_one<1, 1, D2S>(grid, lds, st, a);
+        case 2: return launch_one<2, 1, D2S>(grid, lds, st, a);
+        case 3: return launch_one<3, 1, D2S>(grid, lds, st, a);
+        default: return launch_one<4, 1, D2S>(grid, lds, st, a);
     }
 }
 
@@ -1995,7 +2085,12 @@ extern "C" int mpg_debug_small_diag(unsigned* out2) {
 }
 #endif
 
-extern "C" int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d) {
+// the depth-to-space output of mpg_conv2d_fused_d2s (block size 2)
+struct D2SOut {
+    int cs, coff;
+};
+
+static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOut* d2s) {
     MPG_REQUIRE(d != nullptr, "mpg_conv2d_fused: null desc");
     MPG_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1, "mpg_conv2d_fused: bad shape %d x %d x %d", d->n, d->h, d->w);
     MPG_REQUIRE(d->cout >= 1 && d->cout <= 128, "mpg_conv2d_fused: cout %d not in 1..128", d->cout);
@@ -2005,7 +2100,8 @@ extern "C" int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d) {
                 "mpg_conv2d_fused: bad prec %d", d->prec);
     MPG_REQUIRE(d->act >= MPG_ACT_NONE && d->act <= MPG_ACT_TANH, "mpg_conv2d_fused: bad act %d", d->act);
     {   // small-channel layers: conv_small_kernel
-        bool small = d->cout <= 8 && !d->pixel_norm && d->post_add == nullptr && d->reserved == 0;
+        // (the depth-to-space store is an epilogue of the MFMA kernels only: such a launch stays on them)
+        bool small = d->cout <= 8 && !d->pixel_norm && d->post_add == nullptr && d->reserved == 0 && d2s == nullptr;
         for (int s = 0; s < d->nseg && small; ++s) small = d->seg[s].cin <= 8;
         if (small) {
             SmallArgs sa;
@@ -2129,17 +2225,43 @@ extern "C" int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d) {
     MPG_REQUIRE(lds <= 160 * 1024, "mpg_conv2d_fused: LDS budget %zu exceeds 160 KiB", lds);
     const dim3 grid((unsigned)nblk);
     hipError_t le;
-    if (f8) {
-        switch (nt) {
-            case 1: le = launch_f6<1>(grid, lds, (hipStream_t)stream, a); break;
-            case 2: le = launch_f6<2>(grid, lds, (hipStream_t)stream, a); break;
-            case 3: le = launch_f6<3>(grid, lds, (hipStream_t)stream, a); break;
-            default: le = launch_f6<4>(grid, lds, (hipStream_t)stream, a); break;
-        }
-    } else if (d->prec == MPG_PREC_F16X3)
-        le = launch_nt<3>(nt, grid, lds, (hipStream_t)stream, a);
-    else
-        le = launch_nt<1>(nt, grid, lds, (hipStream_t)stream, a);
+    if (d2s != nullptr) {
+        ConvArgsD2S ad;
+        ad.a = a;
+        ad.cs = d2s->cs;
+        ad.coff = d2s->coff;
+        ad.cg = d2s->cs / 8;
+        le = launch_conv<true>(d->prec, nt, grid, lds, (hipStream_t)stream, ad);
+    } else {
+        le = launch_conv<false>(d->prec, nt, grid, lds, (hipStream_t)stream, a);
+    }
     if (le != hipSuccess) return mpg::hip_check(le, "mpg_conv2d_fused: hipFuncSetAttribute(dynamic LDS)");
     MPG_LAUNCH_CHECK("conv_mfma_kernel");
+}
+
+extern "C" int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d) {
+    return conv2d_fused(stream, d, nullptr);
+}
+
+extern "C" int mpg_conv2d_fused_d2s(mpg_stream_t stream, const mpg_conv_desc* d, int r, int c_total, int co_off) {
+    MPG_REQUIRE(d != nullptr, "mpg_conv2d_fused_d2s: null desc");
+    MPG_REQUIRE(r == 2, "mpg_conv2d_fused_d2s: block size %d (only 2)", r);
+    MPG_REQUIRE(c_total >= 4 && c_total % 4 == 0, "mpg_conv2d_fused_d2s: %d channels are not a multiple of 4", c_total);
+    MPG_REQUIRE(co_off >= 0 && d->cout >= 1 && co_off + d->cout <= c_total,
+                "mpg_conv2d_fused_d2s: channels [%d, %d) outside 0..%d", co_off, co_off + d->cout, c_total);
+    MPG_REQUIRE(!d->pixel_norm && d->post_add == nullptr, "mpg_conv2d_fused_d2s: no pixel norm or post-add");
+    // the F16F6 kernel has no depth-to-space store (the shuffle's 1x1 contraction, K = C <= 256, runs as MPG_PREC_F16X3
+    // under the planner's rule anyway)
+    if (d->prec == MPG_PREC_F16F6) {
+        mpg::set_error("mpg_conv2d_fused_d2s: MPG_PREC_F16F6 has no depth-to-space store (use MPG_PREC_F16X3 / F16X1)");
+        return MPG_ERR_UNSUPPORTED;
+    }
+    const int cs = c_total / 4;
+    // a G8 group of 8 channels must stay inside one parity of the shuffle
+    MPG_REQUIRE(d->y_g8 == nullptr || (cs % 8 == 0 && co_off % 8 == 0 && d->cout % 8 == 0),
+                "mpg_conv2d_fused_d2s: G8 output needs c_total/4 (%d), co_off (%d) and cout (%d) multiples of 8", cs, co_off,
+                d->cout);
+    MPG_REQUIRE((size_t)4 * d->h * d->w < ((size_t)1 << 31), "mpg_conv2d_fused_d2s: %dx%d too large", d->h, d->w);
+    const D2SOut o = {cs, co_off};
+    return conv2d_fused(stream, d, &o);
 }

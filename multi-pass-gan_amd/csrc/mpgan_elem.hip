@@ -548,6 +548,38 @@ __global__ void depth_to_space_kernel(const float* __restrict__ x, int n, int h,
     y[idx] = x[(((size_t)b * h + q) * w + pp) * ((size_t)c_out * r * r) + (size_t)(i * r + j) * c_out + c];
 }
 
+// the adjoint of depth_to_space_kernel (its gradient): y[b, q, p, (i*r + j)*C + c] = x[b, r*q + i, r*p + j, c], one float4 of
+// 4 channels per thread (C % 4 == 0), stores in y order
+__global__ void space_to_depth4_kernel(const float4* __restrict__ x, int n, int h, int w, int c4, int r, float4* __restrict__ y) {
+    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+    const int oh = h / r, ow = w / r;
+    const size_t total = (size_t)n * oh * ow * r * r * c4;
+    if (idx >= total) return;
+    const int c = idx % c4;
+    size_t p = idx / c4;
+    const int k = p % (r * r); p /= r * r;
+    const int px = p % ow; p /= ow;
+    const int qy = p % oh;
+    const int b = p / oh;
+    const int i = k / r, j = k - i * r;
+    y[idx] = x[(((size_t)b * h + r * qy + i) * w + r * px + j) * c4 + c];
+}
+
+__global__ void space_to_depth_kernel(const float* __restrict__ x, int n, int h, int w, int c, int r, float* __restrict__ y) {
+    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+    const int oh = h / r, ow = w / r;
+    const size_t total = (size_t)n * oh * ow * r * r * c;
+    if (idx >= total) return;
+    const int ci = idx % c;
+    size_t p = idx / c;
+    const int k = p % (r * r); p /= r * r;
+    const int px = p % ow; p /= ow;
+    const int qy = p % oh;
+    const int b = p / oh;
+    const int i = k / r, j = k - i * r;
+    y[idx] = x[(((size_t)b * h + r * qy + i) * w + r * px + j) * c + ci];
+}
+
 }  // namespace
 
 extern "C" int mpg_conv2d_direct(mpg_stream_t stream, const float* x, int n, int h, int w, int cin,
@@ -830,4 +862,18 @@ extern "C" int mpg_depth_to_space(mpg_stream_t stream, const float* x, int n, in
     hipLaunchKernelGGL(depth_to_space_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, x, n, h, w, c / (r * r),
                        r, y);
     MPG_LAUNCH_CHECK("depth_to_space_kernel");
+}
+
+extern "C" int mpg_space_to_depth(mpg_stream_t stream, const float* x, int n, int h, int w, int c, int r, float* y) {
+    MPG_REQUIRE(x && y, "mpg_space_to_depth: null pointer");
+    MPG_REQUIRE(n >= 1 && c >= 1 && r >= 1 && h >= r && w >= r && h % r == 0 && w % r == 0,
+                "mpg_space_to_depth: %dx%d is not a multiple of the block size %d", h, w, r);
+    const size_t total = (size_t)n * h * w * c;
+    if (c % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
+        hipLaunchKernelGGL(space_to_depth4_kernel, dim3(grid_for(total / 4)), dim3(BLK), 0, (hipStream_t)stream,
+                           reinterpret_cast<const float4*>(x), n, h, w, c / 4, r, reinterpret_cast<float4*>(y));
+        MPG_LAUNCH_CHECK("space_to_depth4_kernel");
+    }
+    hipLaunchKernelGGL(space_to_depth_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, x, n, h, w, c, r, y);
+    MPG_LAUNCH_CHECK("space_to_depth_kernel");
 }

@@ -108,7 +108,8 @@ class Generator(object):
                                   upsampling_mode=2 if first else 1, upsampleMode=c.get("upsample_mode", 1),
                                   filterSize=c["filter_size"], start_fms=c["start_fms"], max_fms=c["max_fms"],
                                   first_nn_arch=c.get("first_nn_arch", False), use_res_net=c.get("use_res_net", True),
-                                  pixel_norm=c.get("pixel_norm", True), addBicubicUpsample=c.get("add_bicubic", True))
+                                  pixel_norm=c.get("pixel_norm", True), addBicubicUpsample=c.get("add_bicubic", True),
+                                  usePixelShuffle=c.get("pixel_shuffle", False))
                 self.sampler = arch.growing_gen(src, acfg, use_batch_norm=c.get("batch_norm", False), output=True)
             else:
                 raise ValueError("unknown generator kind %r" % (kind,))

@@ -231,6 +231,100 @@ def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=Fal
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
+def conv2d_fused_d2s(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, out=None, want_f32=True, want_g8=False):
+    """GAN.pixel_shuffle (GAN.py:554-560) with the shuffle in the store: depth_to_space(conv(...) + bias, 2) of a
+    c_total-channel convolution given as 128-wide output chunks [(segments, co_off), ...] (each chunk's weights packed
+    for its own output channels), one mpg_conv2d_fused_d2s launch per chunk into the same tensors.  Returns fp32
+    [N, 2H, 2W, c_total/4] and / or G8, like conv2d_fused.  Raises MpgError where the launch refuses (G8 output with
+    c_total/4 not a multiple of 8): the caller then runs conv2d_fused and depth_to_space."""
+    lib = _lib.load()
+    if c_total % 4 or not chunks:
+        raise _lib.MpgError("conv2d_fused_d2s: %d channels are not a multiple of 4" % c_total)
+    h, w = out_hw
+    segs0 = chunks[0][0]
+    n, dev, cs = segs0[0].x.n, segs0[0].x.buf.device, c_total // 4
+    if want_g8 and cs % 8:
+        raise _lib.MpgError("conv2d_fused_d2s: G8 output of %d channels (not a multiple of 8)" % cs)
+    co = 0
+    for segments, co_off in sorted(chunks, key=lambda ch: ch[1]):
+        if co_off != co:
+            break
+        co += segments[0].packed.cout
+    if co != c_total:
+        raise _lib.MpgError("conv2d_fused_d2s: the chunks do not cover channels 0..%d once" % c_total)
+    if bias is not None:
+        bias = _dev(bias, "bias")
+        if bias.numel() != c_total:
+            raise _lib.MpgError("conv2d_fused_d2s: bias has %d entries, expected %d" % (bias.numel(), c_total))
+    y = y8 = None
+    if out is not None:
+        want_f32 = True
+    if want_f32:
+        y = torch.empty((n, 2 * h, 2 * w, cs), dtype=torch.float32, device=dev) if out is None else _dev(out, "out")
+        if tuple(y.shape) != (n, 2 * h, 2 * w, cs):
+            raise _lib.MpgError("conv2d_fused_d2s: out has shape %s" % (tuple(y.shape),))
+    if want_g8:
+        y8 = G8.empty(n, 2 * h, 2 * w, cs, dev, G8_F16)
+    outs = [o for o in (y, y8) if o is not None]
+    if not outs:
+        raise _lib.MpgError("conv2d_fused_d2s: no output requested")
+    for segments, co_off in chunks:
+        cw = segments[0].packed.cout
+        d = _conv_desc(segments, out_hw, bias[co_off:co_off + cw] if bias is not None else None, act, leak)
+        if y is not None:
+            d.y = y.data_ptr()
+        if y8 is not None:
+            d.y_g8 = y8.buf.data_ptr()
+        _lib.check(lib.mpg_conv2d_fused_d2s(_stream(), ctypes.byref(d), 2, c_total, co_off), "mpg_conv2d_fused_d2s")
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def _conv_desc(segments, out_hw, bias, act, leak):
+    """the ConvDesc of conv2d_fused's launch without outputs (segments, bias, activation)"""
+    if not 1 <= len(segments) <= _lib.MAX_SEG:
+        raise _lib.MpgError("conv2d_fused: %d segments (1..%d supported)" % (len(segments), _lib.MAX_SEG))
+    p0 = segments[0].packed
+    h, w = out_hw
+    n = segments[0].x.n
+    d = _lib.ConvDesc()
+    d.n, d.h, d.w, d.cout, d.nseg = n, h, w, p0.cout, len(segments)
+    for i, s in enumerate(segments):
+        g8, pk = s.x, s.packed
+        if (pk.cout, pk.prec) != (p0.cout, p0.prec):
+            raise _lib.MpgError("conv2d_fused: segments packed with different cout/prec")
+        if g8.n != n or g8.h << s.up_log2 != h or g8.w << s.up_log2 != w:
+            raise _lib.MpgError("conv2d_fused: segment %d input %dx%dx%d does not match output %dx%dx%d (up 2^%d)"
+                                % (i, g8.n, g8.h, g8.w, n, h, w, s.up_log2))
+        if s.g_off * 8 + pk.cin > g8.c:
+            raise _lib.MpgError("conv2d_fused: segment %d channel window [%d,%d) exceeds %d"
+                                % (i, s.g_off * 8, s.g_off * 8 + pk.cin, g8.c))
+        g = d.seg[i]
+        g.x, g.wpack = g8.buf.data_ptr(), pk.buf.data_ptr()
+        g.cin, g.cgroups, g.g_off = pk.cin, g8.groups, s.g_off
+        g.kh, g.kw, g.up_log2 = pk.kh, pk.kw, s.up_log2
+        g.pad_hi = s.pad_hi
+    if bias is not None:
+        b = bias.contiguous()
+        if b.numel() != p0.cout:
+            raise _lib.MpgError("conv2d_fused: bias has %d entries, cout is %d" % (b.numel(), p0.cout))
+        d.bias = b.data_ptr()
+    d.act, d.leak = _lib.act_id(act), leak
+    d.prec = p0.prec
+    return d
+
+
+def space_to_depth(x, r):
+    """the adjoint of depth_to_space (mpg_space_to_depth): [N,H,W,C] -> [N,H/r,W/r,C*r^2]"""
+    lib = _lib.load()
+    x = _dev(x, "x")
+    n, h, w, c = x.shape
+    if h % r or w % r:
+        raise _lib.MpgError("space_to_depth: %dx%d is not a multiple of %d" % (h, w, r))
+    y = torch.empty((n, h // r, w // r, c * r * r), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mpg_space_to_depth(_stream(), _ptr(x), n, h, w, c, r, _ptr(y)), "mpg_space_to_depth")
+    return y
+
+
 PAIR_MAX_CIN = 4
 
 

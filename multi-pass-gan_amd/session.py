@@ -9,7 +9,9 @@ Fusion rules (all arithmetic stays in the kernels of libmpgan_hip.so):
   * a conv reading ``concat`` / nearest ``resize`` / channel ``slice`` nodes reads
     their sources directly (multipassGAN-out.py:357; GAN.py:517);
   * ``chain + tensor`` with a linear chain on one side is the epilogue post-add
-    (addBicubicUpsample, multipassGAN-out.py:327-332).
+    (addBicubicUpsample, multipassGAN-out.py:327-332);
+  * ``depth_to_space(2)`` of a linear 1x1 convolution with 4C outputs, C % 8 == 0 (GAN.pixel_shuffle,
+    GAN.py:554-560), is one ``mpg_conv2d_fused_d2s`` launch per 128 outputs writing the shuffled tensor.
 Everything else falls back to one kernel per node.
 """
 import re
@@ -244,7 +246,7 @@ class Session(object):
                     return env[node.id]
                 plan.steps.append((n, feed))
                 return
-            fused = self._match_fused(n, single_use)
+            fused = self._match_d2s(n, single_use) or self._match_fused(n, single_use)
             if fused is not None:
                 deps, fn = fused
                 fused_steps.append((n, fn))
@@ -425,19 +427,7 @@ class Session(object):
         out_hw = (n.shape[1], n.shape[2])
 
         lead = terms[0].conv.inputs[1].attrs["var"]
-        prec = self.prec
-        for pat, pr in self.prec_map:
-            if pat in lead:
-                prec = pr
-        if prec == ops.PREC_F16F6 and not ops.f6_available(
-                cout, [(sg[3].conv.inputs[1].shape[0], sg[3].conv.inputs[1].shape[1], sg[5]) for sg in segs]):
-            prec = ops.PREC_F16X3      # shapes the F16F6 kernels do not cover keep the fp16 split
-        # short contractions on wide outputs (8 -> 128 5x5 of resBlock 1: K = 200, four cout tiles): a launch of 4 weight
-        # stages per tile is all prologue, barriers and conversions; the three-product fp16 kernel (8-KB stages, no
-        # conversions) is faster there AND fp32-grade (109 against 124 us per 8 slices, profiles/r03/kloop_variants.md)
-        total_k = sum(sg[3].conv.inputs[1].shape[0] * sg[3].conv.inputs[1].shape[1] * sg[5] for sg in segs)
-        if prec == ops.PREC_F16F6 and total_k <= ops.F16F6_MIN_K and cout > 8:
-            prec = ops.PREC_F16X3
+        prec = self._launch_prec(lead, cout, segs)
 
         emit = {"f32": True, "g8": False}
 
@@ -483,6 +473,82 @@ class Session(object):
                          for (src, c_off_src, up, term, w_off, cin) in segs],
         }
         return deps, run
+
+    def _launch_prec(self, lead, cout, segs):
+        """the precision of a fused launch of `cout` outputs over segments `segs` whose leading weight is `lead`"""
+        prec = self.prec
+        for pat, pr in self.prec_map:
+            if pat in lead:
+                prec = pr
+        if prec == ops.PREC_F16F6 and not ops.f6_available(
+                cout, [(sg[3].conv.inputs[1].shape[0], sg[3].conv.inputs[1].shape[1], sg[5]) for sg in segs]):
+            prec = ops.PREC_F16X3      # shapes the F16F6 kernels do not cover keep the fp16 split
+        # short contractions on wide outputs (8 -> 128 5x5 of resBlock 1: K = 200, four cout tiles): a launch of 4 weight
+        # stages per tile is all prologue, barriers and conversions; the three-product fp16 kernel (8-KB stages, no
+        # conversions) is faster there AND fp32-grade (109 against 124 us per 8 slices, profiles/r03/kloop_variants.md)
+        total_k = sum(sg[3].conv.inputs[1].shape[0] * sg[3].conv.inputs[1].shape[1] * sg[5] for sg in segs)
+        if prec == ops.PREC_F16F6 and total_k <= ops.F16F6_MIN_K and cout > 8:
+            prec = ops.PREC_F16X3
+        return prec
+
+    # ---- pixel shuffle: depth_to_space(2) of a linear 1x1 convolution, the shuffle in the convolution's store -------
+    def _match_d2s(self, n, single_use):
+        """depth_to_space(bias_add(conv2d 1x1)) with C = 4C' / 4 a multiple of 8 (GAN.pixel_shuffle, GAN.py:554-560):
+        one mpg_conv2d_fused_d2s launch per 128 output channels, whatever the width of the convolution"""
+        if n.op != "depth_to_space" or n.attrs["r"] != 2:
+            return None
+        bias = n.inputs[0]
+        if bias.op != "bias_add" or not single_use(bias) or not single_use(bias.inputs[0]):
+            return None
+        conv = bias.inputs[0]
+        if conv.op != "conv2d" or conv.attrs["stride"] != (1, 1) or conv.inputs[1].op != "variable":
+            return None
+        kh, kw, cin, c_total = conv.inputs[1].shape
+        if (kh, kw) != (1, 1) or c_total % 32:
+            return None
+        term = _Term(conv, bias, None)
+        segs = self._segments_of(term)
+        if segs is None or len(segs) > _lib.MAX_SEG:
+            return None
+        lead = conv.inputs[1].attrs["var"]
+        chunks = [(co, min(128, c_total - co)) for co in range(0, c_total, 128)]
+        precs = [self._launch_prec(lead, cw, segs) for _, cw in chunks]
+        if ops.PREC_F16F6 in precs:      # the F16F6 kernel has no depth-to-space store: conv + standalone shuffle
+            return None
+        out_hw = (conv.shape[1], conv.shape[2])
+        emit = {"f32": True, "g8": False}
+
+        def run(env):
+            launches = []
+            for (co, cw), prec in zip(chunks, precs):
+                seg_objs = []
+                for (src, c_off_src, up, t, w_off, ci) in segs:
+                    pk = self._packed_chunk(t, w_off, ci, prec, co, cw)
+                    g8, off = self._g8(env, src, c_off_src, ci, ops.flavour_for(prec))
+                    seg_objs.append(ops.Segment(g8, pk, off, up))
+                launches.append((seg_objs, co))
+            dst = env.get("__out__") if emit["f32"] else None
+            if dst is not None:
+                dst = dst.view(-1, *n.shape[1:])
+            res = ops.conv2d_fused_d2s(launches, out_hw, c_total, bias=self._bias_for([term]), want_f32=emit["f32"],
+                                       want_g8=emit["g8"], out=dst)
+            res = list(res) if isinstance(res, tuple) else [res]
+            out = {"f32": None, "g8": {}}
+            if emit["f32"]:
+                out["f32"] = res.pop(0)
+            if emit["g8"]:
+                out["g8"][ops.G8_F16] = res.pop(0)
+            return out
+
+        run.emit = emit
+        run.parts = None
+        run.info = {
+            "kind": "conv2d_fused_d2s", "cout": c_total // 4, "conv_cout": c_total, "launches": len(chunks), "act": None,
+            "pixel_norm": False, "prec": precs[0], "post_add": None, "post_add_id": None,
+            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=ci, up_log2=up, w_off=w_off, kernel=(1, 1),
+                              weight=lead) for (src, c_off_src, up, t, w_off, ci) in segs],
+        }
+        return [s[0] for s in segs], run
 
     def plan_summary(self, fetch):
         """the launch plan of `fetch` as a list of dicts (no GPU needed): one entry per kernel launch"""
@@ -593,6 +659,16 @@ class Session(object):
             scale, _ = self._bn_scale_shift(term)
             pk = ops.pack_conv_weights(w, wscale=term.conv.attrs["wscale"], cout_scale=scale, c_off=w_off, cin=cin,
                                        prec=prec)
+            self._packed[key] = pk
+        return pk
+
+    def _packed_chunk(self, term, w_off, cin, prec, co, cw):
+        """output channels [co, co + cw) of a wide convolution, packed as a launch of their own (no batch norm)"""
+        key = ("pack", term.conv.id, w_off, cin, prec, co, cw)
+        pk = self._packed.get(key)
+        if pk is None:
+            w = self.vars.get(term.conv.inputs[1].attrs["var"])[..., co:co + cw].contiguous()
+            pk = ops.pack_conv_weights(w, wscale=term.conv.attrs["wscale"], c_off=w_off, cin=cin, prec=prec)
             self._packed[key] = pk
         return pk
 

@@ -438,6 +438,31 @@ class MinibatchStddevBwd2Fn(torch.autograd.Function):
         return g_dy, g_x, None
 
 
+class DepthToSpaceFn(torch.autograd.Function):
+    """tf.depth_to_space(x, r) of GAN.pixel_shuffle (GAN.py:554-560).  Linear: its gradient is the adjoint
+    space_to_depth, whose gradient is depth_to_space again, so gradients of any order use the two copy kernels."""
+
+    @staticmethod
+    def forward(ctx, x, r):
+        ctx.r = r
+        return ops.depth_to_space(x.detach().contiguous(), r)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return SpaceToDepthFn.apply(dy, ctx.r), None
+
+
+class SpaceToDepthFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dy, r):
+        ctx.r = r
+        return ops.space_to_depth(dy.detach().contiguous(), r)
+
+    @staticmethod
+    def backward(ctx, g):
+        return DepthToSpaceFn.apply(g, ctx.r), None
+
+
 def space_to_depth2(x):
     """[N,H,W,C] -> [N,H/2,W/2,4C], channel (r*2+s)*C + c holds x[2Y+r, 2X+s, c]"""
     n, h, w, c = x.shape
@@ -752,6 +777,8 @@ class TrainSession(object):
             if x.requires_grad and self._higher(n):
                 return MinibatchStddev2Fn.apply(x, n.attrs["group_size"])
             return MinibatchStddevFn.apply(x, n.attrs["group_size"])
+        if op == "depth_to_space":
+            return DepthToSpaceFn.apply(ev(n.inputs[0]), n.attrs["r"])
         if op == "resize":
             x = ev(n.inputs[0])
             if n.attrs["method"] == 1:
