@@ -197,16 +197,35 @@ def lrelu(x, leak=0.2, name="lrelu"):
     return Node("act", [x], shape=x.shape, act="lrelu", leak=leak)
 
 
-def activation_name(fn):
+def match_layer(n, single_use, convs=("conv2d",)):
+    """n = [act](batch_norm?(bias_add?(conv))) with conv.op in `convs` -> (conv, bias, bn, act, leak) or None.
+    The root n may have any number of consumers; every node below it must satisfy single_use."""
+    cur, bias, bn, act, leak = n, None, None, None, 0.2
+    if cur.op == "act":
+        act, leak, cur = cur.attrs["act"], cur.attrs.get("leak", 0.2), cur.inputs[0]
+        if not single_use(cur):
+            return None
+    if cur.op == "batch_norm":
+        bn, cur = cur, cur.inputs[0]
+        if not single_use(cur):
+            return None
+    if cur.op == "bias_add":
+        bias, cur = cur, cur.inputs[0]
+        if not single_use(cur):
+            return None
+    return (cur, bias, bn, act, leak) if cur.op in convs else None
+
+
+def activation_name(activation):
     """Map an activation callable (as passed to GAN.convolutional_layer) to a kernel id."""
-    if fn is None:
+    if activation is None:
         return None
-    if isinstance(fn, str):
-        return fn
-    nm = getattr(fn, "__name__", "")
+    if isinstance(activation, str):
+        return activation
+    nm = getattr(activation, "__name__", "")
     if nm in ("relu", "lrelu", "tanh"):
         return nm
-    raise GraphError("unsupported activation function %r" % (fn,))
+    raise GraphError("unsupported activation function %r" % (activation,))
 
 
 class Scalar(object):

@@ -84,6 +84,7 @@ class Generator(object):
     def __init__(self, kind, cfg, params=None, prec=None, device="cuda:0", seed=777, prec_map=None):
         prec = ops.INFERENCE_PREC if prec is None else prec
         self.kind, self.cfg = kind, dict(cfg)
+        self._clones = []          # further copies for the pass lanes (clones())
         prev = G.get_default_graph()
         self.graph = G.reset_default_graph()
         try:
@@ -126,7 +127,7 @@ class Generator(object):
 
     def clones(self, n):
         """n further copies for the pass lanes, made once"""
-        have = self.__dict__.setdefault("_clones", [])
+        have = self._clones
         while len(have) < n:
             have.append(self.clone())
         for c in have:

@@ -100,11 +100,32 @@ def _is_pow2(v):
     return v >= 1 and (v & (v - 1)) == 0
 
 
+class _Step(object):
+    """One entry of a launch plan: `run(env)` computes `node` from the env entries of `deps`.  A fused convolution
+    launch also carries `info` (its plan_summary entry), `emit` (which output formats it writes) and, where it may
+    still become half of a small pair, `parts` (its operands); these are None on every other step."""
+
+    __slots__ = ("node", "deps", "run", "info", "emit", "parts")
+
+    def __init__(self, node, deps, run, info=None, emit=None, parts=None):
+        self.node, self.deps, self.run, self.info, self.emit, self.parts = node, deps, run, info, emit, parts
+
+    def __call__(self, env):
+        return self.run(env)
+
+
 class _Plan(object):
     def __init__(self):
-        self.steps = []       # (node, callable(env) -> tensor)
-        self.last_use = {}    # node id -> index of the last step reading it
+        self.steps = []       # _Step, in execution order
         self.free_after = []  # per step: node ids whose tensors are dead afterwards
+
+
+def seeded_normal(gens, n, ref, seed):
+    """the draw of random_normal node `n`, shaped like `ref` up to the channels; `gens` keeps one generator per node"""
+    if n.id not in gens:
+        gens[n.id] = torch.Generator(device=ref.device).manual_seed(1000003 * seed + 17)
+    shape = tuple(ref.shape[:-1]) + (n.shape[-1],)
+    return torch.randn(shape, generator=gens[n.id], device=ref.device, dtype=torch.float32) * n.attrs["stddev"]
 
 
 class Session(object):
@@ -119,6 +140,8 @@ class Session(object):
         self._packed = {}
         self._folded = {}
         self._cache_version = -1
+        self._scalars = {}       # Scalar node -> value fed to the current run()
+        self._noise_gen = {}     # random_normal node id -> its generator
         # measurement hook: when `tap` is a substring of a fused launch's leading weight name, the launch's
         # operands (G8 segments taken from the running pipeline, bias, epilogue flags) are kept in `tapped`
         # so that bench.py can re-issue exactly that launch on exactly those activations
@@ -160,12 +183,13 @@ class Session(object):
         env = {}
         for node, t in feeds.items():
             env[node.id] = t
-        producer = self._producer_of(fetch) if out is not None else None
-        for i, (node, fn) in enumerate(plan.steps):
-            env["__out__"] = out if (producer is not None and node.id == producer.id) else None
-            env[node.id] = fn(env)
-            for nid in plan.free_after[i]:
-                env.pop(nid, None)
+        producer = self._producer_of(fetch).id if out is not None else None
+        for step, dead in zip(plan.steps, plan.free_after):
+            nid = step.node.id
+            env["__out__"] = out if nid == producer else None
+            env[nid] = step.run(env)
+            for d in dead:
+                env.pop(d, None)
         res = self._f32(env, fetch)
         if out is not None and res.data_ptr() != out.data_ptr():
             out.view(-1).copy_(res.reshape(-1))
@@ -208,7 +232,6 @@ class Session(object):
     # ------------------------------------------------------------------ compile
     def _compile(self, fetch):
         consumers = {}
-        order = []
         seen = set()
 
         def visit(n):
@@ -218,14 +241,11 @@ class Session(object):
             for i in n.inputs:
                 consumers.setdefault(i.id, []).append(n)
                 visit(i)
-            order.append(n)
 
         visit(fetch)
-        self._consumers = consumers
-        self._fetch = fetch
         plan = _Plan()
         done = set()
-        fused_steps = []       # (node, run) of every fused convolution
+        fused = []             # the steps that are fused convolutions, consumer before producer
         need_f32 = {fetch.id}  # nodes somebody reads as fp32 NHWC
         need_g8 = set()        # (node id, flavour) of fused outputs read by another fused convolution
 
@@ -237,71 +257,86 @@ class Session(object):
                 return
             done.add(n.id)
             if n.op == "variable":
-                plan.steps.append((n, lambda env, nm=n.attrs["var"]: self.vars.get(nm)))
+                plan.steps.append(_Step(n, [], lambda env, nm=n.attrs["var"]: self.vars.get(nm)))
                 return
             if n.op == "placeholder":
                 def feed(env, node=n):
                     if node.id not in env:
                         raise G.GraphError("placeholder %s was not fed" % node.name)
                     return env[node.id]
-                plan.steps.append((n, feed))
+                plan.steps.append(_Step(n, [], feed))
                 return
-            fused = self._match_d2s(n, single_use) or self._match_fused(n, single_use)
-            if fused is not None:
-                deps, fn = fused
-                fused_steps.append((n, fn))
+            step = self._match_d2s(n, single_use) or self._match_fused(n, single_use)
+            if step is not None:
+                fused.append(step)
             else:
-                deps, fn = self._fallback(n, single_use)
-                for d in deps:
-                    need_f32.add(d.id)
-            for d in deps:
+                step = self._fallback(n, single_use)
+                need_f32.update(d.id for d in step.deps)
+            for d in step.deps:
                 emit(d)
-            idx = len(plan.steps)
-            plan.steps.append((n, fn))
-            for d in deps:
-                plan.last_use[d.id] = idx
+            plan.steps.append(step)
 
         emit(fetch)
-        self._fuse_small_pairs(plan, fused_steps, consumers, fetch)
-        fused_steps = [(n, fn) for n, fn in fused_steps if fn.info.get("kind") != "fused_into_next"]
-        fused_ids = set(n.id for n, _ in fused_steps)
-        for n, fn in fused_steps:
-            fl = ops.flavour_for(fn.info["prec"])
-            for seg in fn.info["segments"]:
+        absorbed = self._fuse_small_pairs(fused, consumers, fetch)
+        plan.steps = [s for s in plan.steps if s.node.id not in absorbed]
+        fused = [s for s in fused if s.node.id not in absorbed]
+        fused_ids = set(s.node.id for s in fused)
+        for s in fused:
+            fl = ops.flavour_for(s.info["prec"])
+            for seg in s.info["segments"]:
                 if seg["src_id"] in fused_ids and seg["c_off"] % 8 == 0:
                     need_g8.add((seg["src_id"], fl))
                 else:
                     need_f32.add(seg["src_id"])
-            if fn.info["post_add_id"] is not None:
-                need_f32.add(fn.info["post_add_id"])
-        for n, fn in fused_steps:
-            fn.emit["g8"] = (n.id, ops.G8_F16) in need_g8
-            fn.emit["f32"] = n.id in need_f32 or not fn.emit["g8"]
+            if s.info["post_add_id"] is not None:
+                need_f32.add(s.info["post_add_id"])
+        for s in fused:
+            s.emit["g8"] = (s.node.id, ops.G8_F16) in need_g8
+            s.emit["f32"] = s.node.id in need_f32 or not s.emit["g8"]
         # variables, placeholders and the fetch stay alive; everything else dies after its last reader
+        last_use = {}
+        for i, s in enumerate(plan.steps):
+            for d in s.deps:
+                last_use[d.id] = i
         plan.free_after = [[] for _ in plan.steps]
-        keep = set(n.id for n, _ in plan.steps if n.op in ("variable", "placeholder"))
+        keep = set(s.node.id for s in plan.steps if s.node.op in ("variable", "placeholder"))
         keep.add(fetch.id)
-        for nid, idx in plan.last_use.items():
+        for nid, idx in last_use.items():
             if nid not in keep:
                 plan.free_after[idx].append(nid)
         return plan
 
+    # ---- what the three fused launch kinds share ------------------------------------------------------------
+    @staticmethod
+    def _dst(env, emit, shape):
+        """the buffer run_device was given for this step's fp32 result, viewed as [N] + shape[1:], or None"""
+        out = env.get("__out__") if emit["f32"] else None
+        return out if out is None else out.view(-1, *shape[1:])
+
+    @staticmethod
+    def _boxed(res, emit):
+        """the env entry of a fused launch from what its ops call returned: fp32 first, then G8, as `emit` asked"""
+        res = list(res) if isinstance(res, tuple) else [res]
+        f32 = res.pop(0) if emit["f32"] else None
+        return {"f32": f32, "g8": {ops.G8_F16: res.pop(0)} if emit["g8"] else {}}
+
     # ---- residual blocks of small-channel convolutions: two launches -> one -------------------------------
-    def _fuse_small_pairs(self, plan, fused_steps, consumers, fetch):
+    def _fuse_small_pairs(self, fused, consumers, fetch):
         """relu(convB(relu(convA(x))) + conv1x1(x)) with <= 8 channels everywhere (resBlock 0 and 3 of gen_resnet,
         multipassGAN-4x.py:505-526,560,564) was planned as two conv_small launches with the middle tensor going through
-        HBM; here launch A is dropped and launch B replaced by one mpg_conv2d_small_pair call."""
-        by_id = dict((n.id, (n, fn)) for n, fn in fused_steps)
-        index = dict((n.id, i) for i, (n, _) in enumerate(plan.steps))
-        for n2, fn2 in list(fused_steps):
-            p2 = getattr(fn2, "parts", None)
+        HBM; here the step of launch B becomes one mpg_conv2d_small_pair call and launch A is dropped: returns the node
+        ids of the dropped steps.  Both halves of a pair lose their `parts`, so neither joins another pair."""
+        by_id = dict((s.node.id, s) for s in fused)
+        absorbed = set()
+        for s2 in fused:
+            p2 = s2.parts
             if p2 is None or p2["pn"] or p2["post_add"] is not None or p2["cout"] > 8 or not 1 <= len(p2["segs"]) <= 2:
                 continue
             src1, c_off1, up1, term_b, w_off_b, cin_b = p2["segs"][0]
             if src1.id not in by_id or c_off1 != 0 or up1 != 0 or w_off_b != 0:
                 continue
-            n1, fn1 = by_id[src1.id]
-            p1 = getattr(fn1, "parts", None)
+            s1 = by_id[src1.id]
+            n1, p1 = s1.node, s1.parts
             if (p1 is None or n1 is fetch or len(consumers.get(n1.id, [])) != 1 or p1["pn"] or p1["post_add"] is not None
                     or len(p1["segs"]) != 1 or p1["prec"] != p2["prec"] or p1["cout"] != cin_b):
                 continue
@@ -317,71 +352,45 @@ class Session(object):
             ks = tuple(term_s.conv.inputs[1].shape[:2]) if term_s is not None else None
             if not ops.small_pair_ok(cin_a, p1["cout"], p2["cout"], ka, kb, ks, planner=True):
                 continue
-            emit2 = fn2.emit
+            self._become_pair(s1, s2, term_s)
+            absorbed.add(n1.id)
+        return absorbed
 
-            def run(env, src0=src0, c_off0=c_off0, up0=up0, cin_a=cin_a, term_a=term_a, term_b=term_b, term_s=term_s,
-                    p1=p1, p2=p2, emit2=emit2):
-                prec = p2["prec"]
-                pk_a = self._packed_for(term_a, 0, cin_a, prec)
-                pk_b = self._packed_for(term_b, 0, p1["cout"], prec)
-                pk_s = self._packed_for(term_s, 0, cin_a, prec) if term_s is not None else None
-                g8, off = self._g8(env, src0, c_off0, cin_a, ops.G8_F16)
-                res = ops.conv2d_small_pair(g8, off, up0, pk_a, pk_b, pk_s, p2["out_hw"], bias_a=self._bias_for(p1["terms"]),
-                                            act_a=p1["act"], leak_a=p1["leak"], bias_b=self._bias_for(p2["terms"]),
-                                            act_b=p2["act"], leak_b=p2["leak"], want_f32=emit2["f32"], want_g8=emit2["g8"],
-                                            out=env.get("__out__") if emit2["f32"] else None)
-                res = list(res) if isinstance(res, tuple) else [res]
-                out = {"f32": None, "g8": {}}
-                if emit2["f32"]:
-                    out["f32"] = res.pop(0)
-                if emit2["g8"]:
-                    out["g8"][ops.G8_F16] = res.pop(0)
-                return out
+    def _become_pair(self, s1, s2, term_s):
+        """turn step s2 (launch B) into the conv2d_small_pair launch of s1's convolution, s2's and the shortcut term_s"""
+        p1, p2, emit = s1.parts, s2.parts, s2.emit
+        src0, c_off0, up0, term_a, _, cin_a = p1["segs"][0]
+        term_b, prec = p2["segs"][0][3], p2["prec"]
 
-            run.emit = emit2
-            run.parts = None
-            run.info = dict(fn2.info)
-            run.info["kind"] = "conv2d_small_pair"
-            run.info["cmid"] = p1["cout"]
-            run.info["segments"] = [dict(fn1.info["segments"][0], role="conv_a")] + [
-                dict(sg, role="shortcut") for sg in fn2.info["segments"][1:]]
-            run.info["act_a"] = p1["act"]
+        def run(env):
+            pk_a = self._packed_for(term_a, 0, cin_a, prec)
+            pk_b = self._packed_for(term_b, 0, p1["cout"], prec)
+            pk_s = self._packed_for(term_s, 0, cin_a, prec) if term_s is not None else None
+            g8, off = self._g8(env, src0, c_off0, cin_a, ops.G8_F16)
+            return self._boxed(ops.conv2d_small_pair(
+                g8, off, up0, pk_a, pk_b, pk_s, p2["out_hw"], bias_a=self._bias_for(p1["terms"]), act_a=p1["act"],
+                leak_a=p1["leak"], bias_b=self._bias_for(p2["terms"]), act_b=p2["act"], leak_b=p2["leak"],
+                want_f32=emit["f32"], want_g8=emit["g8"], out=self._dst(env, emit, s2.node.shape)), emit)
 
-            def skipped(env):
-                return None
-            skipped.info = {"kind": "fused_into_next"}
-            plan.steps[index[n1.id]] = (n1, skipped)
-            plan.steps[index[n2.id]] = (n2, run)
-            # the block input is now read by the second launch
-            plan.last_use[src0.id] = max(plan.last_use.get(src0.id, 0), index[n2.id])
-            fused_steps[fused_steps.index((n1, fn1))] = (n1, skipped)
-            fused_steps[fused_steps.index((n2, fn2))] = (n2, run)
-            del by_id[n1.id]
+        segments = [dict(s1.info["segments"][0], role="conv_a")] + [dict(sg, role="shortcut") for sg in s2.info["segments"][1:]]
+        s2.info = dict(s2.info, kind="conv2d_small_pair", cmid=p1["cout"], segments=segments, act_a=p1["act"])
+        s2.run, s2.deps = run, [src0]      # the block input is now read by the second launch
+        s1.parts = s2.parts = None
 
     # ---- pattern matching -------------------------------------------------
     def _match_term(self, n, single_use):
         """bn?(bias_add?(conv2d)) with stride 1, cout <= 128, k <= 7.  The root n may have any
         number of consumers (the caller decides); every inner node must feed this chain only."""
-        bn = bias = None
-        cur = n
-        if cur.op == "batch_norm":
-            if cur.attrs["training"]:
-                return None
-            bn = cur
-            cur = cur.inputs[0]
-            if not single_use(cur):
-                return None
-        if cur.op == "bias_add":
-            bias = cur
-            cur = cur.inputs[0]
-            if not single_use(cur):
-                return None
-        if cur.op != "conv2d" or cur.attrs["stride"] != (1, 1):
+        m = G.match_layer(n, single_use)
+        if m is None:
             return None
-        kh, kw, cin, cout = cur.inputs[1].shape
-        if cout > 128 or kh > 7 or kw > 7 or cur.inputs[1].op != "variable":
+        conv, bias, bn, act, _ = m
+        if act is not None or (bn is not None and bn.attrs["training"]) or conv.attrs["stride"] != (1, 1):
             return None
-        return _Term(cur, bias, bn)
+        kh, kw, cin, cout = conv.inputs[1].shape
+        if cout > 128 or kh > 7 or kw > 7 or conv.inputs[1].op != "variable":
+            return None
+        return _Term(conv, bias, bn)
 
     def _match_lin(self, n, single_use, top=True):
         if n.op == "add":
@@ -431,7 +440,7 @@ class Session(object):
 
         emit = {"f32": True, "g8": False}
 
-        def run(env, segs=segs, terms=terms, prec=prec):
+        def run(env):
             seg_objs = []
             for (src, c_off_src, up, term, w_off, cin) in segs:
                 pk = self._packed_for(term, w_off, cin, prec)
@@ -446,25 +455,15 @@ class Session(object):
             if timed:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record()
-            dst = env.get("__out__") if emit["f32"] else None
-            if dst is not None:
-                dst = dst.view(seg_objs[0].x.n, out_hw[0], out_hw[1], cout)
             res = ops.conv2d_fused(seg_objs, out_hw, bias=bias, act=act, leak=leak, pixel_norm=pn, pn_eps=pn_eps,
-                                   post_add=pa, want_f32=emit["f32"], want_g8=emit["g8"], out=dst)
+                                   post_add=pa, want_f32=emit["f32"], want_g8=emit["g8"], out=self._dst(env, emit, n.shape))
             if timed:
                 ev[1].record()
                 self.tap_events.append(ev)
-            res = list(res) if isinstance(res, tuple) else [res]
-            out = {"f32": None, "g8": {}}
-            if emit["f32"]:
-                out["f32"] = res.pop(0)
-            if emit["g8"]:
-                out["g8"][ops.G8_F16] = res.pop(0)
-            return out
+            return self._boxed(res, emit)
 
-        run.emit = emit
-        run.parts = dict(segs=segs, terms=terms, act=act, leak=leak, pn=pn, post_add=post_add, prec=prec, cout=cout, out_hw=out_hw)
-        run.info = {
+        parts = dict(segs=segs, terms=terms, act=act, leak=leak, pn=pn, post_add=post_add, prec=prec, cout=cout, out_hw=out_hw)
+        info = {
             "kind": "conv2d_fused", "cout": cout, "act": act, "pixel_norm": pn, "prec": prec,
             "post_add": post_add.name if post_add is not None else None,
             "post_add_id": post_add.id if post_add is not None else None,
@@ -472,7 +471,7 @@ class Session(object):
                               kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
                          for (src, c_off_src, up, term, w_off, cin) in segs],
         }
-        return deps, run
+        return _Step(n, deps, run, info, emit, parts)
 
     def _launch_prec(self, lead, cout, segs):
         """the precision of a fused launch of `cout` outputs over segments `segs` whose leading weight is `lead`"""
@@ -527,43 +526,28 @@ class Session(object):
                     g8, off = self._g8(env, src, c_off_src, ci, ops.flavour_for(prec))
                     seg_objs.append(ops.Segment(g8, pk, off, up))
                 launches.append((seg_objs, co))
-            dst = env.get("__out__") if emit["f32"] else None
-            if dst is not None:
-                dst = dst.view(-1, *n.shape[1:])
-            res = ops.conv2d_fused_d2s(launches, out_hw, c_total, bias=self._bias_for([term]), want_f32=emit["f32"],
-                                       want_g8=emit["g8"], out=dst)
-            res = list(res) if isinstance(res, tuple) else [res]
-            out = {"f32": None, "g8": {}}
-            if emit["f32"]:
-                out["f32"] = res.pop(0)
-            if emit["g8"]:
-                out["g8"][ops.G8_F16] = res.pop(0)
-            return out
+            return self._boxed(ops.conv2d_fused_d2s(launches, out_hw, c_total, bias=self._bias_for([term]), want_f32=emit["f32"],
+                                                    want_g8=emit["g8"], out=self._dst(env, emit, n.shape)), emit)
 
-        run.emit = emit
-        run.parts = None
-        run.info = {
+        info = {
             "kind": "conv2d_fused_d2s", "cout": c_total // 4, "conv_cout": c_total, "launches": len(chunks), "act": None,
             "pixel_norm": False, "prec": precs[0], "post_add": None, "post_add_id": None,
             "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=ci, up_log2=up, w_off=w_off, kernel=(1, 1),
                               weight=lead) for (src, c_off_src, up, t, w_off, ci) in segs],
         }
-        return [s[0] for s in segs], run
+        return _Step(n, [s[0] for s in segs], run, info, emit)
 
     def plan_summary(self, fetch):
         """the launch plan of `fetch` as a list of dicts (no GPU needed): one entry per kernel launch"""
         plan = self._plans.get(fetch.id) or self._compile(fetch)
         self._plans[fetch.id] = plan
         out = []
-        for node, fn in plan.steps:
-            if node.op in ("variable", "placeholder"):
+        for step in plan.steps:
+            if step.node.op in ("variable", "placeholder"):
                 continue
-            info = dict(getattr(fn, "info", {"kind": node.op}))
-            if info.get("kind") == "fused_into_next":
-                continue
-            info["node"] = node.name
-            if hasattr(fn, "emit"):
-                info["emit"] = dict(fn.emit)
+            info = dict(step.info or {"kind": step.node.op}, node=step.node.name)
+            if step.emit is not None:
+                info["emit"] = dict(step.emit)
             out.append(info)
         return out
 
@@ -689,68 +673,60 @@ class Session(object):
         op = n.op
         if op == "reshape":
             tgt = n.attrs["target"]
-            return [n.inputs[0]], lambda env, i=n.inputs[0], t=tgt: self._f32(env, i).reshape(t)
+            return _Step(n, [n.inputs[0]], lambda env, i=n.inputs[0], t=tgt: self._f32(env, i).reshape(t))
         if op == "concat":
-            return list(n.inputs), lambda env, ins=n.inputs: torch.cat([self._f32(env, i) for i in ins], dim=-1).contiguous()
+            return _Step(n, list(n.inputs), lambda env, ins=n.inputs: torch.cat([self._f32(env, i) for i in ins], dim=-1).contiguous())
         if op == "slice":
             b, s = n.attrs["begin"], n.attrs["size"]
-            return [n.inputs[0]], lambda env, i=n.inputs[0]: self._f32(env, i)[..., b:b + s].contiguous()
+            return _Step(n, [n.inputs[0]], lambda env, i=n.inputs[0]: self._f32(env, i)[..., b:b + s].contiguous())
         if op == "slice_flat":
             cnt = n.attrs["count"]
-            return [n.inputs[0]], lambda env, i=n.inputs[0]: self._f32(env, i).reshape(self._f32(env, i).shape[0], -1)[:, :cnt].contiguous()
+            return _Step(n, [n.inputs[0]], lambda env, i=n.inputs[0]: self._f32(env, i).reshape(self._f32(env, i).shape[0], -1)[:, :cnt].contiguous())
         if op == "add":
             a, b = n.inputs
-            return [a, b], lambda env: ops.add_act(self._f32(env, a), self._f32(env, b))
+            return _Step(n, [a, b], lambda env: ops.add_act(self._f32(env, a), self._f32(env, b)))
         if op == "act":
             x = n.inputs[0]
             if x.op == "add" and single_use(x):
                 a, b = x.inputs
-                return [a, b], lambda env: ops.add_act(self._f32(env, a), self._f32(env, b), n.attrs["act"], n.attrs.get("leak", 0.2))
+                return _Step(n, [a, b], lambda env: ops.add_act(self._f32(env, a), self._f32(env, b), n.attrs["act"], n.attrs.get("leak", 0.2)))
             direct = self._match_direct(n, single_use)
             if direct is not None:
                 return direct
-            return [x], lambda env: ops.add_act(self._f32(env, x), None, n.attrs["act"], n.attrs.get("leak", 0.2))
+            return _Step(n, [x], lambda env: ops.add_act(self._f32(env, x), None, n.attrs["act"], n.attrs.get("leak", 0.2)))
         if op == "pixel_norm":
             x = n.inputs[0]
-            return [x], lambda env: ops.pixel_norm(self._f32(env, x), n.attrs["eps"])
+            return _Step(n, [x], lambda env: ops.pixel_norm(self._f32(env, x), n.attrs["eps"]))
         if op == "resize":
             x = n.inputs[0]
-            return [x], lambda env: ops.resize_images(self._f32(env, x), n.attrs["oh"], n.attrs["ow"], n.attrs["method"])
+            return _Step(n, [x], lambda env: ops.resize_images(self._f32(env, x), n.attrs["oh"], n.attrs["ow"], n.attrs["method"]))
         if op == "avg_pool":
             x = n.inputs[0]
-            return [x], lambda env: ops.avg_pool2(self._f32(env, x))
+            return _Step(n, [x], lambda env: ops.avg_pool2(self._f32(env, x)))
         if op == "random_normal":
             x = n.inputs[0]
 
-            def run_noise(env, n=n, x=x):
-                ref = self._f32(env, x)
-                gen = self.__dict__.setdefault("_noise_gen", {})
-                if n.id not in gen:
-                    seed = n.attrs["seed"] if n.attrs["seed"] is not None else n.id        # one stream per noise node
-                    gen[n.id] = torch.Generator(device=ref.device).manual_seed(1000003 * seed + 17)
-                shape = tuple(ref.shape[:-1]) + (n.shape[-1],)
-                return torch.randn(shape, generator=gen[n.id], device=ref.device, dtype=torch.float32) * n.attrs["stddev"]
-
-            return [x], run_noise
+            seed = n.attrs["seed"] if n.attrs["seed"] is not None else n.id        # one stream per noise node
+            return _Step(n, [x], lambda env: seeded_normal(self._noise_gen, n, self._f32(env, x), seed))
         if op == "max_pool":
             x = n.inputs[0]
-            return [x], lambda env: ops.max_pool(self._f32(env, x), n.attrs["k"], n.attrs["s"])
+            return _Step(n, [x], lambda env: ops.max_pool(self._f32(env, x), n.attrs["k"], n.attrs["s"]))
         if op == "minibatch_stddev":
             x = n.inputs[0]
-            return [x], lambda env: ops.minibatch_stddev(self._f32(env, x), n.attrs["group_size"])
+            return _Step(n, [x], lambda env: ops.minibatch_stddev(self._f32(env, x), n.attrs["group_size"]))
         if op == "lerp":
             from . import train_ops
             t = n.attrs["t"]
 
             def run_lerp(env, n=n, t=t):
-                tv = t.value(getattr(self, "_scalars", {})) if isinstance(t, G.Scalar) else float(t)
+                tv = t.value(self._scalars) if isinstance(t, G.Scalar) else float(t)
                 xin = None if n.attrs["zero_x"] else self._f32(env, n.inputs[0])
                 return train_ops.lerp(xin, self._f32(env, n.inputs[-1]), tv)
 
-            return list(n.inputs), run_lerp
+            return _Step(n, list(n.inputs), run_lerp)
         if op == "depth_to_space":
             x = n.inputs[0]
-            return [x], lambda env: ops.depth_to_space(self._f32(env, x), n.attrs["r"])
+            return _Step(n, [x], lambda env: ops.depth_to_space(self._f32(env, x), n.attrs["r"]))
         if op == "advect":
             from . import train_ops
 
@@ -760,7 +736,7 @@ class Session(object):
                 at = n.attrs
                 return train_ops.advect(src, vel, flags, at["dt"], at["order"], at["strength"], at["start_bz"])
 
-            return list(n.inputs), run_advect
+            return _Step(n, list(n.inputs), run_advect)
         if op in ("conv2d", "conv2d_transpose", "bias_add", "batch_norm"):
             direct = self._match_direct(n, single_use)
             if direct is not None:
@@ -769,30 +745,12 @@ class Session(object):
 
     def _match_direct(self, n, single_use):
         """[act](bn?(bias_add?(conv2d | matmul))) on the vector-ALU kernel: strided convs, cout > 128, FC."""
-        cur = n
-        act, leak = None, 0.2
-        if cur.op == "act":
-            act, leak = cur.attrs["act"], cur.attrs.get("leak", 0.2)
-            nxt = cur.inputs[0]
-            if not single_use(nxt):
-                return None
-            cur = nxt
-        bn = bias = None
-        if cur.op == "batch_norm":
-            if cur.attrs["training"]:
-                raise NotImplementedError("training-mode batch norm is not lowered yet")
-            bn = cur
-            if not single_use(cur.inputs[0]):
-                return None
-            cur = cur.inputs[0]
-        if cur.op == "bias_add":
-            bias = cur
-            if not single_use(cur.inputs[0]):
-                return None
-            cur = cur.inputs[0]
-        if cur.op not in ("conv2d", "matmul", "conv2d_transpose"):
+        m = G.match_layer(n, single_use, ("conv2d", "matmul", "conv2d_transpose"))
+        if m is None:
             return None
-        conv = cur
+        conv, bias, bn, act, leak = m
+        if bn is not None and bn.attrs["training"]:
+            raise NotImplementedError("training-mode batch norm is not lowered yet")
         x, wv = conv.inputs
         term = _Term(conv, bias, bn)
         is_fc = conv.op == "matmul"
@@ -816,4 +774,4 @@ class Session(object):
                 return y.reshape(xin.shape[0], w.shape[1])
             return ops.conv2d_direct(xin, w, conv.attrs["stride"], conv.attrs["wscale"], scale, b, act, leak)
 
-        return [x], run
+        return _Step(n, [x], run)

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib, ops, train_ops
 from . import graph as G
+from .session import seeded_normal
 
 TRAINABLE_KINDS = ("weight", "bias", "gamma", "beta")
 
@@ -629,6 +630,7 @@ class TrainSession(object):
         self.higher_order_scopes = ()
         self.params = {}
         self._scalar_feeds = {}
+        self._noise_gen = {}     # random_normal node id -> its generator
 
     def parameters(self):
         """name -> leaf tensor for every variable of the graph (trainable ones require grad)"""
@@ -682,30 +684,6 @@ class TrainSession(object):
                 stack.append(i)
         return users
 
-    def _layer_chain(self, n, users):
-        """n = [act](batch_norm?(bias_add?(conv2d|matmul))) with single-use links -> (conv, bias, bn, act, leak)"""
-        cur, act, leak = n, None, 0.2
-        if cur.op == "act":
-            nxt = cur.inputs[0]
-            if users.get(nxt.id, 0) != 1 or nxt.op not in ("batch_norm", "bias_add", "conv2d", "matmul"):
-                return None
-            act, leak = cur.attrs["act"], cur.attrs.get("leak", 0.2)
-            cur = nxt
-        bn = bias = None
-        if cur.op == "batch_norm":
-            bn = cur
-            if users.get(cur.inputs[0].id, 0) != 1:
-                return None
-            cur = cur.inputs[0]
-        if cur.op == "bias_add":
-            bias = cur
-            if users.get(cur.inputs[0].id, 0) != 1:
-                return None
-            cur = cur.inputs[0]
-        if cur.op not in ("conv2d", "matmul"):
-            return None
-        return cur, bias, bn, act, leak
-
     def _higher(self, n):
         """does this node sit in a variable scope that needs differentiable backward passes?"""
         return any(n.scope.startswith(p) for p in self.higher_order_scopes)
@@ -725,7 +703,8 @@ class TrainSession(object):
         if op == "variable":
             return self.params[n.attrs["var"]]
         if op in ("act", "batch_norm", "bias_add", "conv2d", "matmul"):
-            chain = self._layer_chain(n, users)
+            # a layer [act](batch_norm?(bias_add?(conv2d|matmul))) whose inner nodes feed nothing else is one function
+            chain = G.match_layer(n, lambda m: users.get(m.id, 0) == 1, ("conv2d", "matmul"))
             if chain is not None:
                 return self._conv_layer(chain, ev)
             if op == "act":
@@ -757,12 +736,7 @@ class TrainSession(object):
             y = ev(n.inputs[-1])
             return (Lerp2Fn if self._higher(n) else LerpFn).apply(x, y, t)
         if op == "random_normal":
-            ref = ev(n.inputs[0])
-            gen = self.__dict__.setdefault("_noise_gen", {})
-            if n.id not in gen:
-                gen[n.id] = torch.Generator(device=ref.device).manual_seed(1000003 * n.attrs["seed"] + 17)
-            shape = tuple(ref.shape[:-1]) + (n.shape[-1],)
-            return torch.randn(shape, generator=gen[n.id], device=ref.device, dtype=torch.float32) * n.attrs["stddev"]
+            return seeded_normal(self._noise_gen, n, ev(n.inputs[0]), n.attrs["seed"])
         if op == "max_pool":
             if self._higher(n):
                 raise NotImplementedError("second-order gradient through max_pool (no reference network uses it)")

@@ -145,6 +145,32 @@ def test_fusion_plan(mpg):
     assert plan[-1]["cout"] == 1 and plan[-1]["post_add"] is not None and plan[0]["pixel_norm"]
 
 
+def test_fusion_plan_small_conv_chains(mpg):
+    """three small convolutions in a row: a launch is half of at most one small pair; the planner visits consumers first"""
+    from mpgan_amd import graph as G, session as S
+    from mpgan_amd.GAN import GAN
+
+    def launches(shortcut):
+        G.reset_default_graph()
+        g = GAN(G.placeholder([1, 16, 16, 1], name="x"))
+        c1, _ = g.convolutional_layer(2, [3, 3], G.relu, name="c1")
+        g.convolutional_layer(4, [3, 3], G.relu, name="c2")
+        out, c3_lin = g.convolutional_layer(8, [3, 3], None if shortcut else G.relu, name="c3")
+        if shortcut:
+            _, cs_lin = g.convolutional_layer(8, [1, 1], None, name="cs", in_layer=c1)
+            out = G.relu(G.add(c3_lin, cs_lin))
+        plan = S.Session(device="cpu", prec=3).plan_summary(out)
+        G.reset_default_graph()
+        return plan
+
+    for shortcut, nseg in ((False, 1), (True, 2)):
+        plan = launches(shortcut)
+        # c2 + c3 (+ the shortcut from c1's output) are one launch; c1, whose only reader is now that pair, stays its own
+        assert [(e["kind"], e["cout"]) for e in plan] == [("conv2d_fused", 2), ("conv2d_small_pair", 8)]
+        assert plan[1]["cmid"] == 4 and len(plan[1]["segments"]) == nseg
+        assert plan[0]["emit"] == {"f32": False, "g8": True} and plan[1]["emit"] == {"f32": True, "g8": False}
+
+
 def test_trainer_builds_on_cpu_and_refuses_to_run_without_gpu():
     """graph construction and parameter grouping need no GPU; the step itself has no CPU fallback"""
     import torch
