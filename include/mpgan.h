@@ -321,20 +321,16 @@ int mpg_conv2d_dgrad(mpg_stream_t stream, const float* dy, int n, int h, int w, 
  * Its gradients are mpg_conv2d_wgrad / mpg_conv2d_dgrad with h = w = 1. */
 int mpg_fc_forward(mpg_stream_t stream, const float* x, int rows, int k, const float* w, int cout,
                    float wscale, const float* bias, int act, float leak, float* y);
-/* out[c] = sum over pixels of x[p, c]  (bias gradient, GAN.py:683) */
-int mpg_channel_sum(mpg_stream_t stream, const float* x, size_t npix, int c, float* out);
-/* ... with the blocks' sums added in a fixed order: partials holds >= mpg_bn_partials_floats(c) + c floats */
+/* out[c] = sum over pixels of x[p, c]  (bias gradient, GAN.py:683), the blocks' sums added in a fixed order:
+ * partials holds >= mpg_bn_partials_floats(c) + c floats */
 int mpg_channel_sum_ordered(mpg_stream_t stream, const float* x, size_t npix, int c, float* out, float* partials,
                             size_t partials_floats);
 /* tf.contrib.layers.batch_norm(is_training=True) (GAN.py:110): batch mean / biased variance over
  * all pixels, y = act((x - mean) * rsqrt(var + eps) * gamma + beta); the moments are returned, and
  * the moving averages (the UPDATE_OPS, multipassGAN-4x.py:773-776) are advanced in place when
- * moving_mean / moving_var are given: moving = decay * moving + (1 - decay) * batch. */
-int mpg_bn_train_fwd(mpg_stream_t stream, const float* x, size_t npix, int c, const float* gamma,
-                     const float* beta, float eps, int act, float leak, float* y, float* batch_mean,
-                     float* batch_var, float* moving_mean, float* moving_var, float decay);
-/* The same with the blocks' partial sums kept in `partials` (>= mpg_bn_partials_floats(c) floats of device memory) and
- * added in block order instead of by atomics: the batch statistics -- and with them every ReLU mask of the step -- are
+ * moving_mean / moving_var are given: moving = decay * moving + (1 - decay) * batch.
+ * The blocks' partial sums are kept in `partials` (>= mpg_bn_partials_floats(c) floats of device memory) and
+ * added in block order, not by atomics: the batch statistics -- and with them every ReLU mask of the step -- are
  * then the same bits on every run (a pre-activation within 1e-6 of zero otherwise changes side now and then, and one
  * flipped mask element moves the gradients upstream of it by 1 / sqrt(elements): DESIGN section 10). */
 size_t mpg_bn_partials_floats(int c);
@@ -344,12 +340,8 @@ int mpg_bn_train_fwd_ordered(mpg_stream_t stream, const float* x, size_t npix, i
                              size_t partials_floats);
 /* gradient of the normalisation above (dy is taken before the activation).  amax (may be NULL) receives max |dx|:
  * the data- and weight-gradient convolutions that consume dx scale it by a power of two before the fp16 split
- * (mpg_absmax would re-read the tensor for it). */
-int mpg_bn_train_bwd(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c,
-                     const float* batch_mean, const float* batch_var, const float* gamma, float eps,
-                     float* dx, float* dgamma, float* dbeta, float* amax);
-/* ... with the blocks' partial sums of dbeta / dgamma kept in `partials` (mpg_bn_partials_floats(c) floats) and added in a
- * fixed order, as mpg_bn_train_fwd_ordered does for the statistics */
+ * (mpg_absmax would re-read the tensor for it).  The blocks' partial sums of dbeta / dgamma are kept in `partials`
+ * (mpg_bn_partials_floats(c) floats) and added in a fixed order, as mpg_bn_train_fwd_ordered does for the statistics */
 int mpg_bn_train_bwd_ordered(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c,
                              const float* batch_mean, const float* batch_var, const float* gamma, float eps,
                              float* dx, float* dgamma, float* dbeta, float* amax, float* partials, size_t partials_floats);

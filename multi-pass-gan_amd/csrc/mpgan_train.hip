@@ -155,11 +155,8 @@ __global__ void dgrad_kernel(const float* __restrict__ dy, const float* __restri
     dx[idx] = acc * wscale;
 }
 
-#ifndef MPG_BN_TWO_PASS
-#define MPG_BN_TWO_PASS 0
-#endif
 // ---------------------------------------------------------------- per-channel sums over pixels
-// MODE 0: sum x            MODE 1: sum (x - m)^2 with m = aux0[c] * inv_n
+// MODE 0: sum x
 // MODE 2: sum a, sum a*(x - mean)*invstd  (a = dy; two outputs)
 // MODE 3: sum (x - k), sum (x - k)^2 with k = bn_shift(x, ch): the channel's mean over four pixels spread through the
 //         batch: both batch moments in ONE pass over x.  With k within a few sigma of the mean,
@@ -173,9 +170,8 @@ __device__ __forceinline__ float bn_shift(const float* __restrict__ x, size_t np
 template <int MODE>
 __global__ __launch_bounds__(256) void chan_sum_kernel(const float* __restrict__ a, const float* __restrict__ x,
                                                        size_t npix, int c, int lanes, const float* __restrict__ aux0,
-                                                       const float* __restrict__ aux1, float inv_n, float eps,
-                                                       float* __restrict__ out0, float* __restrict__ out1,
-                                                       size_t pix_per_block, float* __restrict__ partials) {
+                                                       const float* __restrict__ aux1, float eps, size_t pix_per_block,
+                                                       float* __restrict__ partials) {
     __shared__ float red0[BLK];
     __shared__ float red1[BLK];
     const int tid = threadIdx.x;
@@ -187,13 +183,11 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const float* __restrict__
     float s0 = 0.f, s1 = 0.f;
     if (ch < c) {
         float m = 0.f, is = 0.f;
-        if (MODE == 1) m = aux0[ch] * inv_n;
         if (MODE == 2) { m = aux0[ch]; is = rsqrtf(aux1[ch] + eps); }
         if (MODE == 3) m = bn_shift(a, npix, c, ch);
         for (size_t p = p_begin + row; p < p_end; p += ppi) {
             const float v = a[p * c + ch];
             if (MODE == 0) s0 += v;
-            if (MODE == 1) { const float d = v - m; s0 = fmaf(d, d, s0); }
             if (MODE == 2) { s0 += v; s1 = fmaf(v, (x[p * c + ch] - m) * is, s1); }
             if (MODE == 3) { const float d = v - m; s0 += d; s1 = fmaf(d, d, s1); }
         }
@@ -203,13 +197,9 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const float* __restrict__
     __syncthreads();
     if (row == 0 && ch < c) {
         for (int r = 1; r < ppi; ++r) { s0 += red0[r * lanes + lane]; s1 += red1[r * lanes + lane]; }
-        if (partials != nullptr) {           // ordered form: the block's sums are kept, bn_finalize_kernel adds them in block order
-            partials[((size_t)blockIdx.x * c + ch) * 2] = s0;
-            partials[((size_t)blockIdx.x * c + ch) * 2 + 1] = s1;
-        } else {
-            atomicAdd(out0 + ch, s0);
-            if (MODE == 2 || MODE == 3) atomicAdd(out1 + ch, s1);
-        }
+        // the block's sums are kept; sum_partials_kernel adds them in block order
+        partials[((size_t)blockIdx.x * c + ch) * 2] = s0;
+        partials[((size_t)blockIdx.x * c + ch) * 2 + 1] = s1;
     }
 }
 
@@ -218,9 +208,8 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const float* __restrict__
 template <int MODE>
 __global__ __launch_bounds__(256) void chan_sum4_kernel(const float* __restrict__ a, const float* __restrict__ x, size_t npix,
                                                         int c, int lanes, const float* __restrict__ aux0,
-                                                        const float* __restrict__ aux1, float inv_n, float eps,
-                                                        float* __restrict__ out0, float* __restrict__ out1,
-                                                        size_t pix_per_block, float* __restrict__ partials) {
+                                                        const float* __restrict__ aux1, float eps, size_t pix_per_block,
+                                                        float* __restrict__ partials) {
     __shared__ float4 red0[BLK];
     __shared__ float4 red1[BLK];
     const int tid = threadIdx.x;
@@ -234,7 +223,6 @@ __global__ __launch_bounds__(256) void chan_sum4_kernel(const float* __restrict_
         float m[4] = {0.f, 0.f, 0.f, 0.f}, is[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (MODE == 1) m[j] = aux0[ch + j] * inv_n;
             if (MODE == 2) { m[j] = aux0[ch + j]; is[j] = rsqrtf(aux1[ch + j] + eps); }
             if (MODE == 3) m[j] = bn_shift(a, npix, c, ch + j);
         }
@@ -243,7 +231,6 @@ __global__ __launch_bounds__(256) void chan_sum4_kernel(const float* __restrict_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (MODE == 0) s0[j] += v[j];
-                if (MODE == 1) { const float d = v[j] - m[j]; s0[j] = fmaf(d, d, s0[j]); }
                 if (MODE == 2) { s0[j] += v[j]; s1[j] = fmaf(v[j], (xv[j] - m[j]) * is[j], s1[j]); }
                 if (MODE == 3) { const float d = v[j] - m[j]; s0[j] += d; s1[j] = fmaf(d, d, s1[j]); }
             }
@@ -275,34 +262,26 @@ __global__ __launch_bounds__(256) void chan_sum4_kernel(const float* __restrict_
             t0.x += u0.x; t0.y += u0.y; t0.z += u0.z; t0.w += u0.w;
             t1.x += u1.x; t1.y += u1.y; t1.z += u1.z; t1.w += u1.w;
         }
-        if (partials != nullptr) {
-            float* pp = partials + ((size_t)blockIdx.x * c + ch) * 2;
-            pp[0] = t0.x; pp[1] = t1.x; pp[2] = t0.y; pp[3] = t1.y; pp[4] = t0.z; pp[5] = t1.z; pp[6] = t0.w; pp[7] = t1.w;
-        } else {
-            atomicAdd(out0 + ch, t0.x); atomicAdd(out0 + ch + 1, t0.y); atomicAdd(out0 + ch + 2, t0.z); atomicAdd(out0 + ch + 3, t0.w);
-            if (MODE == 2 || MODE == 3) {
-                atomicAdd(out1 + ch, t1.x); atomicAdd(out1 + ch + 1, t1.y); atomicAdd(out1 + ch + 2, t1.z); atomicAdd(out1 + ch + 3, t1.w);
-            }
-        }
+        float* pp = partials + ((size_t)blockIdx.x * c + ch) * 2;
+        pp[0] = t0.x; pp[1] = t1.x; pp[2] = t0.y; pp[3] = t1.y; pp[4] = t0.z; pp[5] = t1.z; pp[6] = t0.w; pp[7] = t1.w;
     }
 }
 
 template <int MODE>
 int launch_chan_sum(hipStream_t s, const float* a, const float* x, size_t npix, int c, const float* aux0,
-                    const float* aux1, float inv_n, float eps, float* out0, float* out1, float* partials = nullptr) {
+                    const float* aux1, float eps, float* partials) {
     if (c >= 16 && (c % 4) == 0 && (((uintptr_t)a) & 15) == 0 && (x == nullptr || (((uintptr_t)x) & 15) == 0)) {
         int lanes = 1;
         while (lanes < c / 4 && lanes < BLK) lanes <<= 1;
         const int cblocks = (c / 4 + lanes - 1) / lanes;
         const int ppi = BLK / lanes;
-        // every block ends in one atomic per channel: 2048 blocks queued ~100 us of atomics on each address
         size_t blocks = (npix + (size_t)ppi * 16 - 1) / ((size_t)ppi * 16);
         if (blocks > 512) blocks = 512;
         if (blocks < 1) blocks = 1;
         const size_t ppb = (npix + blocks - 1) / blocks;
         blocks = (npix + ppb - 1) / ppb;
         hipLaunchKernelGGL((chan_sum4_kernel<MODE>), dim3((unsigned)blocks, cblocks), dim3(BLK), 0, s, a, x, npix, c, lanes,
-                           aux0, aux1, inv_n, eps, out0, out1, ppb, partials);
+                           aux0, aux1, eps, ppb, partials);
         return (int)blocks;
     }
     int lanes = 1;
@@ -315,7 +294,7 @@ int launch_chan_sum(hipStream_t s, const float* a, const float* x, size_t npix, 
     const size_t ppb = (npix + blocks - 1) / blocks;
     blocks = (npix + ppb - 1) / ppb;
     hipLaunchKernelGGL((chan_sum_kernel<MODE>), dim3((unsigned)blocks, cblocks), dim3(BLK), 0, s, a, x, npix, c, lanes,
-                       aux0, aux1, inv_n, eps, out0, out1, ppb, partials);
+                       aux0, aux1, eps, ppb, partials);
     return (int)blocks;
 }
 constexpr int CHAN_SUM_MAX_BLOCKS = 1024;       // pixel blocks of either kernel (the size of a `partials` buffer: blocks x c x 2)
@@ -967,18 +946,8 @@ extern "C" int mpg_fc_forward(mpg_stream_t stream, const float* x, int rows, int
     MPG_LAUNCH_CHECK("fc_fwd_kernel");
 }
 
-extern "C" int mpg_channel_sum(mpg_stream_t stream, const float* x, size_t npix, int c, float* out) {
-    MPG_REQUIRE(x && out, "mpg_channel_sum: null pointer");
-    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_channel_sum: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = mpg::zero_async(out, (size_t)c * sizeof(float), s);
-    if (e != hipSuccess) return mpg::hip_check(e, "mpg_channel_sum: memset");
-    launch_chan_sum<0>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, 0.f, out, nullptr);
-    MPG_LAUNCH_CHECK("chan_sum_kernel");
-}
-
-// ... with the blocks' sums kept in `partials` (mpg_bn_partials_floats(c) floats; the second float of a pair receives a
-// copy) and added in a fixed order
+// per-channel sum over pixels; the blocks' sums are kept in `partials` (mpg_bn_partials_floats(c) + c floats: the second
+// float of a pair receives a copy) and added in a fixed order
 extern "C" int mpg_channel_sum_ordered(mpg_stream_t stream, const float* x, size_t npix, int c, float* out, float* partials,
                                        size_t partials_floats) {
     MPG_REQUIRE(x && out && partials, "mpg_channel_sum_ordered: null pointer");
@@ -986,64 +955,29 @@ extern "C" int mpg_channel_sum_ordered(mpg_stream_t stream, const float* x, size
     MPG_REQUIRE(partials_floats >= (size_t)CHAN_SUM_MAX_BLOCKS * c * 2 + (size_t)c, "mpg_channel_sum_ordered: partials buffer too small");
     hipStream_t s = (hipStream_t)stream;
     float* spare = partials + (size_t)CHAN_SUM_MAX_BLOCKS * c * 2;      // sum_partials_kernel writes two vectors: the second goes here
-    const int nb = launch_chan_sum<0>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, 0.f, out, nullptr, partials);
+    const int nb = launch_chan_sum<0>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, partials);
     hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, out, spare);
     MPG_LAUNCH_CHECK("chan_sum_kernel (ordered)");
 }
 
 extern "C" size_t mpg_bn_partials_floats(int c) { return c >= 1 ? (size_t)CHAN_SUM_MAX_BLOCKS * c * 2 : 0; }
 
-static int bn_train_fwd_impl(mpg_stream_t stream, const float* x, size_t npix, int c, const float* gamma, const float* beta,
-                             float eps, int act, float leak, float* y, float* batch_mean, float* batch_var, float* moving_mean,
-                             float* moving_var, float decay, float* partials);
-
-extern "C" int mpg_bn_train_fwd(mpg_stream_t stream, const float* x, size_t npix, int c, const float* gamma,
-                                const float* beta, float eps, int act, float leak, float* y, float* batch_mean,
-                                float* batch_var, float* moving_mean, float* moving_var, float decay) {
-    return bn_train_fwd_impl(stream, x, npix, c, gamma, beta, eps, act, leak, y, batch_mean, batch_var, moving_mean, moving_var,
-                             decay, nullptr);
-}
-
 extern "C" int mpg_bn_train_fwd_ordered(mpg_stream_t stream, const float* x, size_t npix, int c, const float* gamma,
                                         const float* beta, float eps, int act, float leak, float* y, float* batch_mean,
                                         float* batch_var, float* moving_mean, float* moving_var, float decay, float* partials,
                                         size_t partials_floats) {
+    MPG_REQUIRE(x && gamma && beta && y && batch_mean && batch_var, "mpg_bn_train_fwd_ordered: null pointer");
+    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_bn_train_fwd_ordered: bad shape");
+    MPG_REQUIRE(act >= MPG_ACT_NONE && act <= MPG_ACT_TANH, "mpg_bn_train_fwd_ordered: bad activation %d", act);
     MPG_REQUIRE(partials != nullptr && partials_floats >= mpg_bn_partials_floats(c), "mpg_bn_train_fwd_ordered: partials buffer too small");
-    return bn_train_fwd_impl(stream, x, npix, c, gamma, beta, eps, act, leak, y, batch_mean, batch_var, moving_mean, moving_var,
-                             decay, partials);
-}
-
-static int bn_train_fwd_impl(mpg_stream_t stream, const float* x, size_t npix, int c, const float* gamma, const float* beta,
-                             float eps, int act, float leak, float* y, float* batch_mean, float* batch_var, float* moving_mean,
-                             float* moving_var, float decay, float* partials) {
-    MPG_REQUIRE(x && gamma && beta && y && batch_mean && batch_var, "mpg_bn_train_fwd: null pointer");
-    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_bn_train_fwd: bad shape");
-    MPG_REQUIRE(act >= MPG_ACT_NONE && act <= MPG_ACT_TANH, "mpg_bn_train_fwd: bad activation %d", act);
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    if (partials != nullptr) {
-        // ordered form: sum_partials_kernel writes every sum, nothing to clear
-    } else if (batch_var == batch_mean + c) {
-        e = mpg::zero_async(batch_mean, (size_t)2 * c * sizeof(float), s);
-    } else {
-        e = mpg::zero_async(batch_mean, (size_t)c * sizeof(float), s);
-        if (e == hipSuccess) e = mpg::zero_async(batch_var, (size_t)c * sizeof(float), s);
-    }
-    if (e != hipSuccess) return mpg::hip_check(e, "mpg_bn_train_fwd: memset");
     const float inv_n = 1.f / (float)npix;
-#if MPG_BN_TWO_PASS
-    launch_chan_sum<0>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, 0.f, batch_mean, nullptr);
-    launch_chan_sum<1>(s, x, nullptr, npix, c, batch_mean, nullptr, inv_n, 0.f, batch_var, nullptr);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(grid_for(c)), dim3(BLK), 0, s, batch_mean, batch_var, c, inv_n,
-                       moving_mean, moving_var, decay, (const float*)nullptr, (size_t)0);
-#else
-    const int nb = launch_chan_sum<3>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, 0.f, batch_mean, batch_var, partials);
-    if (partials != nullptr)
-        hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, batch_mean,
-                           batch_var);
+    // sum_partials_kernel writes every sum: nothing to clear
+    const int nb = launch_chan_sum<3>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, partials);
+    hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, batch_mean,
+                       batch_var);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(grid_for(c)), dim3(BLK), 0, s, batch_mean, batch_var, c, inv_n,
                        moving_mean, moving_var, decay, x, npix);
-#endif
     const size_t total = npix * c;
     const uintptr_t al = (uintptr_t)x | (uintptr_t)y;
     if ((c % 4) == 0 && c <= BN4_CMAX && (al & 15) == 0) {
@@ -1055,54 +989,32 @@ static int bn_train_fwd_impl(mpg_stream_t stream, const float* x, size_t npix, i
     else
         hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total)), dim3(BLK), 0, s, x, total, c, batch_mean, batch_var,
                            gamma, beta, eps, act, leak, y);
-    MPG_LAUNCH_CHECK("bn_train_fwd");
-}
-
-static int bn_train_bwd_impl(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c, const float* batch_mean,
-                             const float* batch_var, const float* gamma, float eps, float* dx, float* dgamma, float* dbeta,
-                             float* amax, float* partials);
-
-extern "C" int mpg_bn_train_bwd(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c,
-                                const float* batch_mean, const float* batch_var, const float* gamma, float eps,
-                                float* dx, float* dgamma, float* dbeta, float* amax) {
-    return bn_train_bwd_impl(stream, dy, x, npix, c, batch_mean, batch_var, gamma, eps, dx, dgamma, dbeta, amax, nullptr);
+    MPG_LAUNCH_CHECK("bn_train_fwd_ordered");
 }
 
 extern "C" int mpg_bn_train_bwd_ordered(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c,
                                         const float* batch_mean, const float* batch_var, const float* gamma, float eps,
                                         float* dx, float* dgamma, float* dbeta, float* amax, float* partials,
                                         size_t partials_floats) {
-    MPG_REQUIRE(partials != nullptr && partials_floats >= mpg_bn_partials_floats(c), "mpg_bn_train_bwd_ordered: partials buffer too small");
-    return bn_train_bwd_impl(stream, dy, x, npix, c, batch_mean, batch_var, gamma, eps, dx, dgamma, dbeta, amax, partials);
-}
-
-static int bn_train_bwd_impl(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c, const float* batch_mean,
-                             const float* batch_var, const float* gamma, float eps, float* dx, float* dgamma, float* dbeta,
-                             float* amax, float* partials) {
     MPG_REQUIRE(dy && x && batch_mean && batch_var && gamma && dx && dgamma && dbeta,
-                "mpg_bn_train_bwd: null pointer");
-    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_bn_train_bwd: bad shape");
+                "mpg_bn_train_bwd_ordered: null pointer");
+    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_bn_train_bwd_ordered: bad shape");
+    MPG_REQUIRE(partials != nullptr && partials_floats >= mpg_bn_partials_floats(c), "mpg_bn_train_bwd_ordered: partials buffer too small");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    if (partials != nullptr) {
-        // ordered form: sum_partials_kernel writes every sum, nothing to clear
-    } else if (dbeta == dgamma + c) {
-        e = mpg::zero_async(dgamma, (size_t)2 * c * sizeof(float), s);
-    } else {
-        e = mpg::zero_async(dgamma, (size_t)c * sizeof(float), s);
-        if (e == hipSuccess) e = mpg::zero_async(dbeta, (size_t)c * sizeof(float), s);
+    // sum_partials_kernel writes every sum: only the abs-max (an atomic maximum) is cleared
+    if (amax != nullptr) {
+        hipError_t e = mpg::zero_async(amax, sizeof(float), s);
+        if (e != hipSuccess) return mpg::hip_check(e, "mpg_bn_train_bwd_ordered: memset");
     }
-    if (e == hipSuccess && amax != nullptr) e = mpg::zero_async(amax, sizeof(float), s);
-    if (e != hipSuccess) return mpg::hip_check(e, "mpg_bn_train_bwd: memset");
-    const int nb = launch_chan_sum<2>(s, dy, x, npix, c, batch_mean, batch_var, 0.f, eps, dbeta, dgamma, partials);
-    if (partials != nullptr)      // the blocks' sums in a fixed order (and no atomics queueing on 2 c addresses)
-        hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, dbeta, dgamma);
+    const int nb = launch_chan_sum<2>(s, dy, x, npix, c, batch_mean, batch_var, eps, partials);
+    // the blocks' sums in a fixed order (and no atomics queueing on 2 c addresses)
+    hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, dbeta, dgamma);
     const size_t total = npix * c;
     unsigned g = grid_for(total);
     if (amax != nullptr && g > AMAX_GRID) g = AMAX_GRID;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(g), dim3(BLK), 0, s, dy, x, total, c, batch_mean,
                        batch_var, gamma, dgamma, dbeta, eps, 1.f / (float)npix, dx, (unsigned int*)amax);
-    MPG_LAUNCH_CHECK("bn_train_bwd");
+    MPG_LAUNCH_CHECK("bn_train_bwd_ordered");
 }
 
 extern "C" int mpg_act_bwd(mpg_stream_t stream, const float* dy, const float* y, size_t n, int act, float leak,

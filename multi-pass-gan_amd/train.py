@@ -14,6 +14,7 @@ import math
 import numpy as np
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops, train_ops
 from . import graph as G
@@ -44,6 +45,37 @@ def _wgrad_prec(prec):
     return prec if prec == ops.PREC_F16X1 else ops.PREC_F16X3
 
 
+def _cached_g8(t, prec, scaled):
+    """(G8 form of t, the abs-max it was scaled by or None), kept on the tensor object.
+    scaled False: the plain hi/lo split of an activation -- a block's input feeds two convolutions (first conv and 1x1
+    shortcut), the second one finds the form the first one made.  scaled True: t times the power of two of its abs-max -- a
+    gradient that enters both the data- and the weight-gradient convolution of a layer (or a second-order forward and its
+    weight gradient) is reduced and converted once.
+    A cached copy is valid while the tensor holds the values it was made from.  The tag (`_version`, `data_ptr`, shape) sees
+    in-place torch operations and a swapped storage; it does NOT see a library kernel writing through the raw pointer, so no
+    tensor that is converted here may be rewritten that way afterwards.  Today none is: the kernels' outputs are fresh tensors,
+    and what the library updates in place (the optimisers' flat parameter buffers, the batch-norm moving averages) are
+    variables, which are packed as weights or read as vectors and never come here."""
+    tags = getattr(t, "_mpg_g8", None)
+    tag = None if tags is None else tags.get(scaled)
+    if tag is None or tag[2:] != (t._version, t.data_ptr(), tuple(t.shape)):
+        tc = t.detach().contiguous()
+        am = ops.absmax(tc) if scaled else None
+        tag = (ops.to_g8(tc, 0, tc.shape[3], ops.flavour_for(prec), amax=am), am, t._version, t.data_ptr(), tuple(t.shape))
+        try:
+            if tags is None:
+                tags = t._mpg_g8 = {}
+            tags[scaled] = tag
+        except AttributeError:      # a tensor type that takes no attributes: convert every time
+            pass
+    return tag[0], tag[1]
+
+
+def _dgrad_weights(w):
+    """[kh,kw,cin,cout] -> [kh,kw,cout,cin] with the taps mirrored: the data gradient as a forward convolution over dy"""
+    return w.flip(0, 1).permute(0, 1, 3, 2).contiguous()
+
+
 def _mfma_conv(x, w, wscale, prec, bias=None, act=None, leak=0.2, pad_hi=0, rescale=False, amax=None, keep=None):
     """conv2d_SAME(x, w * wscale) [+ bias, act] on the MFMA kernel, output channels in chunks of 128.
     rescale: x is a gradient (1e-4 .. 1e-8 in magnitude, below the fp16 normal range): it is split into
@@ -54,17 +86,7 @@ def _mfma_conv(x, w, wscale, prec, bias=None, act=None, leak=0.2, pad_hi=0, resc
     if not rescale:
         amax = None
         if isinstance(x, torch.Tensor):
-            # a block's input feeds two convolutions (first conv and 1x1 shortcut): the second one finds the G8 form the first
-            # one made, on the tensor itself (valid while the tensor is neither rewritten in place nor another storage)
-            x = x.contiguous()
-            tag = getattr(x, "_mpg_g8", None)
-            if tag is None or tag[1] != x._version or tag[2] != x.data_ptr() or tag[3] != tuple(x.shape):
-                tag = (ops.to_g8(x, 0, x.shape[3], ops.flavour_for(prec)), x._version, x.data_ptr(), tuple(x.shape))
-                try:
-                    x._mpg_g8 = tag
-                except AttributeError:      # a tensor type that takes no attributes: convert every time
-                    pass
-            x = tag[0]
+            x = _cached_g8(x.contiguous(), prec, False)[0]
     elif isinstance(x, torch.Tensor):
         amax = ops.absmax(x) if amax is None else amax
         x = ops.to_g8(x.contiguous(), 0, x.shape[3], ops.flavour_for(prec), amax=amax)
@@ -98,7 +120,7 @@ class ConvLayerFn(torch.autograd.Function):
             lin = train_ops.fc_forward(x.reshape(x.shape[0], cin), w.detach().reshape(cin, cout), wscale, b, conv_act,
                                        leak).reshape(x.shape[0], 1, 1, cout)
         elif _mfma_ok(kh, kw, cout, stride):
-            keep = [] if (ctx.needs_input_grad[1] and train_ops.wgrad_mfma_ok(kh, kw, stride) and cfg.get("wgrad_mfma", True)) else None
+            keep = [] if (ctx.needs_input_grad[1] and train_ops.wgrad_mfma_ok(kh, kw, stride)) else None
             lin = _mfma_conv(x, w.detach().contiguous(), wscale, cfg["prec"], b.detach() if b is not None else None,
                              conv_act, leak, keep=keep)
             x_g8 = keep[0] if keep else None
@@ -117,6 +139,7 @@ class ConvLayerFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         cfg = ctx.cfg
         stride, wscale, act, leak = cfg["stride"], cfg["wscale"], cfg["act"], cfg["leak"]
@@ -145,8 +168,7 @@ class ConvLayerFn(torch.autograd.Function):
         dw = None
         if need_amax and d_amax is None:
             d_amax = ops.absmax(d)                                                      # shared by both gradients
-        wgrad_mm = ctx.needs_input_grad[1] and train_ops.wgrad_mfma_ok(kh, kw, stride) and not cfg.get("fc") and \
-            cfg.get("wgrad_mfma", True)
+        wgrad_mm = ctx.needs_input_grad[1] and train_ops.wgrad_mfma_ok(kh, kw, stride) and not cfg.get("fc")
         dgrad_mm = ctx.needs_input_grad[0] and _mfma_ok(kh, kw, cin, stride) and not cfg.get("fc")
         d_g8 = None
         if x_g8 is not None and wgrad_mm:
@@ -164,8 +186,8 @@ class ConvLayerFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             if dgrad_mm:
-                wt = w.detach().flip(0, 1).permute(0, 1, 3, 2).contiguous()      # [kh,kw,cout,cin], taps mirrored
-                dx = _mfma_conv(d if d_g8 is None else d_g8, wt, wscale, cfg["prec"], pad_hi=1, rescale=True, amax=d_amax)
+                dx = _mfma_conv(d if d_g8 is None else d_g8, _dgrad_weights(w.detach()), wscale, cfg["prec"], pad_hi=1,
+                                rescale=True, amax=d_amax)
             else:
                 dx = train_ops.conv2d_dgrad(d, w.detach(), (x.shape[1], x.shape[2]), stride, wscale)
         return dx, dw, db, dgamma, dbeta, None
@@ -180,22 +202,6 @@ class ConvLayerFn(torch.autograd.Function):
 #   dw = wgrad(x, dy)    : dx = dgrad(dy, G)     d(dy) = conv(x, G)
 # so three Functions that call each other give gradients of any order from the same kernels.
 # ----------------------------------------------------------------------------------------------
-def _scaled_g8(t, prec):
-    """(G8 of t scaled by the power of two of its abs-max, the abs-max), kept on the tensor: a gradient that enters both the
-    data- and the weight-gradient convolution of a layer (or a second-order forward and its weight gradient) is reduced
-    and converted once.  Valid while the tensor is neither rewritten in place nor another storage."""
-    tag = getattr(t, "_mpg_sg8", None)
-    if tag is None or tag[2] != t._version or tag[3] != t.data_ptr() or tag[4] != tuple(t.shape):
-        tc = t.detach().contiguous()
-        am = ops.absmax(tc)
-        tag = (ops.to_g8(tc, 0, tc.shape[3], ops.flavour_for(prec), amax=am), am, t._version, t.data_ptr(), tuple(t.shape))
-        try:
-            t._mpg_sg8 = tag
-        except AttributeError:
-            pass
-    return tag[0], tag[1]
-
-
 def _conv_fwd(x, w, b, cfg):
     """x may be the autograd tensor itself (its scaled G8 form is cached on it); w, b detached"""
     kh, kw, cin, cout = w.shape
@@ -205,7 +211,7 @@ def _conv_fwd(x, w, b, cfg):
             xd.shape[0], 1, 1, cout)
     if _mfma_ok(kh, kw, cout, cfg["stride"]):
         if cfg.get("rescale_fwd") and x.dim() == 4:
-            g8, am = _scaled_g8(x, cfg["prec"])
+            g8, am = _cached_g8(x, cfg["prec"], True)
             return _mfma_conv(g8, w.contiguous(), cfg["wscale"], cfg["prec"], b, rescale=True, amax=am)
         return _mfma_conv(x.detach().contiguous(), w.contiguous(), cfg["wscale"], cfg["prec"], b)
     return ops.conv2d_direct(x.detach().contiguous(), w.contiguous(), cfg["stride"], cfg["wscale"], None, b)
@@ -214,16 +220,15 @@ def _conv_fwd(x, w, b, cfg):
 def _conv_dgrad(dy, w, cfg, hw):
     kh, kw, cin, cout = w.shape
     if _mfma_ok(kh, kw, cin, cfg["stride"]) and not cfg.get("fc"):
-        g8, am = _scaled_g8(dy, cfg["prec"])
-        return _mfma_conv(g8, w.flip(0, 1).permute(0, 1, 3, 2).contiguous(), cfg["wscale"], cfg["prec"],
-                          pad_hi=1, rescale=True, amax=am)
+        g8, am = _cached_g8(dy, cfg["prec"], True)
+        return _mfma_conv(g8, _dgrad_weights(w), cfg["wscale"], cfg["prec"], pad_hi=1, rescale=True, amax=am)
     return train_ops.conv2d_dgrad(dy.detach(), w, hw, cfg["stride"], cfg["wscale"])
 
 
 def _conv_wgrad(x, dy, cfg, kh, kw):
     if train_ops.wgrad_mfma_ok(kh, kw, cfg["stride"]) and not cfg.get("fc"):
-        xg, xam = _scaled_g8(x, cfg["prec"])
-        dg, dam = _scaled_g8(dy, cfg["prec"])
+        xg, xam = _cached_g8(x, cfg["prec"], True)
+        dg, dam = _cached_g8(dy, cfg["prec"], True)
         return train_ops.conv2d_wgrad_g8(xg, dg, kh, kw, cfg["wscale"], _wgrad_prec(cfg["prec"]), xam, dam)
     return train_ops.conv2d_wgrad(x.detach(), dy.detach(), kh, kw, cfg["stride"], cfg["wscale"])
 
@@ -277,38 +282,46 @@ class ConvWgradFn(torch.autograd.Function):
         return dx, ddy, None, None, None
 
 
-class ActBwdFn(torch.autograd.Function):
-    """dx = dy * act'(.) with the mask taken from the activation output: linear in dy"""
+# The elementwise and resampling layers below are linear (or piecewise linear) in their input: forward runs the kernel on
+# detached inputs, backward is another Function's apply, so gradients of any order come from the same kernels and one
+# Function serves the first-order step and the WGAN-GP critics alike (under plain first-order training the nested apply
+# records nothing).
+class ActFn(torch.autograd.Function):
+    """act(a [+ b]) (tf.nn.relu(tf.add(B, s)), multipassGAN-4x.py:523); act None = the plain sum"""
 
     @staticmethod
-    def forward(ctx, dy, y, act, leak):
+    def forward(ctx, a, b, act, leak):
+        y = ops.add_act(a.detach().contiguous(), b.detach().contiguous() if b is not None else None, act, leak)
         ctx.save_for_backward(y)
-        ctx.act, ctx.leak = act, leak
-        return train_ops.act_bwd(dy.detach(), y, act, leak)
-
-    @staticmethod
-    def backward(ctx, g):
-        (y,) = ctx.saved_tensors
-        return ActBwdFn.apply(g, y, ctx.act, ctx.leak), None, None, None
-
-
-class Act2Fn(torch.autograd.Function):
-    """act(x) for relu / lrelu (piecewise linear: the second derivative is zero almost everywhere)"""
-
-    @staticmethod
-    def forward(ctx, x, act, leak):
-        y = ops.add_act(x.detach().contiguous(), None, act, leak)
-        ctx.save_for_backward(y)
-        ctx.act, ctx.leak = act, leak
+        ctx.act, ctx.leak, ctx.two = act, leak, b is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        return ActBwdFn.apply(dy, y, ctx.act, ctx.leak), None, None
+        d = ActBwdFn.apply(dy, y, ctx.act, ctx.leak) if ctx.act is not None else dy
+        return d, (d if ctx.two else None), None, None
 
 
-class AvgPool2Fn(torch.autograd.Function):
+class ActBwdFn(torch.autograd.Function):
+    """dx = dy * act'(.) with the mask taken from the activation output: linear in dy.  relu / lrelu are piecewise linear
+    (the second derivative is zero almost everywhere); tanh is not, and has no lowering for the derivative in y"""
+
+    @staticmethod
+    def forward(ctx, dy, y, act, leak):
+        ctx.save_for_backward(y)
+        ctx.act, ctx.leak = act, leak
+        return train_ops.act_bwd(dy.detach(), y.detach(), act, leak)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.act == "tanh" and ctx.needs_input_grad[1]:
+            raise NotImplementedError("second-order gradient through tanh (d/dy of dy * (1 - y^2) has no kernel)")
+        (y,) = ctx.saved_tensors
+        return ActBwdFn.apply(g, y, ctx.act, ctx.leak), None, None, None
+
+
+class AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         ctx.hw = (x.shape[1], x.shape[2])
@@ -316,31 +329,31 @@ class AvgPool2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        return AvgPoolBwd2Fn.apply(dy, ctx.hw)
+        return AvgPoolBwdFn.apply(dy, ctx.hw)
 
 
-class AvgPoolBwd2Fn(torch.autograd.Function):
+class AvgPoolBwdFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dy, hw):
         return train_ops.avg_pool2_bwd(dy.detach(), *hw)
 
     @staticmethod
     def backward(ctx, g):
-        return AvgPool2Fn.apply(g), None
+        return AvgPoolFn.apply(g), None
 
 
-class ResizeNearest2Fn(torch.autograd.Function):
+class ResizeNearestFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, oh, ow):
-        ctx.hw, ctx.ohw = (x.shape[1], x.shape[2]), (oh, ow)
+        ctx.hw = (x.shape[1], x.shape[2])
         return ops.resize_nearest(x.detach().contiguous(), oh, ow)
 
     @staticmethod
     def backward(ctx, dy):
-        return ResizeNearestBwd2Fn.apply(dy, ctx.hw), None, None
+        return ResizeNearestBwdFn.apply(dy, ctx.hw), None, None
 
 
-class ResizeNearestBwd2Fn(torch.autograd.Function):
+class ResizeNearestBwdFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dy, hw):
         ctx.ohw = (dy.shape[1], dy.shape[2])
@@ -348,21 +361,22 @@ class ResizeNearestBwd2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return ResizeNearest2Fn.apply(g, *ctx.ohw), None
+        return ResizeNearestFn.apply(g, *ctx.ohw), None
 
 
-class Lerp2Fn(torch.autograd.Function):
-    """lerp with a backward made of lerps (linear in both operands)"""
+class LerpFn(torch.autograd.Function):
+    """lerp(x, y, t) (multipassGAN-8x.py:598-599); x may be None (tf.zeros_like).  Linear in both operands: the backward is
+    made of lerps.  train_ops.lerp clamps t to [0, 1], and 1 - clamp(t) = clamp(1 - t), so t is kept as given"""
 
     @staticmethod
     def forward(ctx, x, y, t):
-        ctx.t, ctx.has_x = min(max(float(t), 0.0), 1.0), x is not None
+        ctx.t, ctx.has_x = float(t), x is not None
         return train_ops.lerp(x.detach() if x is not None else None, y.detach(), ctx.t)
 
     @staticmethod
     def backward(ctx, dy):
-        dyy = Lerp2Fn.apply(None, dy, ctx.t) if ctx.needs_input_grad[1] else None
-        dx = Lerp2Fn.apply(None, dy, 1.0 - ctx.t) if (ctx.has_x and ctx.needs_input_grad[0]) else None
+        dyy = LerpFn.apply(None, dy, ctx.t) if ctx.needs_input_grad[1] else None
+        dx = LerpFn.apply(None, dy, 1.0 - ctx.t) if (ctx.has_x and ctx.needs_input_grad[0]) else None
         return dx, dyy, None
 
 
@@ -408,7 +422,7 @@ class BNTrainBwd2Fn(torch.autograd.Function):
         return g_dz, g_x, g_gamma, None, None, None
 
 
-class MinibatchStddev2Fn(torch.autograd.Function):
+class MinibatchStddevFn(torch.autograd.Function):
     """GAN.minibatch_stddev_layer (GAN.py:476-488), differentiable twice"""
 
     @staticmethod
@@ -420,10 +434,10 @@ class MinibatchStddev2Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        return MinibatchStddevBwd2Fn.apply(dy, x, ctx.group_size), None
+        return MinibatchStddevBwdFn.apply(dy, x, ctx.group_size), None
 
 
-class MinibatchStddevBwd2Fn(torch.autograd.Function):
+class MinibatchStddevBwdFn(torch.autograd.Function):
     """dx = dy[..., :C] + D_m u / (K G s_f): linear in dy, the statistic's second derivative in x"""
 
     @staticmethod
@@ -480,45 +494,7 @@ def strided4_as_3x3(w):
     return wp.reshape(3, 2, 3, 2, c, co).permute(0, 2, 1, 3, 4, 5).reshape(3, 3, 4 * c, co)
 
 
-class ActFn(torch.autograd.Function):
-    """act(a [+ b]) (tf.nn.relu(tf.add(B, s)), multipassGAN-4x.py:523)"""
-
-    @staticmethod
-    def forward(ctx, a, b, act, leak):
-        y = ops.add_act(a.contiguous(), b.contiguous() if b is not None else None, act, leak)
-        ctx.save_for_backward(y)
-        ctx.act, ctx.leak, ctx.two = act, leak, b is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (y,) = ctx.saved_tensors
-        d = train_ops.act_bwd(dy, y, ctx.act, ctx.leak) if ctx.act is not None else dy
-        return d, (d if ctx.two else None), None, None
-
-
-class ResizeNearestFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, oh, ow):
-        ctx.hw = (x.shape[1], x.shape[2])
-        return ops.resize_nearest(x.contiguous(), oh, ow)
-
-    @staticmethod
-    def backward(ctx, dy):
-        return train_ops.resize_nearest_bwd(dy, *ctx.hw), None, None
-
-
-class AvgPoolFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        ctx.hw = (x.shape[1], x.shape[2])
-        return ops.avg_pool2(x.contiguous())
-
-    @staticmethod
-    def backward(ctx, dy):
-        return train_ops.avg_pool2_bwd(dy, *ctx.hw)
-
-
+# First-order only: a second derivative through these raises (once_differentiable) instead of reading as zero.
 class MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k, s):
@@ -529,23 +505,10 @@ class MaxPoolFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         (arg,) = ctx.saved_tensors
         return train_ops.max_pool_bwd(dy, arg, *ctx.geom), None, None
-
-
-class MinibatchStddevFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, group_size):
-        x = x.contiguous()
-        ctx.save_for_backward(x)
-        ctx.group_size = group_size
-        return ops.minibatch_stddev(x, group_size)
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        return train_ops.minibatch_stddev_bwd(dy, x, ctx.group_size), None
 
 
 class PixelNormFn(torch.autograd.Function):
@@ -557,25 +520,10 @@ class PixelNormFn(torch.autograd.Function):
         return ops.pixel_norm(x, eps)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         return train_ops.pixel_norm_bwd(dy, x, ctx.eps), None
-
-
-class LerpFn(torch.autograd.Function):
-    """lerp(x, y, t) (multipassGAN-8x.py:598-599); x may be None (tf.zeros_like)"""
-
-    @staticmethod
-    def forward(ctx, x, y, t):
-        ctx.t = min(max(float(t), 0.0), 1.0)
-        ctx.has_x = x is not None
-        return train_ops.lerp(x, y, ctx.t)
-
-    @staticmethod
-    def backward(ctx, dy):
-        dxy = train_ops.lerp(None, dy, ctx.t)
-        dx = train_ops.lerp(None, dy, 1.0 - ctx.t) if ctx.has_x else None
-        return dx, dxy, None
 
 
 class PairLossFn(torch.autograd.Function):
@@ -606,6 +554,7 @@ class ResampleFn(torch.autograd.Function):
         return train_ops.tensor_resample(value, pos, clamp)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         (pos,) = ctx.saved_tensors
         return train_ops.tensor_resample_bwd(dy, pos, ctx.clamp), None, None
@@ -625,7 +574,6 @@ class TrainSession(object):
         self.prec = prec
         self.bn_decay = bn_decay
         self.device = torch.device(device)
-        self.strided_on_mfma = True      # 4x4 stride-2 convs as 3x3 stride-1 convs over space-to-depth inputs
         # variable-name prefixes whose layers must support gradients of gradients (the WGAN-GP discriminators)
         self.higher_order_scopes = ()
         self.params = {}
@@ -667,7 +615,7 @@ class TrainSession(object):
                 env[node.id] = torch.as_tensor(t, dtype=torch.float32, device=self.device)
         users = self._count_users(fetches)
         # the UPDATE_OPS of tf.contrib.layers.batch_norm (multipassGAN-4x.py:773-776,889-899) run inside
-        # mpg_bn_train_fwd: every evaluated batch-norm layer advances its moving averages once
+        # mpg_bn_train_fwd_ordered: every evaluated batch-norm layer advances its moving averages once
         return [self._eval(f, env, users) for f in fetches]
 
     def _count_users(self, fetches):
@@ -728,13 +676,13 @@ class TrainSession(object):
         if op == "pixel_norm":
             return PixelNormFn.apply(ev(n.inputs[0]), n.attrs["eps"])
         if op == "avg_pool":
-            return (AvgPool2Fn if self._higher(n) else AvgPoolFn).apply(ev(n.inputs[0]))
+            return AvgPoolFn.apply(ev(n.inputs[0]))
         if op == "lerp":
             t = n.attrs["t"]
             t = t.value(self._scalar_feeds) if isinstance(t, G.Scalar) else float(t)
             x = None if n.attrs["zero_x"] else ev(n.inputs[0])
             y = ev(n.inputs[-1])
-            return (Lerp2Fn if self._higher(n) else LerpFn).apply(x, y, t)
+            return LerpFn.apply(x, y, t)
         if op == "random_normal":
             return seeded_normal(self._noise_gen, n, ev(n.inputs[0]), n.attrs["seed"])
         if op == "max_pool":
@@ -747,16 +695,13 @@ class TrainSession(object):
             at = n.attrs
             return train_ops.advect(src, vel.detach(), flags.detach(), at["dt"], at["order"], at["strength"], at["start_bz"])
         if op == "minibatch_stddev":
-            x = ev(n.inputs[0])
-            if x.requires_grad and self._higher(n):
-                return MinibatchStddev2Fn.apply(x, n.attrs["group_size"])
-            return MinibatchStddevFn.apply(x, n.attrs["group_size"])
+            return MinibatchStddevFn.apply(ev(n.inputs[0]), n.attrs["group_size"])
         if op == "depth_to_space":
             return DepthToSpaceFn.apply(ev(n.inputs[0]), n.attrs["r"])
         if op == "resize":
             x = ev(n.inputs[0])
             if n.attrs["method"] == 1:
-                return (ResizeNearest2Fn if self._higher(n) else ResizeNearestFn).apply(x, n.attrs["oh"], n.attrs["ow"])
+                return ResizeNearestFn.apply(x, n.attrs["oh"], n.attrs["ow"])
             if x.requires_grad:
                 raise NotImplementedError("gradient of bilinear / bicubic resize (only applied to network inputs)")
             return ops.resize_images(x.contiguous(), n.attrs["oh"], n.attrs["ow"], n.attrs["method"])
@@ -775,8 +720,8 @@ class TrainSession(object):
             stride = (1, 1)
         else:
             w4, stride = w, tuple(conv.attrs["stride"])
-            if stride == (2, 2) and tuple(w.shape[:2]) == (4, 4) and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0 \
-                    and self.strided_on_mfma:
+            if stride == (2, 2) and tuple(w.shape[:2]) == (4, 4) and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0:
+                # 4x4 stride-2 convs as 3x3 stride-1 convs over space-to-depth inputs
                 x, w4, stride = space_to_depth2(x), strided4_as_3x3(w), (1, 1)
         cfg = {"stride": stride, "wscale": conv.attrs["wscale"], "act": act, "leak": leak, "prec": self.prec, "fc": is_fc,
                "eps": bn.attrs["eps"] if bn is not None else 0.0}
@@ -792,7 +737,7 @@ class TrainSession(object):
             if act is not None:
                 if act == "tanh":
                     raise G.GraphError("tanh has no higher-order lowering")
-                y = Act2Fn.apply(y, act, leak)
+                y = ActFn.apply(y, None, act, leak)
             return y.reshape(y.shape[0], -1) if is_fc else y
         gamma = beta = None
         if bn is not None:
@@ -820,19 +765,31 @@ class AdamTF(object):
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m = torch.zeros(n, dtype=torch.float32, device=dev)
         self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-        off = 0
+        self._grad_views = []
         with torch.no_grad():
-            for p in self.params:
-                k = p.numel()
-                self.flat[off:off + k].copy_(p.reshape(-1))
-                p.data = self.flat[off:off + k].view(p.shape)       # parameters alias the flat buffer
-                off += k
-        self._grad_views, off = [], 0
-        for p in self.params:
-            self._grad_views.append(self.grad[off:off + p.numel()].view(p.shape))
-            off += p.numel()
+            for _, p, sl in self._slices():
+                self.flat[sl].copy_(p.reshape(-1))
+                p.data = self.flat[sl].view(p.shape)       # parameters alias the flat buffer
+                self._grad_views.append(self.grad[sl].view(p.shape))
         self.lr, self.b1, self.b2, self.eps, self.t = lr, beta1, beta2, eps, 0
         self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)      # read by the kernel: replayable in a graph
+
+    def _slices(self):
+        """(name, parameter, its slice of the flat buffers) for every variable, in buffer order"""
+        off = 0
+        for name, p in zip(self.names, self.params):
+            yield name, p, slice(off, off + p.numel())
+            off += p.numel()
+
+    def _gather(self, grads):
+        """grads (aligned with self.params; None = zero, as tf treats unconnected variables) into the flat gradient buffer,
+        averaged over the ranks"""
+        if any(g is None for g in grads):
+            self.grad.zero_()
+        dst = [v for v, g in zip(self._grad_views, grads) if g is not None]
+        torch._foreach_copy_(dst, [g.contiguous() for g in grads if g is not None])
+        if self.comm is not None:
+            self.comm.all_reduce_mean(self.grad)
 
     def advance(self, lr=None):
         """host side of a step: t += 1 and the bias-corrected step size into device memory"""
@@ -844,40 +801,31 @@ class AdamTF(object):
         """grads: list aligned with self.params (None = zero gradient, as tf treats unconnected variables)"""
         if advance:
             self.advance(lr)
-        if any(g is None for g in grads):
-            self.grad.zero_()
-        dst = [v for v, g in zip(self._grad_views, grads) if g is not None]
-        torch._foreach_copy_(dst, [g.contiguous() for g in grads if g is not None])
-        if self.comm is not None:
-            self.comm.all_reduce_mean(self.grad)
+        self._gather(grads)
         train_ops.adam_step(self.flat, self.grad, self.m, self.v, self.lr_t, self.b1, self.b2, self.eps)
 
     def slot_state(self, tag):
         """the optimiser's slots under the names tf.train.Saver gives them (``<variable>/Adam``, ``<variable>/Adam_1``;
         the step count as TF's ``beta1_power`` = beta1^(t+1), prefixed with `tag` because every optimiser of a graph
         owns one): what a checkpoint needs so that a resumed run continues like the reference's Saver restore"""
-        out, off = {}, 0
+        out = {}
         m, v = self.m.cpu().numpy(), self.v.cpu().numpy()
-        for n, p_ in zip(self.names, self.params):
-            k = p_.numel()
-            out[n + "/Adam"] = m[off:off + k].reshape(tuple(p_.shape))
-            out[n + "/Adam_1"] = v[off:off + k].reshape(tuple(p_.shape))
-            off += k
+        for n, p_, sl in self._slices():
+            out[n + "/Adam"] = m[sl].reshape(tuple(p_.shape))
+            out[n + "/Adam_1"] = v[sl].reshape(tuple(p_.shape))
         out[tag + "/beta1_power"] = np.float32(self.b1 ** (self.t + 1))
         out[tag + "/adam_t"] = np.int64(self.t)
         return out
 
     def load_slot_state(self, state, tag):
         """inverse of slot_state; variables without slots in `state` keep theirs.  Returns the number restored."""
-        off, hit = 0, 0
+        hit = 0
         with torch.no_grad():
-            for n, p_ in zip(self.names, self.params):
-                k = p_.numel()
+            for n, _, sl in self._slices():
                 if n + "/Adam" in state and n + "/Adam_1" in state:
-                    self.m[off:off + k].copy_(torch.as_tensor(np.asarray(state[n + "/Adam"], np.float32).reshape(-1)))
-                    self.v[off:off + k].copy_(torch.as_tensor(np.asarray(state[n + "/Adam_1"], np.float32).reshape(-1)))
+                    self.m[sl].copy_(torch.as_tensor(np.asarray(state[n + "/Adam"], np.float32).reshape(-1)))
+                    self.v[sl].copy_(torch.as_tensor(np.asarray(state[n + "/Adam_1"], np.float32).reshape(-1)))
                     hit += 1
-                off += k
         if tag + "/adam_t" in state:
             self.t = int(state[tag + "/adam_t"])
         return hit
@@ -913,11 +861,9 @@ class StagedAdam(AdamTF):
         for z in range(levels):
             chosen = set(stage_variable_names(self.names, z, levels))
             mask = torch.zeros(n, dtype=torch.float32, device=dev)
-            off = 0
-            for name, p in zip(self.names, self.params):
+            for name, _, sl in self._slices():
                 if name in chosen:
-                    mask[off:off + p.numel()] = 1.0
-                off += p.numel()
+                    mask[sl] = 1.0
             self.masks.append(None if len(chosen) == len(self.names) else mask)
             self.counts.append(len(chosen))
         self.ms = [torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(levels)]
@@ -951,12 +897,7 @@ class StagedAdam(AdamTF):
         if lr is not None:
             self.lr = lr
         self.lr_dev.fill_(float(self.lr))
-        if any(g is None for g in grads):
-            self.grad.zero_()
-        dst = [v for v, g in zip(self._grad_views, grads) if g is not None]
-        torch._foreach_copy_(dst, [g.contiguous() for g in grads if g is not None])
-        if self.comm is not None:
-            self.comm.all_reduce_mean(self.grad)
+        self._gather(grads)
         train_ops.adam_step_staged(self.flat, self.grad, self.ms[stage], self.vs[stage], self.masks[stage], self.state[stage],
                                    self.lr_dev, self.counts[stage], self.loss_scaling, self.b1, self.b2, self.eps,
                                    self.LS_INC, self.LS_DEC, None if self.shadows is None else self.shadows[stage],
@@ -968,13 +909,11 @@ class StagedAdam(AdamTF):
         out = {}
         for z in range(self.levels):
             m, v = self.ms[z].cpu().numpy(), self.vs[z].cpu().numpy()
-            chosen, off = set(stage_variable_names(self.names, z, self.levels)), 0
-            for n, p_ in zip(self.names, self.params):
-                k = p_.numel()
+            chosen = set(stage_variable_names(self.names, z, self.levels))
+            for n, p_, sl in self._slices():
                 if n in chosen:
-                    out[n + self._slot(2 * z)] = m[off:off + k].reshape(tuple(p_.shape))
-                    out[n + self._slot(2 * z + 1)] = v[off:off + k].reshape(tuple(p_.shape))
-                off += k
+                    out[n + self._slot(2 * z)] = m[sl].reshape(tuple(p_.shape))
+                    out[n + self._slot(2 * z + 1)] = v[sl].reshape(tuple(p_.shape))
             st = self.state[z].cpu().numpy()
             out["%s/stage%d/adam_t" % (tag, z)] = np.int64(st[3])
             out["%s/stage%d/ls_var" % (tag, z)] = np.float32(st[0])
@@ -988,15 +927,12 @@ class StagedAdam(AdamTF):
         hit = 0
         with torch.no_grad():
             for z in range(self.levels):
-                off = 0
-                for n, p_ in zip(self.names, self.params):
-                    k = p_.numel()
+                for n, _, sl in self._slices():
                     km, kv = n + self._slot(2 * z), n + self._slot(2 * z + 1)
                     if km in state and kv in state:
-                        self.ms[z][off:off + k].copy_(torch.as_tensor(np.asarray(state[km], np.float32).reshape(-1)))
-                        self.vs[z][off:off + k].copy_(torch.as_tensor(np.asarray(state[kv], np.float32).reshape(-1)))
+                        self.ms[z][sl].copy_(torch.as_tensor(np.asarray(state[km], np.float32).reshape(-1)))
+                        self.vs[z][sl].copy_(torch.as_tensor(np.asarray(state[kv], np.float32).reshape(-1)))
                         hit += 1
-                    off += k
                 if "%s/stage%d/adam_t" % (tag, z) in state:
                     self.state[z][3] = float(state["%s/stage%d/adam_t" % (tag, z)])
                     self.state[z][0] = float(state["%s/stage%d/ls_var" % (tag, z)])
@@ -1005,11 +941,7 @@ class StagedAdam(AdamTF):
     def ema_params(self, stage=None):
         """name -> moving-average tensor of the stage's shadows (swapping_saver of the last stage's optimiser, :1369)"""
         stage = self.levels - 1 if stage is None else stage
-        out, off = {}, 0
-        for name, p in zip(self.names, self.params):
-            out[name] = self.shadows[stage][off:off + p.numel()].view(p.shape)
-            off += p.numel()
-        return out
+        return {name: self.shadows[stage][sl].view(p.shape) for name, p, sl in self._slices()}
 
 
 def sigmoid_ce(logits, label):
@@ -1017,7 +949,25 @@ def sigmoid_ce(logits, label):
     return (torch.clamp(logits, min=0) - logits * label + torch.log1p(torch.exp(-logits.abs()))).mean()
 
 
-class Trainer4x(object):
+class _SlotStateMixin(object):
+    """the optimiser book-keeping both trainers share; a trainer has opt_d, opt_g and, with a temporal critic, opt_t"""
+
+    def optimisers(self):
+        """-> [(tag, optimiser)] in the order the reference creates them (multipassGAN-4x.py:812-900)"""
+        return [("disc", self.opt_d), ("gen", self.opt_g)] + ([("tempo", self.opt_t)] if hasattr(self, "opt_t") else [])
+
+
+    def slot_state(self):
+        out = {}
+        for tag, o in self.optimisers():
+            out.update(o.slot_state(tag))
+        return out
+
+    def load_slot_state(self, state):
+        return sum(o.load_slot_state(state, tag) for tag, o in self.optimisers())
+
+
+class Trainer4x(_SlotStateMixin):
     """The GAN training iteration of multipassGAN-4x.py (graph :728-768,880-902, loop :1317-1356):
     ``discRuns`` discriminator updates then ``genRuns`` generator updates on tile batches, spatial
     discriminator with feature losses, sigmoid cross entropy + lambda * L1 (+ lambda2 * layer loss)."""
@@ -1072,23 +1022,10 @@ class Trainer4x(object):
             self.t_var = {n: p for n, p in self.sess.trainable("t_").items() if n.startswith("discriminatorTempo")}
             self.opt_t = AdamTF(self.t_var, learning_rate, beta1, comm=comm)
 
-    def optimisers(self):
-        """-> [(tag, AdamTF)] in the order the reference creates them (:812-900)"""
-        return [("disc", self.opt_d), ("gen", self.opt_g)] + ([("tempo", self.opt_t)] if hasattr(self, "opt_t") else [])
-
     def set_learning_rate(self, lr):
         """the fed learning rate of all optimisers (the decayLR schedule of :773-774 is evaluated by the caller)"""
         for _, o in self.optimisers():
             o.lr = float(lr)
-
-    def slot_state(self):
-        out = {}
-        for tag, o in self.optimisers():
-            out.update(o.slot_state(tag))
-        return out
-
-    def load_slot_state(self, state):
-        return sum(o.load_slot_state(state, tag) for tag, o in self.optimisers())
 
     def losses(self, batch_xs, batch_ys):
         """-> dict of the loss tensors of multipassGAN-4x.py:744-768 (one forward of G, D(real), D(fake))"""
@@ -1231,7 +1168,7 @@ class Trainer4x(object):
         return Ld["disc_loss"].detach(), Lg["gen_loss_complete"].detach()
 
 
-class Trainer8x(object):
+class Trainer8x(_SlotStateMixin):
     """One stage of the progressive-growing training of multipassGAN-8x.py (graph :1023-1144, optimisers
     :1305-1362): WGAN-GP (lambda 10, target 1, epsilon penalty 1e-3) or LSGAN or sigmoid-CE losses, L1 and
     layer losses for the generator, Adam(beta1, beta2) per network, and the 0.999 moving average of the
@@ -1248,7 +1185,7 @@ class Trainer8x(object):
         self.k, self.k2, self.weight_dld = lambda_l1, lambda2, weight_dld
         self.use_wgan_gp, self.use_LSGAN = use_wgan_gp, use_LSGAN
         # `batchNorm 1` / `use_mb_stddev 1` (multipassGAN-8x.py:85,149,847,907; both 0 in the reference runs) with the WGAN-GP
-        # penalty: the critic is differentiated twice through BNTrain2Fn / MinibatchStddev2Fn (mpg_bn_train_bwd2_ordered,
+        # penalty: the critic is differentiated twice through BNTrain2Fn / MinibatchStddevFn (mpg_bn_train_bwd2_ordered,
         # mpg_minibatch_stddev_bwd2)
         self.batch_norm = bool(batch_norm)
         if use_wgan_gp:
@@ -1402,7 +1339,7 @@ class Trainer8x(object):
             else:
                 v = ResampleFn.apply(v, pos.reshape(-1, pc, pc, 2), self.clamping)
             if pc != th:
-                v = (ResizeNearest2Fn if self.use_wgan_gp else ResizeNearestFn).apply(v, th, th)
+                v = ResizeNearestFn.apply(v, th, th)
         else:
             v = self._to_full_res(frames).reshape(-1, th, th, 1)
         return v.reshape(-1, self.n_t, self.cfg.n_output).permute(0, 2, 1).reshape(-1, self.cfg.n_output * self.n_t)
@@ -1441,18 +1378,6 @@ class Trainer8x(object):
         L["t_disc_loss"] = t_disc_loss
         L["g_loss_t"] = self._adv(gen_s, True)
         return L
-
-    def optimisers(self):
-        return [("disc", self.opt_d), ("gen", self.opt_g)] + ([("tempo", self.opt_t)] if hasattr(self, "opt_t") else [])
-
-    def slot_state(self):
-        out = {}
-        for tag, o in self.optimisers():
-            out.update(o.slot_state(tag))
-        return out
-
-    def load_slot_state(self, state):
-        return sum(o.load_slot_state(state, tag) for tag, o in self.optimisers())
 
     @property
     def ema(self):

@@ -1,6 +1,7 @@
 """Thin wrappers over the training entries of the C ABI (include/mpgan.h, "Training step").
 fp32 NHWC GPU tensors in, fp32 GPU tensors out; no CPU fallback."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .ops import _dev, _ptr, _stream
@@ -223,7 +224,7 @@ def lerp(x, y, t):
     y = _cont(y, "y")
     x = _cont(x, "x") if x is not None else None
     out = torch.empty_like(y)
-    t = min(max(float(t), 0.0), 1.0)
+    t = min(max(float(t), 0.0), 1.0)      # the one place t is clamped (train.LerpFn relies on it)
     _lib.check(lib.mpg_lerp(_stream(), _ptr(x), _ptr(y), y.numel(), t, _ptr(out)), "mpg_lerp")
     return out
 
@@ -292,7 +293,7 @@ def semi_lagrange_bwd(dy, vel_c, sign=1.0):
 
 
 class _SemiLagrangeFn(torch.autograd.Function):
-    """differentiable in `source` (a fixed linear gather): what the generator loss needs of GAN.advect with order 1"""
+    """differentiable once in `source` (a fixed linear gather): what the generator loss needs of GAN.advect with order 1"""
 
     @staticmethod
     def forward(ctx, source, vel_c, sign):
@@ -301,6 +302,7 @@ class _SemiLagrangeFn(torch.autograd.Function):
         return semi_lagrange(source, vel_c, sign)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         (vel_c,) = ctx.saved_tensors
         return semi_lagrange_bwd(dy.contiguous(), vel_c, ctx.sign), None, None
@@ -327,6 +329,7 @@ class _MacCormackFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         vel_c, keep = ctx.saved_tensors
         g = keep * (0.5 * ctx.strength) * dy

@@ -221,6 +221,29 @@ def test_elementwise_backward():
         for a, b in zip(th, tr):
             assert rel(a.grad.cpu().numpy(), b.grad.numpy()) < tol
 
+    def check2(fn_hip, fn_ref, *arrs, tol=1e-6):
+        """second derivative of an any-order Function: the first gradient is taken with create_graph=True for an upstream
+        gradient g that is a variable itself, then a random projection of that gradient is differentiated back to g
+        (J applied to the projection) and to the inputs (zero: the ops are linear, or piecewise linear away from 0)"""
+        th = [dev(a).requires_grad_(True) for a in arrs]
+        tr = [torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in arrs]
+        yh, yr = fn_hip(*th), fn_ref(*tr)
+        g = rng.standard_normal(tuple(yr.shape)).astype(np.float32)
+        gh, gr = dev(g).requires_grad_(True), torch.tensor(g, dtype=torch.float64, requires_grad=True)
+        dh = torch.autograd.grad(yh, th, gh, create_graph=True)
+        dr = torch.autograd.grad(yr, tr, gr, create_graph=True)
+        proj = [rng.standard_normal(tuple(d.shape)).astype(np.float32) for d in dr]
+        for a, b in zip(dh, dr):
+            assert rel(a.detach().cpu().numpy(), b.detach().numpy()) < tol
+        sum((d * dev(q)).sum() for d, q in zip(dh, proj)).backward()
+        sum((d * torch.tensor(q, dtype=torch.float64)).sum() for d, q in zip(dr, proj)).backward()
+        assert float(gr.grad.norm()) > 0
+        assert rel(gh.grad.cpu().numpy(), gr.grad.numpy()) < tol
+        for a, b, arr in zip(th, tr, arrs):
+            ga = np.zeros_like(arr) if a.grad is None else a.grad.cpu().numpy()
+            gb = np.zeros_like(arr) if b.grad is None else b.grad.numpy(force=True)
+            assert rel(ga, gb) < tol
+
     check(lambda a, b: ActFn.apply(a, b, "relu", 0.2), lambda a, b: torch.relu(a + b), x, x2)
     check(lambda a: ActFn.apply(a, None, "lrelu", 0.2), lambda a: TR.lrelu(a), x)
     check(lambda a: ActFn.apply(a, None, "tanh", 0.2), lambda a: torch.tanh(a), x)
@@ -232,8 +255,33 @@ def test_elementwise_backward():
           lambda a: F.avg_pool2d(a.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1), x)
     check(lambda a, b: LerpFn.apply(a, b, 0.3), lambda a, b: a + (b - a) * 0.3, x, x2)
     check(lambda b: LerpFn.apply(None, b, 1.7), lambda b: b * 1.0, x2)
+    # the any-order Functions differentiated twice (seeded normal data: no pre-activation at or next to 0)
+    check2(lambda a: ActFn.apply(a, None, "relu", 0.2), lambda a: torch.relu(a), x)
+    check2(lambda a: ActFn.apply(a, None, "lrelu", 0.2), lambda a: TR.lrelu(a), x)
+    check2(lambda a, b: ActFn.apply(a, b, "relu", 0.2), lambda a, b: torch.relu(a + b), x, x2)
+    check2(lambda a, b: ActFn.apply(a, b, "lrelu", 0.2), lambda a, b: TR.lrelu(a + b), x, x2)
+    check2(lambda a, b: ActFn.apply(a, b, None, 0.2), lambda a, b: a + b, x, x2)
+    check2(lambda a: ResizeNearestFn.apply(a, 24, 20),
+           lambda a: a.repeat_interleave(4, 1).repeat_interleave(2, 2), x)
+    check2(lambda a: AvgPoolFn.apply(a),
+           lambda a: F.avg_pool2d(a.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1), x)
+    check2(lambda a, b: LerpFn.apply(a, b, 0.3), lambda a, b: a + (b - a) * 0.3, x, x2)
+    check2(lambda b: LerpFn.apply(None, b, 1.7), lambda b: b * 1.0, x2)
     s = train_ops.channel_sum(dev(x)).cpu().numpy()
     assert rel(s, x.reshape(-1, 12).astype(np.float64).sum(0)) < 1e-6
+
+
+def test_first_order_function_refuses_second_derivative():
+    """PixelNormFn's backward is a kernel call without a tape: a second derivative through it has to raise, not read as
+    zero.  The product with `a` gives the first gradient a grad_fn of its own, so nothing else can raise here."""
+    from mpgan_amd.train import PixelNormFn
+    rng = np.random.default_rng(4)
+    a = dev(rng.standard_normal((2, 6, 10, 12)).astype(np.float32)).requires_grad_(True)
+    z = PixelNormFn.apply(a, 1e-8) * a
+    (g,) = torch.autograd.grad(z.sum(), a, create_graph=True)
+    assert g.grad_fn is not None
+    with pytest.raises(RuntimeError, match="differentiate twice"):
+        g.sum().backward()
 
 
 def test_adam_step_matches_tf_formula():

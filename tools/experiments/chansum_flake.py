@@ -1,4 +1,4 @@
-"""diagnostic: mpg_bn_train_bwd on fixed data repeated; how many distinct dbeta / dgamma / dx results, how far apart"""
+"""diagnostic: mpg_bn_train_bwd_ordered (through train_ops.bn_train_bwd) on fixed data repeated; how many distinct dbeta / dgamma / dx results, how far apart"""
 import sys
 sys.path.insert(0, "/root/repo")
 import torch
