@@ -33,6 +33,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef MPG_AH
 #define MPG_AH 2
 #endif
+// extra bytes of dynamic LDS asked for by every conv_small_kernel launch (occupancy experiments)
+#ifndef MPG_SM_PAD
+#define MPG_SM_PAD 0
+#endif
 // development switches of the F16F6 K loop (tools/build_variants.sh builds one library per setting, tools/probe_variants.py
 // times them against each other on one box):
 //   MPG_WD          bf6 weight planes read MPG_WD correction steps ahead of their MFMAs (MPG_WD + 1 register buffers)
@@ -88,6 +92,8 @@ constexpr int lo_step(int pt, int nt, int ptn) {
 }
 constexpr int TW = 32;              // tile cols == MFMA N dimension
 constexpr int TAPOFF_BYTES = 1024;  // 256 tap offsets
+// floats per pixel row of conv_epilogue's staging area (32 rows per wave, behind the tap table): NT * 32 channels + pad
+constexpr int epi_rowf(int nt) { return nt * 32 + 4; }
 
 struct SegArgs {
     const char* x;        // G8 tensor
@@ -103,7 +109,7 @@ struct SegArgs {
     int ni_img;           // image DMA instructions per thread per chunk
     int direct;           // F16F6, 1x1 over >= 2 groups: B fragments straight from memory, K runs over groups
     int tp;               // F16F6: tap slots per channel group (kh*kw, or rounded up to 8 when below 16)
-    int pref;             // F16F6: the B fragments of stage st + 1 may be read during stage st (seg_shape_f6)
+    int pref;             // F16F6: the B fragments of stage st + 1 may be read during stage st (seg_shape)
 };
 
 struct ConvArgs {
@@ -159,9 +165,10 @@ __device__ __forceinline__ D2SPos d2s_pos(const KArgsD2S dp, int py, int px, int
     return p;
 }
 
-// Per (NT, PREC) pipeline shape (host mirror: pipe_shape()).
+// Per (NT, PREC) pipeline shape (the host reads it through shape_of()).
 template <int NT, int PREC>
 struct Pipe {
+    static constexpr int WAVES = 4;
     static constexpr int NPL = (PREC == 3) ? 2 : 1;
     static constexpr int PT = (NT >= 3) ? 2 : 4;       // pixel tiles (tile rows) per wave
     static constexpr int TH = 4 * PT;                  // tile rows per workgroup
@@ -171,6 +178,7 @@ struct Pipe {
     static constexpr int WPLANE = KS * NT * 1024;
     static constexpr int WSTAGE = WPLANE * NPL;
     static constexpr int NI = WSTAGE / 4096;
+    static constexpr int ROWF = epi_rowf(NT);
     static_assert(WSTAGE % 4096 == 0, "stage must be a whole number of 256 x 16-byte pieces");
 };
 
@@ -212,7 +220,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
     const int r = lane & 31;
     const int hh = lane >> 5;
     // accumulator element i of n-tile nt: output channel nt*32 + 8*(i>>2) + 4*hh + (i&3), pixel r.
-    constexpr int ROWF = NT * 32 + 4;
+    constexpr int ROWF = epi_rowf(NT);
     float* stg = reinterpret_cast<float*>(smem + TAPOFF_BYTES) + wave * (32 * ROWF);
     const int cg_out = (a.cout + 7) >> 3;
     const float unscale = a.in_amax != nullptr ? 1.f / mpg::pow2_scale(*a.in_amax) : 1.f;
@@ -663,12 +671,14 @@ struct Pipe6 {
     static constexpr int WAVES = (NT == 1) ? 4 : 8;
     static constexpr int PT = 16 / WAVES;                  // tile rows per wave
     static constexpr int TH = 16;
-    static constexpr int WF16 = 4 * NT * 1024;             // four fp16 k-steps
+    static constexpr int KS = 4;                           // fp16 k-steps per stage: 8 tap slots
+    static constexpr int WF16 = KS * NT * 1024;
     static constexpr int WF6 = NT * 2048;                  // one bf6 plane: NT x [2 halves][64 lanes][16 B]: 24 B of codes, scales, pad
     static constexpr int WSTAGE = WF16 + 2 * WF6;          // 8 * NT KiB
     static constexpr int R = 3;
     static constexpr int D = R - 1;
     static constexpr int NI = WSTAGE / (WAVES * 1024);
+    static constexpr int ROWF = epi_rowf(NT);
     static_assert(WSTAGE % (WAVES * 1024) == 0, "stage must be a whole number of per-wave pieces");
 };
 
@@ -1734,143 +1744,137 @@ __global__ void g8_to_f32_kernel(const _Float16* __restrict__ g, int n, int h, i
     y[idx] = (float)src[0] + (float)src[plane_px * 8];
 }
 
+// What the host needs of a kernel's pipeline; every field is read from Pipe<NT, PREC> / Pipe6<NT>.
 struct Shape {
-    int pt, th, ks, r, ni;
+    int th;        // tile rows per workgroup
+    int ks;        // k-steps (two tap slots each) per weight stage
+    int waves;
+    int wstage;    // bytes of a weight stage
+    int ring;      // bytes of the weight ring
+    int rowf;      // floats per staging row of conv_epilogue
 };
+template <class P>
+constexpr Shape shape_of() {
+    return {P::TH, P::KS, P::WAVES, P::WSTAGE, P::R * P::WSTAGE, P::ROWF};
+}
+constexpr Shape SHAPES[3][4] = {   // [prec - 1][nt - 1]: the instantiations launch_conv() picks from
+    {shape_of<Pipe<1, 1>>(), shape_of<Pipe<2, 1>>(), shape_of<Pipe<3, 1>>(), shape_of<Pipe<4, 1>>()},
+    {shape_of<Pipe6<1>>(), shape_of<Pipe6<2>>(), shape_of<Pipe6<3>>(), shape_of<Pipe6<4>>()},
+    {shape_of<Pipe<1, 3>>(), shape_of<Pipe<2, 3>>(), shape_of<Pipe<3, 3>>(), shape_of<Pipe<4, 3>>()},
+};
+static_assert(MPG_PREC_F16X1 == 1 && MPG_PREC_F16F6 == 2 && MPG_PREC_F16X3 == 3, "SHAPES is indexed by prec - 1");
+// prec one of MPG_PREC_*, nt = ceil(cout / 32) in 1..4: the callers have checked both
+const Shape& pipe_shape(int nt, int prec) { return SHAPES[prec - 1][nt - 1]; }
 
-// host mirror of Pipe<NT, PREC>
-Shape pipe_shape(int nt, int prec) {
-    Shape s;
-    const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
-    s.pt = nt >= 3 ? 2 : 4;
-    s.th = 4 * s.pt;
-    if (prec == MPG_PREC_F16X3) s.ks = (nt == 4 || nt == 2) ? 1 : 2;
-    else s.ks = (nt == 4 || nt == 2) ? 2 : 4;
-    s.r = nt == 3 ? 3 : 4;
-    s.ni = s.ks * nt * 1024 * npl / 4096;
-    return s;
+// LDS of a launch.  K loop: [tap-offset table][two halo images][weight ring]; conv_epilogue reuses it as
+// [TAPOFF_BYTES][32 staging rows per wave].  A launch asks for the larger of the two.
+constexpr size_t LDS_MAX = 160 * 1024;     // of a CU, so the most a workgroup can have
+constexpr size_t LDS_TWO_WG = 80 * 1024;   // what leaves room for a second workgroup on the CU
+struct LdsPlan {
+    size_t tap, loop, epi, total;
+};
+LdsPlan lds_plan(int tap_slots, int img_bytes, const Shape& ps) {
+    LdsPlan l;
+    // one int per tap slot in 1 KiB granules, at least the TAPOFF_BYTES the epilogue skips
+    l.tap = ((size_t)tap_slots * 4 + 1023) / 1024 * 1024;
+    if (l.tap < (size_t)TAPOFF_BYTES) l.tap = TAPOFF_BYTES;
+    l.loop = l.tap + 2 * (size_t)img_bytes + ps.ring;
+    l.epi = TAPOFF_BYTES + (size_t)ps.waves * 32 * ps.rowf * sizeof(float);
+    l.total = l.loop > l.epi ? l.loop : l.epi;
+    return l;
 }
 
 struct SegShape {
     int cgc, nchunks, sc, np, ni_img, img_bytes, direct, tp, pref;
+    int slots;     // entries of the tap-offset table
+    int stages;    // weight stages of the packed segment
 };
 
-// groups per chunk: two when that removes the half-empty k-step of an odd tap count and the
-// double-buffered images still leave room for two workgroups per CU
-SegShape seg_shape(int kh, int kw, int cin, int nt, int prec) {
-    const Shape ps = pipe_shape(nt, prec);
-    const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
-    const int cg = (cin + 7) / 8;
-    const int px = (ps.th + kh - 1) * (TW + kw - 1);
-    const int np = (px + 63) & ~63;
-    const int ring = ps.r * ps.ks * nt * 1024 * npl;
-    SegShape s;
-    s.direct = 0;
-    s.tp = 0;
-    s.pref = 0;
-    s.np = np;
-    s.cgc = 1;
-    if (cg >= 2 && ((kh * kw) & 1)) {
-        const int img2 = ((2 * 2 * (np / 64) + 3) & ~3) * 1024;
-        if (TAPOFF_BYTES + 2 * img2 + ring <= 80 * 1024) s.cgc = 2;
-    }
-    const int pieces = s.cgc * 2 * (np / 64);
-    s.ni_img = (pieces + 3) / 4;
-    s.img_bytes = s.ni_img * 4 * 1024;
-    s.nchunks = (cg + s.cgc - 1) / s.cgc;
-    const int ksteps = (kh * kw * s.cgc + 1) / 2;
-    s.sc = (ksteps + ps.ks - 1) / ps.ks;
-    return s;
+// the LDS halo image of a chunk of cgc channel groups: [group][plane][np pixels][16 B], copied in 1 KiB pieces, ni_img
+// per wave
+void set_image(SegShape& s, const Shape& ps, int kh, int kw, int cgc) {
+    s.cgc = cgc;
+    s.np = ((ps.th + kh - 1) * (TW + kw - 1) + 63) & ~63;
+    s.ni_img = (cgc * 2 * (s.np / 64) + ps.waves - 1) / ps.waves;
+    s.img_bytes = s.ni_img * ps.waves * 1024;
 }
 
-// ---- MPG_PREC_F16F6 shapes (host mirror of Pipe6<NT>) ----
-bool f6_supported(int nt) { return nt >= 1 && nt <= 4; }
-int f6_waves(int nt) { return nt == 1 ? 4 : 8; }
-
+// MPG_PREC_F16F6 (conv_mfma_f6_kernel): nchunks = channel groups (one LDS halo image each), sc = weight stages of the
+// whole segment
 SegShape seg_shape_f6(int kh, int kw, int cin, int nt) {
-    // nchunks = channel groups (one LDS halo image each), sc = weight stages of the whole segment
-    SegShape s;
-    s.direct = 0;
-    s.tp = 0;
-    s.pref = 0;
-    if (kh == 1 && kw == 1 && cin > 8 && nt <= 2) {   // conv_mfma_f6_kernel's direct path: K over channel groups
-        s.direct = 1; s.cgc = 1; s.np = 0; s.ni_img = 0; s.img_bytes = 0;
+    const Shape& ps = pipe_shape(nt, MPG_PREC_F16F6);
+    const int stage_slots = 2 * ps.ks;
+    SegShape s = {};
+    if (kh == 1 && kw == 1 && cin > 8 && nt <= 2) {   // the kernel's direct path: K over channel groups, no image, no table
+        s.direct = 1; s.cgc = 1;
         s.nchunks = 1;
-        s.sc = ((cin + 7) / 8 + 7) / 8;
+        s.stages = s.sc = ((cin + 7) / 8 + stage_slots - 1) / stage_slots;
         return s;
     }
-    const int waves = f6_waves(nt);
-    const int px = (16 + kh - 1) * (TW + kw - 1);
-    s.np = (px + 63) & ~63;
-    s.cgc = 1;
-    const int pieces = 2 * (s.np / 64);
-    s.ni_img = (pieces + waves - 1) / waves;
-    s.img_bytes = s.ni_img * waves * 1024;
+    set_image(s, ps, kh, kw, 1);
     s.nchunks = (cin + 7) / 8;
     // tap slots per group: the taps themselves when a group spans >= 2 stages; below that padded to 8, 12 or 16 so
     // that the image of group g+1 (issued once no stage touches group g-1) has >= 1 stage of flight before its
     // first slot: floor(tp (g+1) / 8) - ceil(tp g / 8) >= 1 for every g
     const int T = kh * kw;
     s.tp = T >= 16 ? T : T <= 8 ? 8 : T <= 12 ? 12 : 16;
-    s.sc = (s.nchunks * s.tp + 7) / 8;
+    s.stages = s.sc = (s.nchunks * s.tp + stage_slots - 1) / stage_slots;
+    s.slots = s.sc * stage_slots;
     // The image of group g is issued in stage ceil((g - 1) tp / 8) (the first stage that no longer touches group g - 2)
     // and its first slot lies in stage floor(g tp / 8).  The kernel may read stage st + 1's B fragments during stage st
     // only if every image is then already behind a barrier that followed its DMA wait: two stages between issue and
     // first use, for every group.
     s.pref = 1;
     for (int g = 1; g < s.nchunks; ++g)
-        if ((g * s.tp) / 8 - ((g - 1) * s.tp + 7) / 8 < 2) s.pref = 0;
+        if ((g * s.tp) / stage_slots - ((g - 1) * s.tp + stage_slots - 1) / stage_slots < 2) s.pref = 0;
     return s;
 }
 
-template <int NT>
-hipError_t launch_f6(dim3 grid, size_t lds, hipStream_t st, const ConvArgs& a) {
-    static int lds_limit[64] = {0};
-    if (lds > 48 * 1024) {
-        hipError_t e = mpg::ensure_dyn_lds(reinterpret_cast<const void*>(&conv_mfma_f6_kernel<NT>), (int)lds, lds_limit);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((conv_mfma_f6_kernel<NT>), grid, dim3(Pipe6<NT>::WAVES * 64), lds, st, a);
-    return hipSuccess;
-}
-
-template <int NT, int PREC, bool D2S>
-hipError_t launch_one(dim3 grid, size_t lds, hipStream_t st, const typename KernelArgs<D2S>::type& a) {
-    static int lds_limit[64] = {0};
-    if (lds > 48 * 1024) {
-        hipError_t e = mpg::ensure_dyn_lds(reinterpret_cast<const void*>(&conv_mfma_kernel<NT, PREC, D2S>), (int)lds, lds_limit);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((conv_mfma_kernel<NT, PREC, D2S>), grid, dim3(256), lds, st, a);
-    return hipSuccess;
+// The K decomposition of one segment at `prec`.  MPG_PREC_F16X1 / F16X3 (conv_mfma_kernel): nchunks chunks of cgc
+// channel groups, sc weight stages per chunk; two groups per chunk when that removes the half-empty k-step of an odd tap
+// count and the double-buffered images still leave room for two workgroups per CU
+SegShape seg_shape(int kh, int kw, int cin, int nt, int prec) {
+    if (prec == MPG_PREC_F16F6) return seg_shape_f6(kh, kw, cin, nt);
+    const Shape& ps = pipe_shape(nt, prec);
+    const int cg = (cin + 7) / 8;
+    SegShape s = {};
+    set_image(s, ps, kh, kw, 2);
+    if (cg < 2 || !((kh * kw) & 1) || lds_plan(0, s.img_bytes, ps).loop > LDS_TWO_WG) set_image(s, ps, kh, kw, 1);
+    s.nchunks = (cg + s.cgc - 1) / s.cgc;
+    const int ksteps = (kh * kw * s.cgc + 1) / 2;
+    s.sc = (ksteps + ps.ks - 1) / ps.ks;
+    s.slots = s.sc * ps.ks * 2;
+    s.stages = s.nchunks * s.sc;
+    return s;
 }
 
 // one launch of the fused convolution: prec (MPG_PREC_*) and cout tiles pick the instantiation
 template <bool D2S>
 hipError_t launch_conv(int prec, int nt, dim3 grid, size_t lds, hipStream_t st, const typename KernelArgs<D2S>::type& a) {
+    const dim3 block(pipe_shape(nt, prec).waves * 64);
     if constexpr (!D2S) {
         if (prec == MPG_PREC_F16F6) {
             switch (nt) {
-                case 1: return launch_f6<1>(grid, lds, st, a);
-                case 2: return launch_f6<2>(grid, lds, st, a);
-                case 3: return launch_f6<3>(grid, lds, st, a);
-                default: return launch_f6<4>(grid, lds, st, a);
+                case 1: return mpg::launch_dyn_lds<conv_mfma_f6_kernel<1>>(grid, block, lds, st, a);
+                case 2: return mpg::launch_dyn_lds<conv_mfma_f6_kernel<2>>(grid, block, lds, st, a);
+                case 3: return mpg::launch_dyn_lds<conv_mfma_f6_kernel<3>>(grid, block, lds, st, a);
+                default: return mpg::launch_dyn_lds<conv_mfma_f6_kernel<4>>(grid, block, lds, st, a);
             }
         }
     }
     if (prec == MPG_PREC_F16X3) {
         switch (nt) {
-            case 1: return launch_one<1, 3, D2S>(grid, lds, st, a);
-            case 2: return launch_one<2, 3, D2S>(grid, lds, st, a);
-            case 3: return launch_one<3, 3, D2S>(grid, lds, st, a);
-            default: return launch_one<4, 3, D2S>(grid, lds, st, a);
+            case 1: return mpg::launch_dyn_lds<conv_mfma_kernel<1, 3, D2S>>(grid, block, lds, st, a);
+            case 2: return mpg::launch_dyn_lds<conv_mfma_kernel<2, 3, D2S>>(grid, block, lds, st, a);
+            case 3: return mpg::launch_dyn_lds<conv_mfma_kernel<3, 3, D2S>>(grid, block, lds, st, a);
+            default: return mpg::launch_dyn_lds<conv_mfma_kernel<4, 3, D2S>>(grid, block, lds, st, a);
         }
     }
     switch (nt) {
-        case 1: return launch_one<1, 1, D2S>(grid, lds, st, a);
-        case 2: return launch_one<2, 1, D2S>(grid, lds, st, a);
-        case 3: return launch_one<3, 1, D2S>(grid, lds, st, a);
-        default: return launch_one<4, 1, D2S>(grid, lds, st, a);
+        case 1: return mpg::launch_dyn_lds<conv_mfma_kernel<1, 1, D2S>>(grid, block, lds, st, a);
+        case 2: return mpg::launch_dyn_lds<conv_mfma_kernel<2, 1, D2S>>(grid, block, lds, st, a);
+        case 3: return mpg::launch_dyn_lds<conv_mfma_kernel<3, 1, D2S>>(grid, block, lds, st, a);
+        default: return mpg::launch_dyn_lds<conv_mfma_kernel<4, 1, D2S>>(grid, block, lds, st, a);
     }
 }
 
@@ -1954,22 +1958,13 @@ extern "C" size_t mpg_conv_pack_size(int kh, int kw, int cin, int cout, int prec
 
 static size_t pack_base_bytes(int kh, int kw, int cin, int cout, int prec) {
     if (kh < 1 || kw < 1 || kh > 7 || kw > 7 || cin < 1 || cout < 1 || cout > 128) return 0;
+    if (prec != MPG_PREC_F16X1 && prec != MPG_PREC_F16F6 && prec != MPG_PREC_F16X3) return 0;
     const int nt = (cout + 31) / 32;
-    if (prec == MPG_PREC_F16F6) {
-        if (!f6_supported(nt)) return 0;
-        const SegShape ss = seg_shape_f6(kh, kw, cin, nt);
-        // a segment whose tables + two images + ring cannot fit the 160 KiB of LDS is "not available at this
-        // precision" (callers then pack for MPG_PREC_F16X3), e.g. 7x7 with four cout tiles
-        const size_t tabs = ss.direct ? TAPOFF_BYTES : (((size_t)ss.sc * 8 * 4 + 1023) / 1024) * 1024;
-        if ((tabs < (size_t)TAPOFF_BYTES ? (size_t)TAPOFF_BYTES : tabs) + 2 * (size_t)ss.img_bytes + (size_t)3 * 8 * nt * 1024 > 160 * 1024)
-            return 0;
-        return (size_t)ss.sc * 8 * nt * 1024;
-    }
-    if (prec != MPG_PREC_F16X1 && prec != MPG_PREC_F16X3) return 0;
-    const Shape ps = pipe_shape(nt, prec);
     const SegShape ss = seg_shape(kh, kw, cin, nt, prec);
-    const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
-    return (size_t)ss.nchunks * ss.sc * ps.ks * nt * 1024 * npl;
+    // a segment whose tables + two images + ring cannot fit the LDS is "not available at this precision" (callers then
+    // pack for MPG_PREC_F16X3), e.g. 7x7 with four cout tiles at MPG_PREC_F16F6
+    if (lds_plan(ss.slots, ss.img_bytes, pipe_shape(nt, prec)).total > LDS_MAX) return 0;
+    return (size_t)ss.stages * pipe_shape(nt, prec).wstage;
 }
 
 extern "C" int mpg_conv_pack_weights(mpg_stream_t stream, const float* w_hwio, int kh, int kw, int w_cin_total,
@@ -1985,45 +1980,31 @@ extern "C" int mpg_conv_pack_weights(mpg_stream_t stream, const float* w_hwio, i
     MPG_REQUIRE(need > 0, "mpg_conv_pack_weights: %dx%d %d->%d not available at prec %d", kh, kw, cin, cout, prec);
     MPG_REQUIRE(out_bytes >= need, "mpg_conv_pack_weights: out buffer %zu < %zu", out_bytes, need);
     const int nt = (cout + 31) / 32;
+    const SegShape ss = seg_shape(kh, kw, cin, nt, prec);
     if (prec == MPG_PREC_F16F6) {
-        const SegShape ss = seg_shape_f6(kh, kw, cin, nt);
         const long total = (long)ss.sc * nt * 64;
         hipLaunchKernelGGL(pack_weights_f6_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
                            w_hwio, kh, kw, w_cin_total, w_c_off, cin, cout, wscale, cout_scale, nt, ss.sc, ss.direct, ss.tp,
                            (char*)out);
-        if (small_layer(cin, cout))
-            hipLaunchKernelGGL(pack_small_kernel, dim3((kh * kw * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hwio,
-                               kh * kw, w_cin_total, w_c_off, cin, cout, wscale, cout_scale,
-                               (float*)((char*)out + pack_base_bytes(kh, kw, cin, cout, prec)));
-        MPG_LAUNCH_CHECK("pack_weights_f6_kernel");
+    } else {
+        const int ks = pipe_shape(nt, prec).ks;
+        const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
+        const long total = (long)ss.stages * ks * nt * 512;
+        hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           w_hwio, kh, kw, w_cin_total, w_c_off, cin, cout, wscale, cout_scale, nt, ks, npl, ss.cgc,
+                           ss.nchunks, ss.sc, (_Float16*)out);
     }
-    const Shape ps = pipe_shape(nt, prec);
-    const SegShape ss = seg_shape(kh, kw, cin, nt, prec);
-    const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
-    const long total = (long)ss.nchunks * ss.sc * ps.ks * nt * 512;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_hwio, kh, kw,
-                       w_cin_total, w_c_off, cin, cout, wscale, cout_scale, nt, ps.ks, npl, ss.cgc, ss.nchunks, ss.sc,
-                       (_Float16*)out);
     if (small_layer(cin, cout))
         hipLaunchKernelGGL(pack_small_kernel, dim3((kh * kw * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_hwio,
                            kh * kw, w_cin_total, w_c_off, cin, cout, wscale, cout_scale,
                            (float*)((char*)out + pack_base_bytes(kh, kw, cin, cout, prec)));
-    MPG_LAUNCH_CHECK("pack_weights_kernel");
+    MPG_LAUNCH_CHECK(prec == MPG_PREC_F16F6 ? "pack_weights_f6_kernel" : "pack_weights_kernel");
 }
+
+// SAME padding in front of a k-wide filter; pad_hi moves the odd pixel of an even filter to the front
+static inline int pad_before(int k, int pad_hi) { return pad_hi ? k / 2 : (k - 1) / 2; }
 
 // One residual block of <= 8-channel convolutions as a single launch (conv_small_pair_kernel).
-template <int CI, int CM, int CO>
-static hipError_t launch_pair(dim3 grid, size_t lds, hipStream_t st, const PairArgs& a) {
-    static int lds_limit[64] = {0};
-    if (lds > 48 * 1024) {
-        hipError_t e = mpg::ensure_dyn_lds(reinterpret_cast<const void*>(&conv_small_pair_kernel<CI, CM, CO>), (int)lds, lds_limit);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((conv_small_pair_kernel<CI, CM, CO>), grid, dim3(256), lds, st, a);
-    return hipSuccess;
-}
-
 extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_desc* d) {
     MPG_REQUIRE(d != nullptr, "mpg_conv2d_small_pair: null desc");
     MPG_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1 && d->n <= 65535, "mpg_conv2d_small_pair: bad shape %d x %d x %d", d->n, d->h, d->w);
@@ -2050,9 +2031,9 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
     a.wa = (const float*)((const char*)d->wpack_a + pack_base_bytes(d->kh_a, d->kw_a, d->cin, d->cmid, d->prec));
     a.wb = (const float*)((const char*)d->wpack_b + pack_base_bytes(d->kh_b, d->kw_b, d->cmid, d->cout, d->prec));
     a.wsc = d->wpack_s ? (const float*)((const char*)d->wpack_s + pack_base_bytes(d->kh_s, d->kw_s, d->cin, d->cout, d->prec)) : nullptr;
-    a.kha = d->kh_a; a.kwa = d->kw_a; a.pta = (d->kh_a - 1) / 2; a.pla = (d->kw_a - 1) / 2;
-    a.khb = d->kh_b; a.kwb = d->kw_b; a.ptb = (d->kh_b - 1) / 2; a.plb = (d->kw_b - 1) / 2;
-    a.khs = d->wpack_s ? d->kh_s : 1; a.kws = d->wpack_s ? d->kw_s : 1; a.pts = (a.khs - 1) / 2; a.pls = (a.kws - 1) / 2;
+    a.kha = d->kh_a; a.kwa = d->kw_a; a.pta = pad_before(d->kh_a, 0); a.pla = pad_before(d->kw_a, 0);
+    a.khb = d->kh_b; a.kwb = d->kw_b; a.ptb = pad_before(d->kh_b, 0); a.plb = pad_before(d->kw_b, 0);
+    a.khs = d->wpack_s ? d->kh_s : 1; a.kws = d->wpack_s ? d->kw_s : 1; a.pts = pad_before(a.khs, 0); a.pls = pad_before(a.kws, 0);
     a.bias_a = d->bias_a; a.bias_b = d->bias_b; a.act_a = d->act_a; a.act_b = d->act_b; a.leak_a = d->leak_a; a.leak_b = d->leak_b;
     a.cout = d->cout; a.y = d->y; a.y_g8 = (char*)d->y_g8;
     const int mw = SM_TW + a.kwb - 1, mh = SM_TH + a.khb - 1;
@@ -2064,11 +2045,12 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
     const int ci = d->cin == 1 ? 1 : d->cin <= 4 ? 4 : 8, cm = d->cmid <= 2 ? 2 : 8, co = d->cout == 1 ? 1 : 8;
     const size_t lds = ((size_t)((ci + 3) / 4) * a.x_px + (size_t)((cm + 3) / 4) * a.mid_px) * 16 +
                        ((size_t)a.kha * a.kwa * ci * cm + (size_t)a.khb * a.kwb * cm * co + (size_t)a.khs * a.kws * ci * co) * sizeof(float);
-    MPG_REQUIRE(lds <= 160 * 1024, "mpg_conv2d_small_pair: LDS budget %zu exceeds 160 KiB", lds);
+    MPG_REQUIRE(lds <= LDS_MAX, "mpg_conv2d_small_pair: LDS budget %zu exceeds 160 KiB", lds);
     const dim3 grid((unsigned)((d->w + SM_TW - 1) / SM_TW), (unsigned)((d->h + SM_TH - 1) / SM_TH), (unsigned)d->n);
     hipError_t le = hipSuccess;
     switch (ci * 100 + cm * 10 + co) {
-#define MPG_PAIR(CI, CM, CO) case CI * 100 + CM * 10 + CO: le = launch_pair<CI, CM, CO>(grid, lds, (hipStream_t)stream, a); break;
+#define MPG_PAIR(CI, CM, CO) case CI * 100 + CM * 10 + CO: \
+        le = mpg::launch_dyn_lds<conv_small_pair_kernel<CI, CM, CO>>(grid, dim3(256), lds, (hipStream_t)stream, a); break;
         MPG_PAIR(1, 2, 1) MPG_PAIR(1, 2, 8) MPG_PAIR(1, 8, 1) MPG_PAIR(1, 8, 8)
         MPG_PAIR(4, 2, 1) MPG_PAIR(4, 2, 8) MPG_PAIR(4, 8, 1) MPG_PAIR(4, 8, 8)
         MPG_PAIR(8, 2, 1) MPG_PAIR(8, 2, 8) MPG_PAIR(8, 8, 1) MPG_PAIR(8, 8, 8)
@@ -2090,105 +2072,81 @@ struct D2SOut {
     int cs, coff;
 };
 
-static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOut* d2s) {
-    MPG_REQUIRE(d != nullptr, "mpg_conv2d_fused: null desc");
-    MPG_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1, "mpg_conv2d_fused: bad shape %d x %d x %d", d->n, d->h, d->w);
-    MPG_REQUIRE(d->cout >= 1 && d->cout <= 128, "mpg_conv2d_fused: cout %d not in 1..128", d->cout);
-    MPG_REQUIRE(d->nseg >= 1 && d->nseg <= MPG_MAX_SEG, "mpg_conv2d_fused: nseg %d", d->nseg);
-    MPG_REQUIRE(d->y != nullptr || d->y_g8 != nullptr, "mpg_conv2d_fused: no output requested");
-    MPG_REQUIRE(d->prec == MPG_PREC_F16X1 || d->prec == MPG_PREC_F16X3 || d->prec == MPG_PREC_F16F6,
-                "mpg_conv2d_fused: bad prec %d", d->prec);
-    MPG_REQUIRE(d->act >= MPG_ACT_NONE && d->act <= MPG_ACT_TANH, "mpg_conv2d_fused: bad act %d", d->act);
-    {   // small-channel layers: conv_small_kernel
-        // (the depth-to-space store is an epilogue of the MFMA kernels only: such a launch stays on them)
-        bool small = d->cout <= 8 && !d->pixel_norm && d->post_add == nullptr && d->reserved == 0 && d2s == nullptr;
-        for (int s = 0; s < d->nseg && small; ++s) small = d->seg[s].cin <= 8;
-        if (small) {
-            SmallArgs sa;
-            sa.n = d->n; sa.h = d->h; sa.w = d->w; sa.cout = d->cout; sa.nseg = d->nseg;
-            for (int s = 0; s < d->nseg; ++s) {
-                const mpg_conv_seg& g = d->seg[s];
-                MPG_REQUIRE(g.x && g.wpack, "mpg_conv2d_fused: segment %d null pointer", s);
-                MPG_REQUIRE(g.kh >= 1 && g.kh <= 7 && g.kw >= 1 && g.kw <= 7, "mpg_conv2d_fused: segment %d kernel %dx%d", s, g.kh, g.kw);
-                MPG_REQUIRE(g.cin >= 1 && g.g_off >= 0 && g.g_off < g.cgroups, "mpg_conv2d_fused: segment %d channel-group range", s);
-                MPG_REQUIRE(g.up_log2 >= 0 && g.up_log2 <= 4 && (d->h % (1 << g.up_log2)) == 0 && (d->w % (1 << g.up_log2)) == 0,
-                            "mpg_conv2d_fused: segment %d upsample %d", s, g.up_log2);
-                MPG_REQUIRE((((uintptr_t)g.x) & 15) == 0 && (((uintptr_t)g.wpack) & 15) == 0, "mpg_conv2d_fused: segment %d misaligned", s);
-                SmallSeg& o = sa.seg[s];
-                o.x = (const char*)g.x;
-                o.w = (const float*)((const char*)g.wpack + pack_base_bytes(g.kh, g.kw, g.cin, d->cout, d->prec));
-                o.cg_total = g.cgroups; o.g_off = g.g_off; o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2;
-                o.pt = g.pad_hi ? g.kh / 2 : (g.kh - 1) / 2; o.pl = g.pad_hi ? g.kw / 2 : (g.kw - 1) / 2;
-                o.hs = d->h >> g.up_log2; o.ws = d->w >> g.up_log2; o.cin = g.cin;
-            }
-            for (int s = d->nseg; s < MPG_MAX_SEG; ++s) sa.seg[s] = sa.seg[0];
-            sa.bias = d->bias; sa.in_amax = d->in_amax; sa.act = d->act; sa.leak = d->leak;
-            sa.y = d->y; sa.y_g8 = (char*)d->y_g8;
-            MPG_REQUIRE((((uintptr_t)d->y_g8) & 15) == 0, "mpg_conv2d_fused: misaligned output");
-            const size_t total = (size_t)d->n * d->h * d->w;
-            (void)total;
-            const dim3 sg((unsigned)((d->w + SM_TW - 1) / SM_TW), (unsigned)((d->h + SM_TH - 1) / SM_TH), (unsigned)d->n);
-            int cmax = 1, tmax = 1, tile_px = 0;
-            for (int s = 0; s < d->nseg; ++s) {
-                const mpg_conv_seg& g = d->seg[s];
-                cmax = g.cin > cmax ? g.cin : cmax;
-                tmax = g.kh * g.kw > tmax ? g.kh * g.kw : tmax;
-                const int px = (SM_TH + g.kh - 1) * (SM_TW + g.kw - 1);
-                tile_px = px > tile_px ? px : tile_px;
-            }
-            const int cob = d->cout == 1 ? 1 : d->cout == 2 ? 2 : d->cout <= 4 ? 4 : 8;
-            const int cib = cmax == 1 ? 1 : cmax == 2 ? 2 : cmax <= 4 ? 4 : 8;
-            sa.tile_floats = tile_px * 4 * ((cib + 3) / 4);       // one or two planes of four channels
-#ifndef MPG_SM_PAD
-#define MPG_SM_PAD 0
-#endif
-            const size_t small_lds = ((size_t)sa.tile_floats + (size_t)tmax * cib * cob) * sizeof(float) + MPG_SM_PAD;
-            switch (cob * 16 + cib) {
-#define MPG_SMALL(CO, CI) \
-    case CO * 16 + CI: hipLaunchKernelGGL((conv_small_kernel<CO, CI>), sg, dim3(256), small_lds, (hipStream_t)stream, sa); break;
-                MPG_SMALL(1, 1) MPG_SMALL(1, 2) MPG_SMALL(1, 4) MPG_SMALL(1, 8)
-                MPG_SMALL(2, 1) MPG_SMALL(2, 2) MPG_SMALL(2, 4) MPG_SMALL(2, 8)
-                MPG_SMALL(4, 1) MPG_SMALL(4, 2) MPG_SMALL(4, 4) MPG_SMALL(4, 8)
-                MPG_SMALL(8, 1) MPG_SMALL(8, 2) MPG_SMALL(8, 4) MPG_SMALL(8, 8)
-#undef MPG_SMALL
-                default: break;
-            }
-            MPG_LAUNCH_CHECK("conv_small_kernel");
-        }
-    }
-    const int nt = (d->cout + 31) / 32;
-    const bool f8 = d->prec == MPG_PREC_F16F6;
-    if (f8 && !f6_supported(nt)) {
-        mpg::set_error("mpg_conv2d_fused: MPG_PREC_F16F6 not available for cout %d", d->cout);
-        return MPG_ERR_UNSUPPORTED;
-    }
-    Shape ps = pipe_shape(nt, f8 ? MPG_PREC_F16X3 : d->prec);
-    if (f8) { ps.th = 16; ps.pt = 16 / f6_waves(nt); }
-    const int npl = d->prec == MPG_PREC_F16X3 ? 2 : 1;
+// the checks of segment s that do not depend on the kernel it runs on
+static int check_segment(const mpg_conv_desc* d, int s) {
+    const mpg_conv_seg& g = d->seg[s];
+    MPG_REQUIRE(g.x && g.wpack, "mpg_conv2d_fused: segment %d null pointer", s);
+    MPG_REQUIRE(g.kh >= 1 && g.kh <= 7 && g.kw >= 1 && g.kw <= 7, "mpg_conv2d_fused: segment %d kernel %dx%d", s, g.kh, g.kw);
+    MPG_REQUIRE(g.cin >= 1 && g.g_off >= 0 && g.g_off + (g.cin + 7) / 8 <= g.cgroups,
+                "mpg_conv2d_fused: segment %d channel-group range", s);
+    MPG_REQUIRE(g.up_log2 >= 0 && g.up_log2 <= 4, "mpg_conv2d_fused: segment %d up_log2 %d", s, g.up_log2);
+    MPG_REQUIRE((d->h % (1 << g.up_log2)) == 0 && (d->w % (1 << g.up_log2)) == 0,
+                "mpg_conv2d_fused: segment %d: %dx%d not divisible by upsample %d", s, d->h, d->w, 1 << g.up_log2);
+    MPG_REQUIRE((((uintptr_t)g.x) & 15) == 0 && (((uintptr_t)g.wpack) & 15) == 0, "mpg_conv2d_fused: segment %d misaligned", s);
+    return MPG_OK;
+}
 
+// small-channel layers (every cin and cout <= 8, plain epilogue): conv_small_kernel
+static int launch_small(hipStream_t stream, const mpg_conv_desc* d) {
+    SmallArgs sa;
+    sa.n = d->n; sa.h = d->h; sa.w = d->w; sa.cout = d->cout; sa.nseg = d->nseg;
+    int cmax = 1, tmax = 1, tile_px = 0;
+    for (int s = 0; s < d->nseg; ++s) {
+        if (const int rc = check_segment(d, s)) return rc;
+        const mpg_conv_seg& g = d->seg[s];
+        SmallSeg& o = sa.seg[s];
+        o.x = (const char*)g.x;
+        o.w = (const float*)((const char*)g.wpack + pack_base_bytes(g.kh, g.kw, g.cin, d->cout, d->prec));
+        o.cg_total = g.cgroups; o.g_off = g.g_off; o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2;
+        o.pt = pad_before(g.kh, g.pad_hi); o.pl = pad_before(g.kw, g.pad_hi);
+        o.hs = d->h >> g.up_log2; o.ws = d->w >> g.up_log2; o.cin = g.cin;
+        cmax = g.cin > cmax ? g.cin : cmax;
+        tmax = g.kh * g.kw > tmax ? g.kh * g.kw : tmax;
+        const int px = (SM_TH + g.kh - 1) * (SM_TW + g.kw - 1);
+        tile_px = px > tile_px ? px : tile_px;
+    }
+    for (int s = d->nseg; s < MPG_MAX_SEG; ++s) sa.seg[s] = sa.seg[0];
+    sa.bias = d->bias; sa.in_amax = d->in_amax; sa.act = d->act; sa.leak = d->leak;
+    sa.y = d->y; sa.y_g8 = (char*)d->y_g8;
+    MPG_REQUIRE((((uintptr_t)d->y_g8) & 15) == 0, "mpg_conv2d_fused: misaligned output");
+    const dim3 grid((unsigned)((d->w + SM_TW - 1) / SM_TW), (unsigned)((d->h + SM_TH - 1) / SM_TH), (unsigned)d->n);
+    const int cob = d->cout == 1 ? 1 : d->cout == 2 ? 2 : d->cout <= 4 ? 4 : 8;
+    const int cib = cmax == 1 ? 1 : cmax == 2 ? 2 : cmax <= 4 ? 4 : 8;
+    sa.tile_floats = tile_px * 4 * ((cib + 3) / 4);       // one or two planes of four channels
+    const size_t lds = ((size_t)sa.tile_floats + (size_t)tmax * cib * cob) * sizeof(float) + MPG_SM_PAD;
+    switch (cob * 16 + cib) {
+#define MPG_SMALL(CO, CI) \
+    case CO * 16 + CI: hipLaunchKernelGGL((conv_small_kernel<CO, CI>), grid, dim3(256), lds, stream, sa); break;
+        MPG_SMALL(1, 1) MPG_SMALL(1, 2) MPG_SMALL(1, 4) MPG_SMALL(1, 8)
+        MPG_SMALL(2, 1) MPG_SMALL(2, 2) MPG_SMALL(2, 4) MPG_SMALL(2, 8)
+        MPG_SMALL(4, 1) MPG_SMALL(4, 2) MPG_SMALL(4, 4) MPG_SMALL(4, 8)
+        MPG_SMALL(8, 1) MPG_SMALL(8, 2) MPG_SMALL(8, 4) MPG_SMALL(8, 8)
+#undef MPG_SMALL
+        default: break;
+    }
+    MPG_LAUNCH_CHECK("conv_small_kernel");
+}
+
+// conv_mfma_kernel / conv_mfma_f6_kernel; d2s: the depth-to-space store of mpg_conv2d_fused_d2s
+static int launch_mfma(hipStream_t stream, const mpg_conv_desc* d, const D2SOut* d2s) {
+    const int nt = (d->cout + 31) / 32;
+    const Shape& ps = pipe_shape(nt, d->prec);
     ConvArgs a;
     a.n = d->n; a.h = d->h; a.w = d->w; a.cout = d->cout; a.nseg = d->nseg;
     int max_img = 0, max_slots = 0;
     for (int s = 0; s < d->nseg; ++s) {
+        if (const int rc = check_segment(d, s)) return rc;
         const mpg_conv_seg& g = d->seg[s];
-        MPG_REQUIRE(g.x && g.wpack, "mpg_conv2d_fused: segment %d null pointer", s);
-        MPG_REQUIRE(g.kh >= 1 && g.kh <= 7 && g.kw >= 1 && g.kw <= 7, "mpg_conv2d_fused: segment %d kernel %dx%d", s, g.kh, g.kw);
-        MPG_REQUIRE(g.cin >= 1 && g.g_off >= 0 && g.g_off + (g.cin + 7) / 8 <= g.cgroups,
-                    "mpg_conv2d_fused: segment %d channel-group range", s);
-        MPG_REQUIRE(g.up_log2 >= 0 && g.up_log2 <= 4, "mpg_conv2d_fused: segment %d up_log2 %d", s, g.up_log2);
-        MPG_REQUIRE((d->h % (1 << g.up_log2)) == 0 && (d->w % (1 << g.up_log2)) == 0,
-                    "mpg_conv2d_fused: segment %d: %dx%d not divisible by upsample %d", s, d->h, d->w, 1 << g.up_log2);
-        MPG_REQUIRE((((uintptr_t)g.x) & 15) == 0 && (((uintptr_t)g.wpack) & 15) == 0, "mpg_conv2d_fused: segment %d misaligned", s);
-        const SegShape ss = f8 ? seg_shape_f6(g.kh, g.kw, g.cin, nt) : seg_shape(g.kh, g.kw, g.cin, nt, d->prec);
-        MPG_REQUIRE(f8 || ss.sc * ps.ks * 2 <= TAPOFF_BYTES / 4, "mpg_conv2d_fused: segment %d tap table too large", s);
-        if (f8 && !ss.direct) max_slots = ss.sc * 8 > max_slots ? ss.sc * 8 : max_slots;
+        const SegShape ss = seg_shape(g.kh, g.kw, g.cin, nt, d->prec);
+        // conv_mfma_kernel's table is the fixed TAPOFF_BYTES; conv_mfma_f6_kernel's grows with the launch (tap_bytes)
+        MPG_REQUIRE(d->prec == MPG_PREC_F16F6 || ss.slots <= TAPOFF_BYTES / 4, "mpg_conv2d_fused: segment %d tap table too large", s);
         SegArgs& o = a.seg[s];
         o.x = (const char*)g.x; o.w = (const char*)g.wpack;
         o.cg_seg = (g.cin + 7) / 8; o.cg_total = g.cgroups; o.g_off = g.g_off;
         o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2;
         o.cgc = ss.cgc; o.nchunks = ss.nchunks; o.sc = ss.sc;
         o.ih = ps.th + g.kh - 1; o.iw = TW + g.kw - 1;
-        o.pt = g.pad_hi ? g.kh / 2 : (g.kh - 1) / 2; o.pl = g.pad_hi ? g.kw / 2 : (g.kw - 1) / 2;
+        o.pt = pad_before(g.kh, g.pad_hi); o.pl = pad_before(g.kw, g.pad_hi);
         o.hs = d->h >> g.up_log2; o.ws = d->w >> g.up_log2;
         o.np = ss.np; o.ni_img = ss.ni_img;
         o.direct = ss.direct;
@@ -2197,6 +2155,7 @@ static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOu
                     "mpg_conv2d_fused: segment %d: %dx%d too large for the 1x1 path (32-bit group offsets)", s, d->h, d->w);
         o.pref = ss.pref;
         max_img = ss.img_bytes > max_img ? ss.img_bytes : max_img;
+        max_slots = ss.slots > max_slots ? ss.slots : max_slots;
     }
     for (int s = d->nseg; s < MPG_MAX_SEG; ++s) a.seg[s] = a.seg[0];
     a.bias = d->bias; a.in_amax = d->in_amax; a.act = d->act; a.leak = d->leak; a.pn = d->pixel_norm; a.pn_eps = d->pn_eps;
@@ -2214,15 +2173,9 @@ static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOu
     a.dbg = d->reserved;
     const long nblk = (long)d->n * a.tiles_x * a.tiles_y;
     MPG_REQUIRE(nblk < (1L << 31), "mpg_conv2d_fused: grid too large");
-    const int waves = f8 ? f6_waves(nt) : 4;
-    const size_t ring = f8 ? (size_t)3 * 8 * nt * 1024 : (size_t)ps.r * ps.ks * nt * 1024 * npl;
-    // F16F6: the tap-offset table ([stage][half][k-step]) of max_slots entries, 1 KiB granules
-    a.tap_bytes = f8 ? ((max_slots * 4 + 1023) / 1024) * 1024 : TAPOFF_BYTES;
-    if (a.tap_bytes < TAPOFF_BYTES) a.tap_bytes = TAPOFF_BYTES;
-    const size_t lds_loop = (size_t)a.tap_bytes + 2 * (size_t)max_img + ring;
-    const size_t lds_epi = TAPOFF_BYTES + (size_t)waves * 32 * (nt * 32 + 4) * sizeof(float);
-    const size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
-    MPG_REQUIRE(lds <= 160 * 1024, "mpg_conv2d_fused: LDS budget %zu exceeds 160 KiB", lds);
+    const LdsPlan lds = lds_plan(max_slots, max_img, ps);
+    a.tap_bytes = (int)lds.tap;
+    MPG_REQUIRE(lds.total <= LDS_MAX, "mpg_conv2d_fused: LDS budget %zu exceeds 160 KiB", lds.total);
     const dim3 grid((unsigned)nblk);
     hipError_t le;
     if (d2s != nullptr) {
@@ -2231,12 +2184,27 @@ static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOu
         ad.cs = d2s->cs;
         ad.coff = d2s->coff;
         ad.cg = d2s->cs / 8;
-        le = launch_conv<true>(d->prec, nt, grid, lds, (hipStream_t)stream, ad);
+        le = launch_conv<true>(d->prec, nt, grid, lds.total, stream, ad);
     } else {
-        le = launch_conv<false>(d->prec, nt, grid, lds, (hipStream_t)stream, a);
+        le = launch_conv<false>(d->prec, nt, grid, lds.total, stream, a);
     }
     if (le != hipSuccess) return mpg::hip_check(le, "mpg_conv2d_fused: hipFuncSetAttribute(dynamic LDS)");
     MPG_LAUNCH_CHECK("conv_mfma_kernel");
+}
+
+static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOut* d2s) {
+    MPG_REQUIRE(d != nullptr, "mpg_conv2d_fused: null desc");
+    MPG_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1, "mpg_conv2d_fused: bad shape %d x %d x %d", d->n, d->h, d->w);
+    MPG_REQUIRE(d->cout >= 1 && d->cout <= 128, "mpg_conv2d_fused: cout %d not in 1..128", d->cout);
+    MPG_REQUIRE(d->nseg >= 1 && d->nseg <= MPG_MAX_SEG, "mpg_conv2d_fused: nseg %d", d->nseg);
+    MPG_REQUIRE(d->y != nullptr || d->y_g8 != nullptr, "mpg_conv2d_fused: no output requested");
+    MPG_REQUIRE(d->prec == MPG_PREC_F16X1 || d->prec == MPG_PREC_F16X3 || d->prec == MPG_PREC_F16F6,
+                "mpg_conv2d_fused: bad prec %d", d->prec);
+    MPG_REQUIRE(d->act >= MPG_ACT_NONE && d->act <= MPG_ACT_TANH, "mpg_conv2d_fused: bad act %d", d->act);
+    // (the depth-to-space store is an epilogue of the MFMA kernels only: such a launch stays on them)
+    bool small = d->cout <= 8 && !d->pixel_norm && d->post_add == nullptr && d->reserved == 0 && d2s == nullptr;
+    for (int s = 0; s < d->nseg && small; ++s) small = d->seg[s].cin <= 8;
+    return small ? launch_small((hipStream_t)stream, d) : launch_mfma((hipStream_t)stream, d, d2s);
 }
 
 extern "C" int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d) {

@@ -761,12 +761,8 @@ extern "C" int mpg_volume_transpose(mpg_stream_t stream, const float* v, int d0,
         const size_t nblk = (size_t)t.tiles_a * t.tiles_b * t.dr;
         MPG_REQUIRE(nblk < (1UL << 31), "mpg_volume_transpose: grid too large");
         constexpr size_t tile_bytes = (size_t)TRT * (TRT + 1) * sizeof(float);
-        if (tile_bytes > 48 * 1024) {
-            static int lds_limit[64] = {0};
-            hipError_t e = mpg::ensure_dyn_lds(reinterpret_cast<const void*>(&transpose_tiled_kernel), (int)tile_bytes, lds_limit);
-            if (e != hipSuccess) return mpg::hip_check(e, "mpg_volume_transpose: dynamic LDS");
-        }
-        hipLaunchKernelGGL(transpose_tiled_kernel, dim3((unsigned)nblk), dim3(BLK), tile_bytes, (hipStream_t)stream, v, t, out);
+        const hipError_t e = mpg::launch_dyn_lds<transpose_tiled_kernel>(dim3((unsigned)nblk), dim3(BLK), tile_bytes, (hipStream_t)stream, v, t, out);
+        if (e != hipSuccess) return mpg::hip_check(e, "mpg_volume_transpose: dynamic LDS");
         MPG_LAUNCH_CHECK("transpose_tiled_kernel");
     }
     if (c == 1 && ident_map && perm[0] == 1 && perm[1] == 0 && perm[2] == 2 && d2 % 4 == 0 && ((uintptr_t)v & 15) == 0 &&

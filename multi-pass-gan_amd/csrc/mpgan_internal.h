@@ -72,4 +72,20 @@ inline hipError_t ensure_dyn_lds(const void* kern, int bytes, int* slot) {
     return hipSuccess;
 }
 
+// Launch `Kernel` with `lds` bytes of dynamic LDS.  Above the 48 KiB a kernel gets by default its limit is raised
+// first (ensure_dyn_lds; the array below is the kernel's own, one entry per device), to max(lds, Reserve): a kernel
+// that names a Reserve pays the driver call once, whatever sizes its later launches ask for.  The launch's own
+// error is left in hipGetLastError().
+template <auto Kernel, size_t Reserve = 0, class... A>
+hipError_t launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    static int lds_limit[64] = {0};
+    const size_t want = lds > Reserve ? lds : Reserve;
+    if (want > 48 * 1024) {
+        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(Kernel), (int)want, lds_limit);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return hipSuccess;
+}
+
 }  // namespace mpg

@@ -103,6 +103,7 @@ struct WgArgs {
 };
 
 constexpr int WG_WAVES = 8, WG_THREADS = WG_WAVES * 64;
+constexpr size_t WG_LDS_MAX = 160 * 1024;   // LDS of a CU: both kernels have their dynamic-LDS limit raised to it once
 // LDS-DMA instructions per wave for the x piece of a chunk: 6 cover a 64-pixel chunk of 128 channels, hi + lo, with the
 // halo and the pad units (2 * 16 * 84 units of 16 bytes); 5 the dy piece of 128 channels (2 * 16 * 68)
 constexpr int X_UNITS_DMA = 6;
@@ -791,24 +792,16 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
 
 template <int KH, int KW, int COTW, int PREC>
 hipError_t launch_ring(hipStream_t s, const WrArgs& a, int blocks) {
-    auto kern = wgrad_ring_kernel<KH, KW, COTW, PREC>;
-    static int lds_limit[64] = {0};
     constexpr size_t lds = (size_t)(KH + 1) * WR_XSLOT + 2 * (size_t)(2 * COTW * 4 * WR_DP * 16);
-    static_assert(lds <= 160 * 1024, "ring kernel LDS plan");
-    hipError_t e = mpg::ensure_dyn_lds((const void*)kern, 160 * 1024, lds_limit);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG_THREADS), lds, s, a);
-    return hipGetLastError();
+    static_assert(lds <= WG_LDS_MAX, "ring kernel LDS plan");
+    const hipError_t e = mpg::launch_dyn_lds<wgrad_ring_kernel<KH, KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks), dim3(WG_THREADS), lds, s, a);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 template <int KW, int COTW, int PREC>
 hipError_t launch(hipStream_t s, const WgArgs& a, int blocks, size_t lds_bytes, int windows) {
-    auto kern = wgrad_mfma_kernel<KW, COTW, PREC>;
-    static int lds_limit[64] = {0};
-    hipError_t e = mpg::ensure_dyn_lds((const void*)kern, 160 * 1024, lds_limit);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(blocks * windows), dim3(WG_THREADS), lds_bytes, s, a);
-    return hipGetLastError();
+    const hipError_t e = mpg::launch_dyn_lds<wgrad_mfma_kernel<KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks * windows), dim3(WG_THREADS), lds_bytes, s, a);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 inline size_t g8_bytes(int n, int h, int w, int c) { return (size_t)n * ((c + 7) / 8) * 2 * h * w * 16; }
@@ -898,7 +891,7 @@ int wgrad_launches(hipStream_t s, const char* xg, const char* dg, const float* x
             a.xp = a.chunk + 16 + LDS_ROW_PAD;
             a.dp = a.chunk + LDS_ROW_PAD;
             const size_t lds = 2 * ((size_t)x_units(a.chunk) + d_units(a.chunk)) * 16;
-            MPG_REQUIRE(lds <= 160 * 1024, "mpg_conv2d_wgrad: LDS plan %zu bytes", lds);
+            MPG_REQUIRE(lds <= WG_LDS_MAX, "mpg_conv2d_wgrad: LDS plan %zu bytes", lds);
             MPG_REQUIRE(x_units(a.chunk) <= xu * WG_THREADS && d_units(a.chunk) <= D_UNITS_DMA * WG_THREADS, "mpg_conv2d_wgrad: copy plan");
             const int rows = n * h;
             int want = 1024 / kh;

@@ -64,6 +64,9 @@ class G8(object):
     def groups(self):
         return (self.c + 7) // 8
 
+    def data_ptr(self):
+        return self.buf.data_ptr()
+
     @staticmethod
     def empty(n, h, w, c, device, flavour=G8_F16):
         buf = torch.empty((n, (c + 7) // 8, 2, h, w, 8), dtype=torch.float16, device=device)
@@ -162,19 +165,14 @@ class Segment(object):
         self.x, self.packed, self.g_off, self.up_log2 = x, packed, c_off // 8, up_log2
 
 
-def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=False, pn_eps=1e-8,
-                 post_add=None, post_add_coff=0, out=None, want_f32=True, want_g8=False, reserved=0,
-                 in_amax=None):
-    """y = post(act(sum_s conv_SAME(up_s(x_s), W_s) + bias)) [+ post_add]; see include/mpgan.h.
-    Returns the requested outputs in the order (fp32 NHWC, G8): a single object when one is requested,
-    else a tuple."""
-    lib = _lib.load()
+def _conv_desc(segments, out_hw, bias, act, leak):
+    """the ConvDesc of a fused-convolution launch without its outputs: the checked segments, bias (a contiguous fp32
+    GPU tensor of cout entries), activation and precision"""
     if not 1 <= len(segments) <= _lib.MAX_SEG:
         raise _lib.MpgError("conv2d_fused: %d segments (1..%d supported)" % (len(segments), _lib.MAX_SEG))
     p0 = segments[0].packed
     h, w = out_hw
     n = segments[0].x.n
-    dev = segments[0].x.buf.device
     d = _lib.ConvDesc()
     d.n, d.h, d.w, d.cout, d.nseg = n, h, w, p0.cout, len(segments)
     for i, s in enumerate(segments):
@@ -196,35 +194,50 @@ def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=Fal
         g.kh, g.kw, g.up_log2 = pk.kh, pk.kw, s.up_log2
         g.pad_hi = s.pad_hi
     if bias is not None:
-        b = _dev(bias, "bias")
-        if b.numel() != p0.cout:
-            raise _lib.MpgError("conv2d_fused: bias has %d entries, cout is %d" % (b.numel(), p0.cout))
-        d.bias = b.data_ptr()
+        if bias.numel() != p0.cout:
+            raise _lib.MpgError("conv2d_fused: bias has %d entries, cout is %d" % (bias.numel(), p0.cout))
+        d.bias = bias.data_ptr()
     d.act, d.leak = _lib.act_id(act), leak
+    d.prec = p0.prec
+    return d
+
+
+def _alloc_outputs(shape, dev, want_f32, want_g8, out, what):
+    """the outputs of a launch of NHWC `shape`: (fp32 tensor or None, G8 or None, [those requested, in that order]).
+    `out`, a contiguous fp32 GPU tensor of exactly that shape, receives the fp32 result (and asks for it)."""
+    y = y8 = None
+    if out is not None:
+        y = _dev(out, "out")
+        if tuple(y.shape) != tuple(shape):
+            raise _lib.MpgError("%s: out has shape %s" % (what, tuple(y.shape)))
+    elif want_f32:
+        y = torch.empty(shape, dtype=torch.float32, device=dev)
+    if want_g8:
+        y8 = G8.empty(*shape, dev, G8_F16)
+    outs = [o for o in (y, y8) if o is not None]
+    if not outs:
+        raise _lib.MpgError("%s: no output requested" % what)
+    return y, y8, outs
+
+
+def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=False, pn_eps=1e-8,
+                 post_add=None, post_add_coff=0, out=None, want_f32=True, want_g8=False, reserved=0,
+                 in_amax=None):
+    """y = post(act(sum_s conv_SAME(up_s(x_s), W_s) + bias)) [+ post_add]; see include/mpgan.h.
+    Returns the requested outputs in the order (fp32 NHWC, G8): a single object when one is requested,
+    else a tuple."""
+    lib = _lib.load()
+    d = _conv_desc(segments, out_hw, _dev(bias, "bias") if bias is not None else None, act, leak)
+    shape = (d.n, d.h, d.w, d.cout)
     d.pixel_norm, d.pn_eps = int(bool(pixel_norm)), pn_eps
     if post_add is not None:
         pa = _dev(post_add, "post_add")
-        if pa.dim() != 4 or tuple(pa.shape[:3]) != (n, h, w) or post_add_coff + p0.cout > pa.shape[3]:
+        if pa.dim() != 4 or tuple(pa.shape[:3]) != shape[:3] or post_add_coff + d.cout > pa.shape[3]:
             raise _lib.MpgError("conv2d_fused: post_add %s does not match output" % (tuple(pa.shape),))
         d.post_add, d.post_add_stride, d.post_add_coff = pa.data_ptr(), pa.shape[3], post_add_coff
-    y = y8 = None
-    if out is not None:
-        want_f32 = True
-    if want_f32:
-        if out is None:
-            y = torch.empty((n, h, w, p0.cout), dtype=torch.float32, device=dev)
-        else:
-            y = _dev(out, "out")
-            if tuple(y.shape) != (n, h, w, p0.cout):
-                raise _lib.MpgError("conv2d_fused: out has shape %s" % (tuple(y.shape),))
-        d.y = y.data_ptr()
-    if want_g8:
-        y8 = G8.empty(n, h, w, p0.cout, dev, G8_F16)
-        d.y_g8 = y8.buf.data_ptr()
-    outs = [o for o in (y, y8) if o is not None]
-    if not outs:
-        raise _lib.MpgError("conv2d_fused: no output requested")
-    d.prec, d.reserved = p0.prec, reserved
+    y, y8, outs = _alloc_outputs(shape, segments[0].x.buf.device, want_f32, want_g8, out, "conv2d_fused")
+    d.y, d.y_g8 = _ptr(y), _ptr(y8)
+    d.reserved = reserved
     if in_amax is not None:     # the inputs were converted with to_g8(..., amax=in_amax): undo the power-of-two scale
         d.in_amax = _dev(in_amax, "in_amax").data_ptr()
     _lib.check(lib.mpg_conv2d_fused(_stream(), ctypes.byref(d)), "mpg_conv2d_fused")
@@ -256,61 +269,13 @@ def conv2d_fused_d2s(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, out
         bias = _dev(bias, "bias")
         if bias.numel() != c_total:
             raise _lib.MpgError("conv2d_fused_d2s: bias has %d entries, expected %d" % (bias.numel(), c_total))
-    y = y8 = None
-    if out is not None:
-        want_f32 = True
-    if want_f32:
-        y = torch.empty((n, 2 * h, 2 * w, cs), dtype=torch.float32, device=dev) if out is None else _dev(out, "out")
-        if tuple(y.shape) != (n, 2 * h, 2 * w, cs):
-            raise _lib.MpgError("conv2d_fused_d2s: out has shape %s" % (tuple(y.shape),))
-    if want_g8:
-        y8 = G8.empty(n, 2 * h, 2 * w, cs, dev, G8_F16)
-    outs = [o for o in (y, y8) if o is not None]
-    if not outs:
-        raise _lib.MpgError("conv2d_fused_d2s: no output requested")
+    y, y8, outs = _alloc_outputs((n, 2 * h, 2 * w, cs), dev, want_f32, want_g8, out, "conv2d_fused_d2s")
     for segments, co_off in chunks:
         cw = segments[0].packed.cout
-        d = _conv_desc(segments, out_hw, bias[co_off:co_off + cw] if bias is not None else None, act, leak)
-        if y is not None:
-            d.y = y.data_ptr()
-        if y8 is not None:
-            d.y_g8 = y8.buf.data_ptr()
+        d = _conv_desc(segments, out_hw, bias[co_off:co_off + cw].contiguous() if bias is not None else None, act, leak)
+        d.y, d.y_g8 = _ptr(y), _ptr(y8)
         _lib.check(lib.mpg_conv2d_fused_d2s(_stream(), ctypes.byref(d), 2, c_total, co_off), "mpg_conv2d_fused_d2s")
     return outs[0] if len(outs) == 1 else tuple(outs)
-
-
-def _conv_desc(segments, out_hw, bias, act, leak):
-    """the ConvDesc of conv2d_fused's launch without outputs (segments, bias, activation)"""
-    if not 1 <= len(segments) <= _lib.MAX_SEG:
-        raise _lib.MpgError("conv2d_fused: %d segments (1..%d supported)" % (len(segments), _lib.MAX_SEG))
-    p0 = segments[0].packed
-    h, w = out_hw
-    n = segments[0].x.n
-    d = _lib.ConvDesc()
-    d.n, d.h, d.w, d.cout, d.nseg = n, h, w, p0.cout, len(segments)
-    for i, s in enumerate(segments):
-        g8, pk = s.x, s.packed
-        if (pk.cout, pk.prec) != (p0.cout, p0.prec):
-            raise _lib.MpgError("conv2d_fused: segments packed with different cout/prec")
-        if g8.n != n or g8.h << s.up_log2 != h or g8.w << s.up_log2 != w:
-            raise _lib.MpgError("conv2d_fused: segment %d input %dx%dx%d does not match output %dx%dx%d (up 2^%d)"
-                                % (i, g8.n, g8.h, g8.w, n, h, w, s.up_log2))
-        if s.g_off * 8 + pk.cin > g8.c:
-            raise _lib.MpgError("conv2d_fused: segment %d channel window [%d,%d) exceeds %d"
-                                % (i, s.g_off * 8, s.g_off * 8 + pk.cin, g8.c))
-        g = d.seg[i]
-        g.x, g.wpack = g8.buf.data_ptr(), pk.buf.data_ptr()
-        g.cin, g.cgroups, g.g_off = pk.cin, g8.groups, s.g_off
-        g.kh, g.kw, g.up_log2 = pk.kh, pk.kw, s.up_log2
-        g.pad_hi = s.pad_hi
-    if bias is not None:
-        b = bias.contiguous()
-        if b.numel() != p0.cout:
-            raise _lib.MpgError("conv2d_fused: bias has %d entries, cout is %d" % (b.numel(), p0.cout))
-        d.bias = b.data_ptr()
-    d.act, d.leak = _lib.act_id(act), leak
-    d.prec = p0.prec
-    return d
 
 
 def space_to_depth(x, r):
@@ -376,21 +341,15 @@ def conv2d_small_pair(x, c_off, up_log2, pk_a, pk_b, pk_s, out_hw, bias_a=None, 
         d.bias_b = _dev(bias_b, "bias_b").data_ptr()
     d.act_a, d.leak_a, d.act_b, d.leak_b = _lib.act_id(act_a), leak_a, _lib.act_id(act_b), leak_b
     d.prec = pk_a.prec
-    y = y8 = None
-    if want_f32:
-        if out is not None:
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.n * h * w * pk_b.cout or out.device != dev:
-                raise _lib.MpgError("conv2d_small_pair: `out` does not hold a contiguous fp32 [%d,%d,%d,%d]" % (x.n, h, w, pk_b.cout))
-            y = out.view(x.n, h, w, pk_b.cout)
-        else:
-            y = torch.empty((x.n, h, w, pk_b.cout), dtype=torch.float32, device=dev)
-        d.y = y.data_ptr()
-    if want_g8:
-        y8 = G8.empty(x.n, h, w, pk_b.cout, dev, G8_F16)
-        d.y_g8 = y8.buf.data_ptr()
-    outs = [o for o in (y, y8) if o is not None]
-    if not outs:
-        raise _lib.MpgError("conv2d_small_pair: no output requested")
+    shape = (x.n, h, w, pk_b.cout)
+    if not want_f32:
+        out = None
+    elif out is not None:       # any contiguous fp32 tensor of that many elements (the planner's destination buffers)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.n * h * w * pk_b.cout or out.device != dev:
+            raise _lib.MpgError("conv2d_small_pair: `out` does not hold a contiguous fp32 [%d,%d,%d,%d]" % shape)
+        out = out.view(shape)
+    y, y8, outs = _alloc_outputs(shape, dev, want_f32, want_g8, out, "conv2d_small_pair")
+    d.y, d.y_g8 = _ptr(y), _ptr(y8)
     _lib.check(lib.mpg_conv2d_small_pair(_stream(), ctypes.byref(d)), "mpg_conv2d_small_pair")
     return outs[0] if len(outs) == 1 else tuple(outs)
 
@@ -644,7 +603,6 @@ def add_adjacent(x, s_off=0, s_cnt=None):
 def channel_gather(a, b, cmap, scales=None, scales2=None):
     """out[..., j] = (cat(a, b)[..., cmap[j]] * scales[j]) * scales2[j] in one pass (mpg_channel_gather): the slice / scale /
     concat steps of the velocity channels between the passes (multipassGAN-4x.py:278-283, 1113-1119)"""
-    import ctypes
     lib = _lib.load()
     a = _dev(a.contiguous(), "a")
     ca, cb = a.shape[-1], 0

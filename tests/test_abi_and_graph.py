@@ -25,6 +25,20 @@ def test_library_exports_every_declared_symbol(mpg):
     # 16 chunks of one channel group x 13 one-k-step stages x (4 cout tiles x 1 KiB x hi/lo)
     assert lib.mpg_conv_pack_size(5, 5, 128, 128, 3) == 16 * 13 * 1 * 4 * 1024 * 2
     assert lib.mpg_conv_pack_size(5, 5, 128, 200, 3) == 0
+    # MPG_PREC_F16F6 (2), stages of 8 tap slots x cout tiles x 8 KiB: the direct 1x1 path (8 groups = 1 stage), 16 groups
+    # x 25 taps = 50 stages, a small layer (9 taps padded to 12 slots = 2 stages, + the fp32 table [9][8][8]), and the
+    # 7x7 whose images do not fit the LDS at four cout tiles
+    assert lib.mpg_conv_pack_size(1, 1, 64, 64, 2) == 1 * 2 * 8192
+    assert lib.mpg_conv_pack_size(5, 5, 128, 128, 2) == 50 * 4 * 8192
+    assert lib.mpg_conv_pack_size(3, 3, 4, 8, 2) == 2 * 1 * 8192 + 9 * 64 * 4
+    assert lib.mpg_conv_pack_size(3, 3, 32, 96, 2) == 147456
+    assert lib.mpg_conv_pack_size(7, 7, 128, 128, 2) == 0
+    # MPG_PREC_F16X1 (1), one plane: the same layers (7x7 fits)
+    assert lib.mpg_conv_pack_size(1, 1, 64, 64, 1) == 32768
+    assert lib.mpg_conv_pack_size(5, 5, 128, 128, 1) == 917504
+    assert lib.mpg_conv_pack_size(3, 3, 4, 8, 1) == 8192 + 9 * 64 * 4
+    assert lib.mpg_conv_pack_size(3, 3, 32, 96, 1) == 98304
+    assert lib.mpg_conv_pack_size(7, 7, 128, 128, 1) == 1703936
     assert lib.mpg_g8_bytes(2, 16, 32, 11) == 2 * 2 * 2 * 16 * 32 * 16
 
 
