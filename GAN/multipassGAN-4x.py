@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 import mpgan_amd  # noqa: E402,F401
-from mpgan_amd import checkpoint, multipass, ops, uniio  # noqa: E402
+from mpgan_amd import checkpoint, heldout, multipass, ops, uniio  # noqa: E402
 from mpgan_amd import fluiddataloader as FDL  # noqa: E402
 from mpgan_amd import paramhelpers as ph  # noqa: E402
 
@@ -81,9 +81,6 @@ def train_main():
         exit(1)
     if int(P["pretrain"]) or int(P["pretrainDisc"]) or int(P["pretrainGen"]):
         print("ERROR: the pretraining phases (pretrain / pretrainDisc / pretrainGen, 4x.py:1232-1296) are not built")
-        exit(1)
-    if int(P["genTestImg"]) > -1:
-        print("ERROR: PNG test images during training (genTestImg, 4x.py:1581-1600) are not built")
         exit(1)
     # `dropout` / `dropoutOutput` feed keep_prob, which no layer of the reference graph reads (4x.py:647-657)
     tileSizeLow, toSim = int(P["tileSize"]), int(P["toSim"])
@@ -187,17 +184,17 @@ def train_main():
     n_out = (tileSizeLow * upRes) ** 2
     n_in = (tileSizeLow * tileSizeLow if mode == 2 else n_out) * n_ch
 
-    def getinput():
+    def getinput(size=batch, isTraining=True, augment=aug):
         if device_tiles:
-            bx, by = tiCr.selectRandomTilesDevice(batch, augment=aug)
+            bx, by = tiCr.selectRandomTilesDevice(size, isTraining, augment=augment)
         else:
-            bx, by = tiCr.selectRandomTiles(selectionSize=batch, augment=aug)
+            bx, by = tiCr.selectRandomTiles(selectionSize=size, isTraining=isTraining, augment=augment)
         return bx.reshape(-1, n_in), by.reshape(-1, n_out)
 
-    def gettempo():
+    def gettempo(size=batch, isTraining=True, augment=aug):
         if device_tiles:
-            return tiCr.selectRandomTempoTilesDevice(batch, True, aug, n_t=3, dt=0.5)
-        return tiCr.selectRandomTempoTiles(batch, True, aug, n_t=3, dt=0.5)
+            return tiCr.selectRandomTempoTilesDevice(size, isTraining, augment, n_t=3, dt=0.5)
+        return tiCr.selectRandomTempoTiles(size, isTraining, augment, n_t=3, dt=0.5)
 
     keep_max, kept = int(P["keepMax"]), []
 
@@ -224,19 +221,26 @@ def train_main():
     discRuns, genRuns = int(P["discRuns"]), int(P["genRuns"])
     outputInterval, saveInterval = int(P["outputInterval"]), int(P["saveInterval"])
     save_no, t0 = 0, time.time()
-    avg_d = avg_g = avg_l1 = 0.0
+    # the "test model" section (:1410-1516): every testInterval iterations numTests tiles of the train and of the test split
+    # go through the networks with `train: False` (Trainer4x.evaluate); genTestImg > -1 writes the sampler's image of
+    # the first frame with every report (:1581-1584)
+    testInterval, numTests, genTestImg = int(P["testInterval"]), int(P["numTests"]), int(P["genTestImg"])
+    have_test = tiCr.setBorders[1] > tiCr.setBorders[0]
+    if not have_test:
+        print('no test frames in the data (%d frames): the test section is skipped' % tiCr.setBorders[2])
+    log, image_no = heldout.HeldOutLog(), 0
     print('\n*****TRAINING STARTED*****\n')
     for epoch in range(epochs):
         if decay_lr:
             trainer.set_learning_rate(decayed_lr(epoch))
         for _ in range(discRuns):
             bx, by = getinput()
-            avg_d += float(trainer.disc_step(bx, by)["disc_loss"].detach())
+            log.add_train("avgCost_disc", trainer.disc_step(bx, by)["disc_loss"].detach())
         tempo = None
         if useTempoD:
             for _ in range(discRuns):
                 tempo = gettempo()
-                trainer.tempo_disc_step(*tempo)
+                log.add_train("avgTemCost_disc", trainer.tempo_disc_step(*tempo)["t_disc_loss"].detach())
         for _ in range(genRuns):
             bx, by = getinput()
             trainer.k, trainer.k2 = k_f * trainer.k, k2_f * trainer.k2   # :1342-1343
@@ -245,15 +249,26 @@ def train_main():
                 L = trainer.gen_step_tempo(bx, by, *tempo)
             else:
                 L = trainer.gen_step(bx, by)
-            avg_g += float(L["gen_loss"].detach())
-            avg_l1 += float(L["gen_l1_loss"].detach())
-        if (epoch + 1) % outputInterval == 0:
-            k = float(outputInterval)
-            print('\nEpoch {:05d}/{}, Cost:'.format(epoch + 1, epochs))
-            print('\tdisc: loss: train_loss={:.6f}'.format(avg_d / (k * discRuns)))
-            print('\tgen: loss: train={:.6f} L1={:.6f}'.format(avg_g / (k * genRuns), avg_l1 / (k * genRuns)))
+            log.add_train("avgCost_gen", L["gen_loss"].detach())
+            log.add_train("avgL1Cost_gen", L["gen_l1_loss"].detach())
+            if useTempoD:
+                log.add_train("avgTemCost_gen", L["t_gen_loss"].detach())
+            if useTempoL2:
+                log.add_train("avgTemCost_gen_l", L["tl_gen_loss"].detach())
+        test_now, print_now, image_now = heldout.schedule(epoch, testInterval, outputInterval, genTestImg, have_test)
+        if test_now:                                                     # draw order of :1415-1458
+            train_b, test_b = getinput(numTests, True, False), getinput(numTests, False, False)
+            tempo_b = tempo_test_b = None
+            if useTempoD or useTempoL2:
+                tempo_b, tempo_test_b = gettempo(numTests, True, False), gettempo(numTests, False, False)
+            log.add_test(trainer.evaluate(train_b[0], train_b[1], test_b[0], test_b[1], tempo=tempo_b, tempo_test=tempo_test_b))
+        if print_now:
+            print(log.report(epoch, epochs, outputInterval, discRuns, genRuns, k=trainer.k, kt=kt, kt_l=kt_l))
             print('\t{} epochs took {:.2f} seconds.'.format(outputInterval, time.time() - t0))
-            avg_d = avg_g = avg_l1 = 0.0
+            if image_now:
+                trainer.sample_frame_image(tiCr, heldout.frame_index(fromSim, fromSim, frame_max), test_path + 'test_img/',
+                                           image_no, simSizeHigh)
+                image_no += 1
             t0 = time.time()
         if (epoch + 1) % saveInterval == 0:
             save(save_no)

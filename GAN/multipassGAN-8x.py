@@ -252,7 +252,7 @@ test_path, _ = ph.getNextTestPath(int(P["testPathStartNo"]), basePath)
 print("\nUsing parameters:\n" + ph.paramsToString())
 ph.writeParams(test_path + "params.json")
 
-from mpgan_amd import ops  # noqa: E402
+from mpgan_amd import heldout, ops  # noqa: E402
 from mpgan_amd.arch import Cfg8x  # noqa: E402
 from mpgan_amd.train import Trainer8x  # noqa: E402
 
@@ -279,26 +279,26 @@ if int(P["load_model_test"]) >= 0:
     print("Model restored (%d optimiser slot pairs)." % n_slots)
 
 
-def getinput():
+def getinput(size=batch, isTraining=True, augment=aug):
     """:1497-1537 incl. the 1-in-20 empty-density batches"""
     if device_tiles:
-        batch_xs, batch_ys = tiCr.selectRandomTilesDevice(batch, augment=aug)
+        batch_xs, batch_ys = tiCr.selectRandomTilesDevice(size, isTraining, augment=augment)
     else:
-        batch_xs, batch_ys = tiCr.selectRandomTiles(selectionSize=batch, augment=aug)
+        batch_xs, batch_ys = tiCr.selectRandomTiles(selectionSize=size, isTraining=isTraining, augment=augment)
     if not min(np.random.randint(0, 20), 1):
         batch_xs[:, :, :, :, 0:1] = 0
         if add_adj_idcs:
             batch_xs[:, :, :, :, 4:6] = 0
         batch_xs[:, :, :, :, 1:4] *= (1.0 + np.random.rand() * 1.5)
         batch_ys[:, :, :, :, :] = 0
-    return batch_xs.reshape(-1, cfg.n_input), batch_ys.reshape(batch, -1)
+    return batch_xs.reshape(-1, cfg.n_input), batch_ys.reshape(size, -1)
 
 
-def getTempoinput():
+def getTempoinput(size=batch, isTraining=True, augment=aug):
     if device_tiles:
-        bx, by, bp = tiCr.selectRandomTempoTilesDevice(batch, True, aug, 3, 0.5)
+        bx, by, bp = tiCr.selectRandomTempoTilesDevice(size, isTraining, augment, 3, 0.5)
     else:
-        bx, by, bp = tiCr.selectRandomTempoTiles(batch, True, aug, 3, 0.5)
+        bx, by, bp = tiCr.selectRandomTempoTiles(size, isTraining, augment, 3, 0.5)
     n = bx.shape[0]
     return bx.reshape(n, -1), by.reshape(n, -1), bp.reshape(n, -1)
 
@@ -340,7 +340,27 @@ lrgs = 0
 discRuns, genRuns = int(P["discRuns"]), int(P["genRuns"])
 outputInterval, saveInterval = int(P["outputInterval"]), int(P["saveInterval"])
 decayLR = int(P["decayLR"]) > 0
-avg_d = avg_g = avg_l1 = 0.0
+# the "test model" section (:2094-2196): every testInterval iterations numTests tiles of the train and of the test split go
+# through the networks with `train: False` at the current blending percentage (Trainer8x.evaluate); genTestImg > -1
+# writes the sampler's image of the first frame with every report (:2263-2266)
+testInterval, numTests, genTestImg = int(P["testInterval"]), int(P["numTests"]), int(P["genTestImg"])
+
+
+noticed = False
+
+
+def test_split(tiles):
+    """does the stage's tile creator hold test frames?  The first one without says so, once per run"""
+    global noticed
+    have = tiles.setBorders[1] > tiles.setBorders[0]
+    if not have and not noticed:
+        noticed = True
+        print('no test frames in the data (%d frames): the test section is skipped' % tiles.setBorders[2])
+    return have
+
+
+have_test = test_split(tiCr)
+log, image_no = heldout.HeldOutLog(), 0
 t0 = time.time()
 print('\n*****TRAINING STARTED***** (stop with ctrl-c)\n')
 for it in range(startingIter, trainingIterations):
@@ -352,6 +372,7 @@ for it in range(startingIter, trainingIterations):
         start_interpol = it + stageIter
         interpolate_Perc = True
         tiCr = load_stage(currentUpres, False)
+        have_test = test_split(tiCr)
         print("--------------------------NEW UPRES: %d--------------------------" % currentUpres)
     if interpolate_Perc:
         interpol_c += 1
@@ -367,27 +388,38 @@ for it in range(startingIter, trainingIterations):
     index = int(round(math.log(currentUpres, 2)) - 1)               # the growing stage's optimisers (:1978)
     for _ in range(discRuns):
         bx, by = getinput()
-        avg_d += float(trainer.disc_step(bx, by, currBlendPer, stage=index)["disc_loss"].detach())
+        log.add_train("avgCost_disc", trainer.disc_step(bx, by, currBlendPer, stage=index)["disc_loss"].detach())
     tempo = None
     if useTempoD:
         for _ in range(discRuns):
             tempo = getTempoinput()
-            trainer.tempo_disc_step(tempo[0], tempo[1], tempo[2], currBlendPer, stage=index)
+            Lt = trainer.tempo_disc_step(tempo[0], tempo[1], tempo[2], currBlendPer, stage=index)
+            log.add_train("avgTemCost_disc", Lt["t_disc_loss"].detach())
     for _ in range(genRuns):
         bx, by = getinput()
         if useTempoD:
             tempo = getTempoinput()
         L = trainer.gen_step(bx, by, currBlendPer, tempo, stage=index)
-        avg_g += float(L["g_loss_d"].detach())
-        avg_l1 += float(L["l1_loss"].detach())
-    if (it + 1) % outputInterval == 0:
-        k = float(outputInterval)
-        print('\nIteration {:05d}/{}, Cost:'.format(it + 1, trainingIterations))
-        print('\tdisc: loss: train_loss={:.6f}'.format(avg_d / (k * discRuns)))
-        print('\tgen: loss: train={:.6f} L1={:.6f}'.format(avg_g / (k * genRuns), avg_l1 / (k * genRuns)))
-        print('\t blending percentage: %f' % currBlendPer)
+        log.add_train("avgCost_gen", L["g_loss_d"].detach())
+        log.add_train("avgL1Cost_gen", L["l1_loss"].detach())
+        if useTempoD:
+            log.add_train("avgTemCost_gen", L["g_loss_t"].detach())
+    test_now, print_now, image_now = heldout.schedule(it, testInterval, outputInterval, genTestImg, have_test)
+    if test_now:                                                     # draw order of :2099-2137
+        train_b, test_b = getinput(numTests, True, False), getinput(numTests, False, False)
+        tempo_b = tempo_test_b = None
+        if useTempoD:
+            tempo_b, tempo_test_b = getTempoinput(numTests, True, False), getTempoinput(numTests, False, False)
+        log.add_test(trainer.evaluate(train_b[0], train_b[1], test_b[0], test_b[1], tempo=tempo_b, tempo_test=tempo_test_b,
+                                      percentage=currBlendPer, stage=index))
+    if print_now:
+        print(log.report(it, trainingIterations, outputInterval, discRuns, genRuns, k=trainer.k, kt=kt, kt_l=kt_l,
+                         blend=currBlendPer))
         print('\t{} iterations took {:.2f} seconds.'.format(outputInterval, time.time() - t0))
-        avg_d = avg_g = avg_l1 = 0.0
+        if image_now:
+            trainer.sample_frame_image(tiCr, heldout.frame_index(fromSim, fromSim, frame_max), test_path + 'test_img/',
+                                       image_no, simSizeLow * upRes, percentage=currBlendPer)
+            image_no += 1
         t0 = time.time()
     if (it + 1) % saveInterval == 0:
         saveModel()

@@ -441,6 +441,26 @@ int mpg_pair_reduce(mpg_stream_t stream, const float* a, const float* b, size_t 
 int mpg_adam_step(mpg_stream_t stream, float* p, const float* grad, float* m, float* v, size_t n,
                   const float* lr_t, float beta1, float beta2, float eps);
 
+/* Held-out evaluation: the "test model" section of the training loops (multipassGAN-4x.py:1410-1500,
+ * multipassGAN-8x.py:2094-2196), which runs the networks with train: False and fetches means of the critic outputs.
+ *   mpg_logit_stats: out6 = means over the n logits of { l, sigmoid(l), sigmoid cross entropy against label 1, against
+ *     label 0 (tf.nn.sigmoid_cross_entropy_with_logits: max(l,0) - l z + log1p(exp(-|l|))), (l - 1)^2, l^2 }.  One block,
+ *     sums folded in a fixed order, no atomics, nothing cleared: the same input gives the same bits, and the call is safe
+ *     inside a captured hipGraph.  A critic output has one logit per tile; n is not limited.
+ *   mpg_bn_infer_act: tf.contrib.layers.batch_norm(is_training=False) + activation (GAN.py:108-119) on [n,h,w,c] with the
+ *     moving averages given: y = act((x - mean) * rsqrt(var + eps) * gamma + beta); nothing is updated.  y (fp32 NHWC)
+ *     and / or y_g8 (G8, MPG_G8_F16, mpg_g8_bytes(n,h,w,c), 16-byte aligned; equal to mpg_f32_to_g8 of y bit for bit).
+ *     Without y_g8 this launches the apply kernels of mpg_bn_train_fwd_ordered.
+ *   mpg_tiles_to_gray8: tiles [n_tiles,th,tw,c] -> n_tiles / (rows*cols) mosaics [rows*th, cols*tw] of channel `channel`
+ *     as 8-bit grey, uint8(clip(v,0,1) * 255) truncated (tilecreator_t.savePngsGrayscale, :1125-1157): one byte per
+ *     pixel leaves the device. */
+int mpg_logit_stats(mpg_stream_t stream, const float* logits, size_t n, float* out6);
+int mpg_bn_infer_act(mpg_stream_t stream, const float* x, int n, int h, int w, int c, const float* mean,
+                     const float* var, const float* gamma, const float* beta, float eps, int act, float leak,
+                     float* y, void* y_g8);
+int mpg_tiles_to_gray8(mpg_stream_t stream, const float* tiles, int n_tiles, int th, int tw, int c, int channel,
+                       int rows, int cols, unsigned char* out);
+
 #ifdef __cplusplus
 }
 #endif

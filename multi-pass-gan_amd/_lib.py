@@ -164,6 +164,10 @@ PROTOTYPES = {
     "mpg_pair_reduce": (_I, [_P, _P, _P, _Z, _I, _P]),
     "mpg_adam_step": (_I, [_P, _P, _P, _P, _P, _Z, _P, _F, _F, _F]),
     "mpg_adam_step_staged": (_I, [_P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _F]),
+    # held-out evaluation
+    "mpg_logit_stats": (_I, [_P, _P, _Z, _P]),
+    "mpg_bn_infer_act": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _I, _F, _P, _P]),
+    "mpg_tiles_to_gray8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

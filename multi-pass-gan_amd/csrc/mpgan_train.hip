@@ -1542,3 +1542,204 @@ extern "C" int mpg_minibatch_stddev_bwd2(mpg_stream_t stream, const float* x, co
                        c, g_x, g_dy);
     MPG_LAUNCH_CHECK("mbstd backward-of-backward kernels");
 }
+
+// ---------------------------------------------------------------- held-out evaluation (the "test model" section of the
+// training loops, multipassGAN-4x.py:1410-1500, multipassGAN-8x.py:2094-2196: the networks with train: False)
+namespace {
+
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+// The six means the test section forms from one critic output: logit, sigmoid, sigmoid cross entropy against label 1 and
+// label 0 in TensorFlow's stable form max(l, 0) - l z + log1p(exp(-|l|)), and the LSGAN squares.  A critic output has one
+// logit per tile, so ONE block covers it: every thread sums its strided share, the 256 sums are folded in a fixed tree.
+// No atomics and nothing to clear: the same input gives the same bits, inside a captured graph too.
+__global__ __launch_bounds__(256) void logit_stats_kernel(const float* __restrict__ l, size_t n, float inv_n,
+                                                          float* __restrict__ out) {
+    __shared__ float red[6][BLK];
+    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, comp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (size_t i = threadIdx.x; i < n; i += BLK) {
+        const float v = l[i];
+        const float e = expf(-fabsf(v));                     // in (0, 1]
+        const float soft = log1pf(e);
+        const float pos = fmaxf(v, 0.f);
+        const float t[6] = {v, (v >= 0.f ? 1.f : e) / (1.f + e),      // sigmoid(v) without overflow
+                            pos - v + soft,                            // label 1
+                            pos + soft,                                // label 0
+                            (v - 1.f) * (v - 1.f), v * v};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {                         // compensated: a long vector costs a thread hundreds of terms
+            const float yk = t[k] - comp[k];
+            const float sk = s[k] + yk;
+            comp[k] = (sk - s[k]) - yk;
+            s[k] = sk;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int st = BLK / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + st];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) out[threadIdx.x] = red[threadIdx.x][0] * inv_n;
+}
+
+// y = act((x - mean) * rsqrt(var + eps) * gamma + beta) with the G8 form of y written by the same thread from the same
+// registers (the next convolution reads it; no mpg_f32_to_g8 pass over y).  One thread per (pixel, group of 8 channels),
+// groups fastest: a pixel row is read as consecutive 32-byte pieces.  The per-channel vectors are staged in LDS as
+// bn_apply4_kernel does (c <= BN4_CMAX; wider tensors read them from memory).  VEC: c % 4 == 0 and 16-byte aligned x / y.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_infer_g8_kernel(const float* __restrict__ x, int n, size_t plane_px, int c,
+                                                          const float* __restrict__ mean, const float* __restrict__ var,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float eps, int act, float leak, float* __restrict__ y,
+                                                          _Float16* __restrict__ g8) {
+    __shared__ __attribute__((aligned(16))) float par[4][BN4_CMAX];
+    const bool staged = c <= BN4_CMAX;
+    if (staged) {
+        for (int i = threadIdx.x; i < c; i += BLK) {
+            par[0][i] = mean[i];
+            par[1][i] = rsqrtf(var[i] + eps);
+            par[2][i] = gamma[i];
+            par[3][i] = beta[i];
+        }
+        __syncthreads();
+    }
+    const int cg_n = (c + 7) >> 3;
+    const size_t total = (size_t)n * plane_px * cg_n;
+    for (size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x; idx < total; idx += (size_t)gridDim.x * BLK) {
+        const int cg = (int)(idx % cg_n);
+        const size_t pix = idx / cg_n;                         // b * plane_px + px
+        const size_t b = pix / plane_px, px = pix % plane_px;
+        const int ch0 = cg * 8;
+        const float* src = x + pix * c + ch0;
+        float v[8];
+        if (VEC) {
+            const float4 a = *reinterpret_cast<const float4*>(src);
+            const float4 z = ch0 + 4 < c ? *reinterpret_cast<const float4*>(src + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = z.x; v[5] = z.y; v[6] = z.z; v[7] = z.w;
+        }
+        else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = ch0 + j < c ? src[j] : 0.f;
+        }
+        float o[8];
+        half8_t hi, lo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int ch = ch0 + j;
+            float r = 0.f;
+            if (ch < c) {
+                const float m = staged ? par[0][ch] : mean[ch], is = staged ? par[1][ch] : rsqrtf(var[ch] + eps);
+                const float g = staged ? par[2][ch] : gamma[ch], bt = staged ? par[3][ch] : beta[ch];
+                r = mpg::apply_act((v[j] - m) * is * g + bt, act, leak);
+            }
+            o[j] = r;
+            hi[j] = (_Float16)r;
+            lo[j] = (_Float16)(r - (float)hi[j]);
+        }
+        if (y != nullptr) {
+            float* dst = y + pix * c + ch0;
+            if (VEC) {
+                *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                if (ch0 + 4 < c) *reinterpret_cast<float4*>(dst + 4) = make_float4(o[4], o[5], o[6], o[7]);
+            }
+            else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (ch0 + j < c) dst[j] = o[j];
+            }
+        }
+        _Float16* gd = g8 + (((b * cg_n + cg) * 2) * plane_px + px) * 8;
+        *reinterpret_cast<half8_t*>(gd) = hi;
+        *reinterpret_cast<half8_t*>(gd + plane_px * 8) = lo;
+    }
+}
+
+// [tiles, th, tw, c] fp32 tiles -> count = tiles / (rows * cols) mosaics of rows x cols tiles, channel `ch`, as 8-bit grey:
+// uint8(clip(v, 0, 1) * 255), truncated (savePngsGrayscale).  QUAD: tw % 4 == 0, a thread packs four pixels of one tile
+// row into one 32-bit store; otherwise one byte per thread.
+__device__ __forceinline__ unsigned gray8(float v) { return (unsigned)(fminf(fmaxf(v, 0.f), 1.f) * 255.f); }
+
+template <bool QUAD>
+__global__ void tiles_to_gray8_kernel(const float* __restrict__ tiles, size_t total, int th, int tw, int c, int ch, int rows,
+                                      int cols, unsigned char* __restrict__ out) {
+    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+    if (idx >= total) return;
+    const size_t o = QUAD ? idx * 4 : idx;                      // first output byte of this thread
+    const size_t W = (size_t)cols * tw, H = (size_t)rows * th;
+    const size_t X = o % W, Y = (o / W) % H, m = o / (W * H);
+    const size_t tile = (m * rows + Y / th) * cols + X / tw;
+    const float* src = tiles + (((tile * th + Y % th) * tw + X % tw) * c + ch);
+    if (QUAD) {
+        const unsigned p = gray8(src[0]) | (gray8(src[c]) << 8) | (gray8(src[2 * (size_t)c]) << 16) |
+                           (gray8(src[3 * (size_t)c]) << 24);
+        reinterpret_cast<unsigned*>(out)[idx] = p;
+    }
+    else
+        out[idx] = (unsigned char)gray8(src[0]);
+}
+
+}  // namespace
+
+extern "C" int mpg_logit_stats(mpg_stream_t stream, const float* logits, size_t n, float* out6) {
+    MPG_REQUIRE(logits && out6, "mpg_logit_stats: null pointer");
+    MPG_REQUIRE(n >= 1, "mpg_logit_stats: empty logit vector");
+    hipLaunchKernelGGL(logit_stats_kernel, dim3(1), dim3(BLK), 0, (hipStream_t)stream, logits, n, 1.f / (float)n, out6);
+    MPG_LAUNCH_CHECK("logit_stats_kernel");
+}
+
+extern "C" int mpg_bn_infer_act(mpg_stream_t stream, const float* x, int n, int h, int w, int c, const float* mean,
+                                const float* var, const float* gamma, const float* beta, float eps, int act, float leak,
+                                float* y, void* y_g8) {
+    MPG_REQUIRE(x && mean && var && gamma && beta && (y || y_g8), "mpg_bn_infer_act: null pointer");
+    MPG_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1, "mpg_bn_infer_act: bad shape");
+    MPG_REQUIRE(act >= MPG_ACT_NONE && act <= MPG_ACT_TANH, "mpg_bn_infer_act: bad activation %d", act);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t plane_px = (size_t)h * w, total = (size_t)n * plane_px * c;
+    const uintptr_t al = (uintptr_t)x | (uintptr_t)y;
+    const bool vec = (c % 4) == 0 && (al & 15) == 0;
+    if (y_g8 == nullptr) {
+        // the normalisation with given vectors is what the training forward applies after its statistics: the same kernels
+        if (vec && c <= BN4_CMAX) {
+            unsigned g = grid_for(total / 4);
+            if (g > 4096) g = 4096;
+            hipLaunchKernelGGL(bn_apply4_kernel, dim3(g), dim3(BLK), 0, s, x, total / 4, c, mean, var, gamma, beta, eps, act,
+                               leak, y);
+        }
+        else
+            hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(total)), dim3(BLK), 0, s, x, total, c, mean, var, gamma, beta,
+                               eps, act, leak, y);
+        MPG_LAUNCH_CHECK("mpg_bn_infer_act");
+    }
+    MPG_REQUIRE((((uintptr_t)y_g8) & 15) == 0, "mpg_bn_infer_act: y_g8 must be 16-byte aligned");
+    unsigned g = grid_for((size_t)n * plane_px * ((c + 7) / 8));
+    if (g > 4096) g = 4096;
+    if (vec)
+        hipLaunchKernelGGL((bn_infer_g8_kernel<true>), dim3(g), dim3(BLK), 0, s, x, n, plane_px, c, mean, var, gamma, beta, eps,
+                           act, leak, y, (_Float16*)y_g8);
+    else
+        hipLaunchKernelGGL((bn_infer_g8_kernel<false>), dim3(g), dim3(BLK), 0, s, x, n, plane_px, c, mean, var, gamma, beta, eps,
+                           act, leak, y, (_Float16*)y_g8);
+    MPG_LAUNCH_CHECK("bn_infer_g8_kernel");
+}
+
+extern "C" int mpg_tiles_to_gray8(mpg_stream_t stream, const float* tiles, int n_tiles, int th, int tw, int c, int channel,
+                                  int rows, int cols, unsigned char* out) {
+    MPG_REQUIRE(tiles && out, "mpg_tiles_to_gray8: null pointer");
+    MPG_REQUIRE(n_tiles >= 1 && th >= 1 && tw >= 1 && c >= 1 && rows >= 1 && cols >= 1, "mpg_tiles_to_gray8: bad shape");
+    MPG_REQUIRE(channel >= 0 && channel < c, "mpg_tiles_to_gray8: channel %d of %d", channel, c);
+    MPG_REQUIRE(n_tiles % (rows * cols) == 0, "mpg_tiles_to_gray8: %d tiles do not fill %d x %d mosaics", n_tiles, rows, cols);
+    const size_t bytes = (size_t)n_tiles * th * tw;
+    hipStream_t s = (hipStream_t)stream;
+    if ((tw % 4) == 0 && (((uintptr_t)out) & 3) == 0)
+        hipLaunchKernelGGL((tiles_to_gray8_kernel<true>), dim3(grid_for(bytes / 4)), dim3(BLK), 0, s, tiles, bytes / 4, th, tw, c,
+                           channel, rows, cols, out);
+    else
+        hipLaunchKernelGGL((tiles_to_gray8_kernel<false>), dim3(grid_for(bytes)), dim3(BLK), 0, s, tiles, bytes, th, tw, c,
+                           channel, rows, cols, out);
+    MPG_LAUNCH_CHECK("tiles_to_gray8_kernel");
+}

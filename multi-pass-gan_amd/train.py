@@ -9,7 +9,9 @@ views (reshape / concat / slice), the scalar loss reductions and device memory, 
 the losses and optimiser bookkeeping host/PyTorch side; the Adam update itself is ``mpg_adam_step``
 with TensorFlow's epsilon placement.
 """
+import contextlib
 import math
+import os
 
 import numpy as np
 
@@ -69,6 +71,11 @@ def _cached_g8(t, prec, scaled):
         except AttributeError:      # a tensor type that takes no attributes: convert every time
             pass
     return tag[0], tag[1]
+
+
+def _attach_g8(t, g8):
+    """hand _cached_g8 the unscaled G8 form of t that the kernel producing t wrote alongside (mpg_bn_infer_act)"""
+    t._mpg_g8 = {False: (g8, None, t._version, t.data_ptr(), tuple(t.shape))}
 
 
 def _dgrad_weights(w):
@@ -579,6 +586,9 @@ class TrainSession(object):
         self.params = {}
         self._scalar_feeds = {}
         self._noise_gen = {}     # random_normal node id -> its generator
+        # True inside evaluation(): the reference's `train: False` feed (batch norm on its moving averages, nothing updated)
+        self.eval_mode = False
+        self._consumers = {}
 
     def parameters(self):
         """name -> leaf tensor for every variable of the graph (trainable ones require grad)"""
@@ -600,6 +610,17 @@ class TrainSession(object):
             self.vars.values[name] = p.detach().clone()
         self.vars.version += 1
 
+    @contextlib.contextmanager
+    def evaluation(self):
+        """the reference's `train: False` (multipassGAN-4x.py:1417, -8x.py:2100): inside, run() normalises with the moving
+        averages and leaves them alone, records no tape and keeps nothing for a backward pass"""
+        prev, self.eval_mode = self.eval_mode, True
+        try:
+            with torch.no_grad():
+                yield self
+        finally:
+            self.eval_mode = prev
+
     # ------------------------------------------------------------------ evaluation
     def run(self, fetches, feeds):
         _lib.load()
@@ -614,6 +635,7 @@ class TrainSession(object):
             else:
                 env[node.id] = torch.as_tensor(t, dtype=torch.float32, device=self.device)
         users = self._count_users(fetches)
+        self._consumers = self._consumer_map(fetches) if self.eval_mode else {}
         # the UPDATE_OPS of tf.contrib.layers.batch_norm (multipassGAN-4x.py:773-776,889-899) run inside
         # mpg_bn_train_fwd_ordered: every evaluated batch-norm layer advances its moving averages once
         return [self._eval(f, env, users) for f in fetches]
@@ -631,6 +653,31 @@ class TrainSession(object):
                 users[i.id] = users.get(i.id, 0) + 1
                 stack.append(i)
         return users
+
+    def _consumer_map(self, fetches):
+        """node id -> the nodes that read it (a fetched node also lists None): evaluation asks whether a layer's only reader
+        is a convolution that takes the G8 form"""
+        cons, seen, stack = {}, set(), list(fetches)
+        for f in fetches:
+            cons.setdefault(f.id, []).append(None)
+        while stack:
+            n = stack.pop()
+            if n.id in seen:
+                continue
+            seen.add(n.id)
+            for i in n.inputs:
+                cons.setdefault(i.id, []).append(n)
+                stack.append(i)
+        return cons
+
+    def _feeds_one_mfma_conv(self, n):
+        """is the only reader of node n a stride-1 convolution of the matrix-core kernel reading it as its input?"""
+        readers = self._consumers.get(n.id, [])
+        if len(readers) != 1 or readers[0] is None or readers[0].op != "conv2d" or readers[0].inputs[0] is not n:
+            return False
+        r = readers[0]
+        kh, kw, _, cout = self.graph.variables[r.inputs[1].attrs["var"]].shape
+        return _mfma_ok(kh, kw, cout, tuple(r.attrs["stride"]))
 
     def _higher(self, n):
         """does this node sit in a variable scope that needs differentiable backward passes?"""
@@ -654,7 +701,7 @@ class TrainSession(object):
             # a layer [act](batch_norm?(bias_add?(conv2d|matmul))) whose inner nodes feed nothing else is one function
             chain = G.match_layer(n, lambda m: users.get(m.id, 0) == 1, ("conv2d", "matmul"))
             if chain is not None:
-                return self._conv_layer(chain, ev)
+                return self._conv_layer(chain, ev, n)
             if op == "act":
                 x = n.inputs[0]
                 if x.op == "add" and users.get(x.id, 0) == 1:
@@ -688,6 +735,8 @@ class TrainSession(object):
         if op == "max_pool":
             if self._higher(n):
                 raise NotImplementedError("second-order gradient through max_pool (no reference network uses it)")
+            if self.eval_mode:                          # no argmax plane: nothing runs backward
+                return ops.max_pool(ev(n.inputs[0]).contiguous(), n.attrs["k"], n.attrs["s"])
             return MaxPoolFn.apply(ev(n.inputs[0]), n.attrs["k"], n.attrs["s"])
         if op == "advect":
             src, vel = ev(n.inputs[0]), ev(n.inputs[1])
@@ -707,7 +756,34 @@ class TrainSession(object):
             return ops.resize_images(x.contiguous(), n.attrs["oh"], n.attrs["ow"], n.attrs["method"])
         raise G.GraphError("training: no lowering for %r" % (n,))
 
-    def _conv_layer(self, chain, ev):
+    def _conv_layer_eval(self, x, w4, b, bn, cfg, is_fc, top):
+        """the layer with `train: False`: one forward launch, batch norm through mpg_bn_infer_act on the moving averages
+        (read, never written); no G8 operand kept for a weight gradient, no batch statistics, nothing saved"""
+        kh, kw, cin, cout = w4.shape
+        act, leak, wscale = cfg["act"], cfg["leak"], cfg["wscale"]
+        # x is kept as the object it is: the G8 form a batch-norm layer wrote travels on it (_cached_g8)
+        x, w = x.contiguous(), w4.detach().contiguous()
+        bd = b.detach() if b is not None else None
+        conv_act = None if bn is not None else act
+        if is_fc:
+            lin = train_ops.fc_forward(x.reshape(x.shape[0], cin), w.reshape(cin, cout), wscale, bd, conv_act,
+                                       leak).reshape(x.shape[0], 1, 1, cout)
+        elif _mfma_ok(kh, kw, cout, cfg["stride"]):
+            lin = _mfma_conv(x, w, wscale, cfg["prec"], bd, conv_act, leak)
+        else:
+            lin = ops.conv2d_direct(x, w, cfg["stride"], wscale, None, bd, conv_act, leak)
+        y = lin
+        if bn is not None:
+            gamma, beta, mm, mv = (self.params[bn.inputs[i].attrs["var"]] for i in (1, 2, 3, 4))
+            if not is_fc and self._feeds_one_mfma_conv(top):
+                # the reader finds the G8 form on the tensor (_cached_g8) instead of converting y
+                y, g8 = train_ops.bn_infer_act(lin, mm, mv, gamma, beta, bn.attrs["eps"], act, leak, want_g8=True)
+                _attach_g8(y, g8)
+            else:
+                y = train_ops.bn_infer_act(lin, mm, mv, gamma, beta, bn.attrs["eps"], act, leak)
+        return y.reshape(y.shape[0], -1) if is_fc else y
+
+    def _conv_layer(self, chain, ev, chain_top=None):
         conv, bias, bn, act, leak = chain
         x = ev(conv.inputs[0])
         w = self.params[conv.inputs[1].attrs["var"]]
@@ -725,6 +801,8 @@ class TrainSession(object):
                 x, w4, stride = space_to_depth2(x), strided4_as_3x3(w), (1, 1)
         cfg = {"stride": stride, "wscale": conv.attrs["wscale"], "act": act, "leak": leak, "prec": self.prec, "fc": is_fc,
                "eps": bn.attrs["eps"] if bn is not None else 0.0}
+        if self.eval_mode:
+            return self._conv_layer_eval(x, w4, b, bn, cfg, is_fc, chain_top)
         wname = conv.inputs[1].attrs["var"]
         if any(wname.startswith(p) for p in self.higher_order_scopes):
             y = ConvFn.apply(x, w4, b, cfg)
@@ -967,7 +1045,79 @@ class _SlotStateMixin(object):
         return sum(o.load_slot_state(state, tag) for tag, o in self.optimisers())
 
 
-class Trainer4x(_SlotStateMixin):
+class _HeldOutMixin(object):
+    """The "test model" section of the training loops (multipassGAN-4x.py:1410-1500, -8x.py:2094-2196) and the test image
+    (generateTestImage, 4x.py:1050-1087, 8x.py:1539-1597) for both trainers: forward passes with `train: False`
+    (TrainSession.evaluation), the means of the critic outputs from mpg_logit_stats.  A trainer supplies
+    `_eval_spatial`, `_eval_tempo`, `_adv_stat` and `_sample`."""
+
+    def evaluate(self, x, y, x_test, y_test, tempo=None, tempo_test=None, percentage=None, stage=None):
+        """-> dict of device scalars, the quantities the reference's test section fetches:
+          out_disc_train / out_gen_train   mean sigmoid(D(y)) / sigmoid(D(G(x))) on the train-split batch (x, y)
+          out_disc_test / out_gen_test, d_loss_y, d_loss_g, g_loss_d   the same means and the losses on (x_test, y_test)
+          t_out_disc_train .. t_loss_g, g_loss_t [, tl_gen_loss]   on the advected triples tempo / tempo_test =
+                                            (x_t, y_t, y_pos) of a trainer with a temporal critic (tl: lambda_t_l2)
+        with the losses of the configured trainer (sigmoid-CE, LSGAN or WGAN; the gradient penalty is not fetched).
+        Batch norm runs on its moving averages; no parameter, moving average, optimiser slot or counter is written and
+        nothing is kept for a backward pass.  `percentage` (8x) is the fed blending value; `stage` (8x) is the growing
+        stage train_step runs at: no optimiser takes part here, so it is only checked to be one of the trainer's stages."""
+        self._check_stage(percentage, stage)
+        out = {}
+        with self.sess.evaluation():
+            sd, sg = self._eval_spatial(x, y, percentage)
+            out["out_disc_train"], out["out_gen_train"] = sd[1], sg[1]
+            sd, sg = self._eval_spatial(x_test, y_test, percentage)
+            out["out_disc_test"], out["out_gen_test"] = sd[1], sg[1]
+            out["d_loss_y"], out["d_loss_g"] = self._adv_stat(sd, True), self._adv_stat(sg, False)
+            out["g_loss_d"] = self._adv_stat(sg, True)
+            if tempo is not None and self.use_tempo:
+                sd, sg, _ = self._eval_tempo(tempo, percentage)
+                out["t_out_disc_train"], out["t_out_gen_train"] = sd[1], sg[1]
+            if tempo_test is not None and (self.use_tempo or getattr(self, "use_tempo_l2", False)):
+                sd, sg, tl = self._eval_tempo(tempo_test, percentage)
+                if self.use_tempo:
+                    out["t_out_disc_test"], out["t_out_gen_test"] = sd[1], sg[1]
+                    out["t_loss_y"], out["t_loss_g"] = self._adv_stat(sd, True), self._adv_stat(sg, False)
+                    out["g_loss_t"] = self._adv_stat(sg, True)
+                if tl is not None:
+                    out["tl_gen_loss"] = tl
+        return out
+
+    def _check_stage(self, percentage, stage):
+        if stage is None:
+            return
+        levels = getattr(self, "currentUpres", None)
+        if levels is None:
+            raise _lib.MpgError("evaluate: this trainer has no growing stages (stage %r)" % (stage,))
+        if not 0 <= int(stage) < levels:
+            raise _lib.MpgError("evaluate: growing stage %d of %d" % (stage, levels))
+
+    def sample_frame_image(self, tiCr, index, out_dir, image_no=0, sim_size_high=None, percentage=None):
+        """generateTestImage: the tiles of frame `index` (tiCr.getFrameTiles; index = (sim_no - fromSim) * frame_max +
+        frame_no) through the sampler one tile at a time with `train: False`, the generator outputs assembled into the
+        (sim_size_high / tileSizeHigh)^2 mosaic on the device (mpg_tiles_to_gray8) and written as
+        out_dir/img_%04d.png.  Returns the path."""
+        from . import heldout
+        low, high = tiCr.getFrameTiles(index)
+        th = self.tileSizeHigh
+        side = (sim_size_high // th) if sim_size_high else int(round(math.sqrt(len(low))))
+        if side * side != len(low):
+            raise _lib.MpgError("sample_frame_image: %d tiles do not fill a %d x %d mosaic" % (len(low), side, side))
+        dev = self.sess.device
+        lows = torch.as_tensor(np.ascontiguousarray(low, dtype=np.float32)).to(dev).reshape(len(low), -1)
+        highs = torch.as_tensor(np.ascontiguousarray(high, dtype=np.float32)).to(dev).reshape(len(high), -1)
+        tiles = []
+        with self.sess.evaluation():
+            for t in range(lows.shape[0]):
+                tiles.append(self._sample(lows[t:t + 1], highs[t:t + 1], percentage).reshape(1, th, th, 1))
+        grey = train_ops.tiles_to_gray8(torch.cat(tiles, dim=0), side, side)[0]
+        os.makedirs(out_dir, exist_ok=True)
+        path = os.path.join(out_dir, "img_%04d.png" % image_no)
+        heldout.write_gray_png(path, grey.cpu().numpy())
+        return path
+
+
+class Trainer4x(_SlotStateMixin, _HeldOutMixin):
     """The GAN training iteration of multipassGAN-4x.py (graph :728-768,880-902, loop :1317-1356):
     ``discRuns`` discriminator updates then ``genRuns`` generator updates on tile batches, spatial
     discriminator with feature losses, sigmoid cross entropy + lambda * L1 (+ lambda2 * layer loss)."""
@@ -1062,27 +1212,36 @@ class Trainer4x(_SlotStateMixin):
             v = ResampleFn.apply(v, pos, self.clamping)
         return v.reshape(-1, self.n_t, self.n_output).permute(0, 2, 1).reshape(-1, self.n_output * self.n_t)
 
-    def tempo_losses(self, batch_xts, batch_yts, batch_y_pos=None):
-        """-> t_disc_loss, t_gen_loss (:834-866) for a coherent batch from TileCreator.selectRandomTempoTiles"""
+    def _tempo_forward(self, batch_xts, batch_yts, batch_y_pos=None):
+        """the forward passes tempo_losses and evaluate share -> (tl_gen_loss or None, D_t(fake) logits, D_t(real) logits;
+        both None without a temporal critic)"""
         dev = self.sess.device
-        xts = torch.as_tensor(batch_xts, dtype=torch.float32, device=dev)
-        yts = torch.as_tensor(batch_yts, dtype=torch.float32, device=dev)
+        xts = torch.as_tensor(batch_xts, dtype=torch.float32, device=dev).reshape(-1, self.n_input)
+        yts = torch.as_tensor(batch_yts, dtype=torch.float32, device=dev).reshape(-1, self.n_output)
         gen_part_t = self.sess.run([self.gen_part_t], {self.x_t: xts})[0]
         fake = self._frames_as_channels(gen_part_t, batch_y_pos)
-        L = {}
+        tl = None
         if self.use_tempo_l2:
             # tl_gen_loss = sum_i mean((frame_i - frame_i+1)^2) over the n_t advected generator frames (:821-826)
             f = fake.reshape(-1, self.n_output, self.n_t)
             fr = [f[:, :, i].contiguous() for i in range(self.n_t)]
-            tl = None
             for i in range(self.n_t - 1):
                 term = PairLossFn.apply(fr[i], fr[i + 1], 1) / float(fr[i].numel())
                 tl = term if tl is None else tl + term
+        if not self.use_tempo:
+            return tl, None, None
+        real = self._frames_as_channels(yts, batch_y_pos)
+        gen_t, disc_t = self.sess.run([self.gen_t, self.disc_t], {self.t_fake: fake, self.t_real: real})
+        return tl, gen_t, disc_t
+
+    def tempo_losses(self, batch_xts, batch_yts, batch_y_pos=None):
+        """-> t_disc_loss, t_gen_loss (:834-866) for a coherent batch from TileCreator.selectRandomTempoTiles"""
+        tl, gen_t, disc_t = self._tempo_forward(batch_xts, batch_yts, batch_y_pos)
+        L = {}
+        if tl is not None:
             L["tl_gen_loss"] = tl
         if not self.use_tempo:
             return L
-        real = self._frames_as_channels(yts, batch_y_pos)
-        gen_t, disc_t = self.sess.run([self.gen_t, self.disc_t], {self.t_fake: fake, self.t_real: real})
         L["t_disc_loss_disc"] = sigmoid_ce(disc_t, torch.ones_like(disc_t))
         L["t_disc_loss_gen"] = sigmoid_ce(gen_t, torch.zeros_like(gen_t))
         L["t_disc_loss"] = L["t_disc_loss_disc"] * self.weight_dld + L["t_disc_loss_gen"]
@@ -1107,6 +1266,28 @@ class Trainer4x(_SlotStateMixin):
         grads = torch.autograd.grad(L["gen_loss_complete"], self.opt_g.params, allow_unused=True)
         self.opt_g.step(grads, advance=advance)
         return L
+
+    # ------------------------------------------------------------------ held-out evaluation (_HeldOutMixin)
+    def _adv_stat(self, st, real):
+        """sigmoid cross entropy against label 1 / 0 out of the mpg_logit_stats vector (:744-768)"""
+        return st[2] if real else st[3]
+
+    def _eval_spatial(self, bx, by, percentage=None):
+        dev = self.sess.device
+        bx = torch.as_tensor(bx, dtype=torch.float32, device=dev).reshape(-1, self.n_input)
+        by = torch.as_tensor(by, dtype=torch.float32, device=dev).reshape(-1, self.n_output)
+        disc, gen = self.sess.run([self.disc[0], self.gen[0]], {self.x: bx, self.x_disc: bx, self.y: by})
+        return train_ops.logit_stats(disc), train_ops.logit_stats(gen)
+
+    def _eval_tempo(self, tempo, percentage=None):
+        """-> (stats of D_t(real), stats of D_t(fake), tl_gen_loss or None) for a coherent batch"""
+        tl, gen_t, disc_t = self._tempo_forward(*tempo)
+        if not self.use_tempo:
+            return None, None, tl
+        return train_ops.logit_stats(disc_t), train_ops.logit_stats(gen_t), tl
+
+    def _sample(self, low, high, percentage=None):
+        return self.sess.run([self.gen_part], {self.x: low})[0]
 
     def disc_step(self, batch_xs, batch_ys, advance=True):
         L = self.losses(batch_xs, batch_ys)
@@ -1168,7 +1349,7 @@ class Trainer4x(_SlotStateMixin):
         return Ld["disc_loss"].detach(), Lg["gen_loss_complete"].detach()
 
 
-class Trainer8x(_SlotStateMixin):
+class Trainer8x(_SlotStateMixin, _HeldOutMixin):
     """One stage of the progressive-growing training of multipassGAN-8x.py (graph :1023-1144, optimisers
     :1305-1362): WGAN-GP (lambda 10, target 1, epsilon penalty 1e-3) or LSGAN or sigmoid-CE losses, L1 and
     layer losses for the generator, Adam(beta1, beta2) per network, and the 0.999 moving average of the
@@ -1344,22 +1525,31 @@ class Trainer8x(_SlotStateMixin):
             v = self._to_full_res(frames).reshape(-1, th, th, 1)
         return v.reshape(-1, self.n_t, self.cfg.n_output).permute(0, 2, 1).reshape(-1, self.cfg.n_output * self.n_t)
 
-    def tempo_losses(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, lerp_factor=None, need_gp=True):
-        """t_disc_loss / g_loss_t of multipassGAN-8x.py:1216-1300 for [3B, .] coherent frame rows (final stage)"""
+    def _tempo_forward(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0):
+        """the forward passes tempo_losses and evaluate share, for [3B, .] coherent frame rows
+        -> (fake, real frames as channels, T(fake) logits, T(real) logits)"""
         dev = self.sess.device
-        xts = torch.as_tensor(batch_xts, dtype=torch.float32, device=dev)
-        yts = torch.as_tensor(batch_yts, dtype=torch.float32, device=dev)
+        xts = torch.as_tensor(batch_xts, dtype=torch.float32, device=dev).reshape(-1, self.cfg.n_input)
+        yts = torch.as_tensor(batch_yts, dtype=torch.float32, device=dev).reshape(xts.shape[0], -1)
+        if batch_y_pos is not None and self.adv_flag and not self.adv_mode:
+            batch_y_pos = torch.as_tensor(batch_y_pos, dtype=torch.float32, device=dev).reshape(xts.shape[0], -1)
         if self.y_t2 is None:
             gen_ts = self.sess.run([self.gen_ts], {self.x_t: xts, self.percentage: percentage})[0]
         else:       # rows of (target, previous pass) pairs: the real frames are channel 0 (:1218-1219)
             gen_ts = self.sess.run([self.gen_ts], {self.x_t: xts, self.y_t2: yts, self.percentage: percentage})[0]
             yts = yts.reshape(-1, self.cfg.n_output, 2)[:, :, 0].contiguous()
         # resolution of the current growing stage = that of the fed targets (tileSizeLow * 2^ceil(percentage), :1180-1181)
-        cur_size = int(round(math.sqrt(yts.reshape(yts.shape[0], -1).shape[1]))) if self.cfg.upsampling_mode == 2 else self.cfg.tileSizeHigh
+        cur_size = int(round(math.sqrt(yts.shape[1]))) if self.cfg.upsampling_mode == 2 else self.cfg.tileSizeHigh
         fake = self._frames_as_channels(gen_ts, batch_y_pos, xts, cur_size)
         real = self._frames_as_channels(yts, batch_y_pos, xts, cur_size)
         gen_s, disc_s = self.sess.run([self.gen_s, self.disc_s], {self.t_fake: fake, self.t_real: real,
                                                                    self.percentage: percentage})
+        return fake, real, gen_s, disc_s
+
+    def tempo_losses(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, lerp_factor=None, need_gp=True):
+        """t_disc_loss / g_loss_t of multipassGAN-8x.py:1216-1300 for [3B, .] coherent frame rows (final stage)"""
+        dev = self.sess.device
+        fake, real, gen_s, disc_s = self._tempo_forward(batch_xts, batch_yts, batch_y_pos, percentage)
         L = {"t_loss_y": self._adv(disc_s, True), "t_loss_g": self._adv(gen_s, False)}
         t_disc_loss = L["t_loss_y"] * self.weight_dld + L["t_loss_g"]
         if self.use_wgan_gp and need_gp:
@@ -1383,6 +1573,45 @@ class Trainer8x(_SlotStateMixin):
     def ema(self):
         """moving averages of the generator variables as the last stage's optimiser keeps them (the model_ema checkpoint)"""
         return list(self.opt_g.ema_params().values())
+
+    # ------------------------------------------------------------------ held-out evaluation (_HeldOutMixin)
+    @property
+    def tileSizeHigh(self):
+        return self.cfg.tileSizeHigh
+
+    def _adv_stat(self, st, real):
+        """_adv out of the mpg_logit_stats vector: LSGAN 0.5 (l - target)^2, WGAN -l / +l, else sigmoid cross entropy"""
+        if self.use_LSGAN:
+            return 0.5 * (st[4] if real else st[5])
+        if self.use_wgan_gp:
+            return -st[0] if real else st[0]
+        return st[2] if real else st[3]
+
+    def _eval_spatial(self, bx, by, percentage=None):
+        dev = self.sess.device
+        percentage = float(self.currentUpres) if percentage is None else percentage
+        xs = torch.as_tensor(bx, dtype=torch.float32, device=dev).reshape(-1, self.cfg.n_input)
+        ys = torch.as_tensor(by, dtype=torch.float32, device=dev).reshape(xs.shape[0], -1)
+        if self.y2 is None:
+            feeds = {self.x: xs, self.x_disc: xs, self.y_in: self._to_full_res(ys), self.percentage: percentage}
+        else:
+            feeds = {self.x: xs, self.x_disc: xs, self.y2: ys, self.percentage: percentage}
+        disc, gen = self.sess.run([self.disc, self.gen], feeds)
+        return train_ops.logit_stats(disc), train_ops.logit_stats(gen)
+
+    def _eval_tempo(self, tempo, percentage=None):
+        """-> (stats of T(real), stats of T(fake), None) for [3B, .] coherent rows"""
+        percentage = float(self.currentUpres) if percentage is None else percentage
+        _, _, gen_s, disc_s = self._tempo_forward(tempo[0], tempo[1], tempo[2] if len(tempo) > 2 else None, percentage)
+        return train_ops.logit_stats(disc_s), train_ops.logit_stats(gen_s), None
+
+    def _sample(self, low, high, percentage=None):
+        """the sampler on one tile; the later networks read the previous pass from channel 1 of `high` (later_network_input)"""
+        percentage = float(self.currentUpres) if percentage is None else percentage
+        feeds = {self.x: low, self.percentage: percentage}
+        if self.y2 is not None:
+            feeds[self.y2] = high
+        return self.sess.run([self.gen_y], feeds)[0]
 
     def _update(self, opt, loss, stage):
         """calc_gradients + apply_updates (:510-541): d(loss * 2^ls_var) for ALL of the network's variables; the stage's

@@ -403,3 +403,55 @@ def adam_step(p, grad, m, v, lr_t, beta1, beta2, eps=1e-8):
             raise _lib.MpgError("adam_step: %s must be contiguous" % nm)
     _lib.check(lib.mpg_adam_step(_stream(), _ptr(p), _ptr(grad), _ptr(m), _ptr(v), p.numel(), _ptr(lr_t), float(beta1),
                                  float(beta2), float(eps)), "mpg_adam_step")
+
+
+# ------------------------------------------------------------------ held-out evaluation (train: False)
+LOGIT_STATS = ("mean", "sigmoid", "ce_one", "ce_zero", "ls_one", "ls_zero")
+
+
+def logit_stats(logits):
+    """[6] device tensor of means over a critic's logits: logit, sigmoid, sigmoid-CE against label 1 / label 0,
+    (l - 1)^2, l^2 (mpg_logit_stats; fixed summation order, the same bits for the same input)"""
+    lib = _lib.load()
+    l = _cont(logits.detach().reshape(-1), "logits")
+    out = torch.empty((6,), dtype=torch.float32, device=l.device)
+    _lib.check(lib.mpg_logit_stats(_stream(), _ptr(l), l.numel(), _ptr(out)), "mpg_logit_stats")
+    return out
+
+
+def bn_infer_act(x, mean, var, gamma, beta, eps=1e-3, act=None, leak=0.2, want_f32=True, want_g8=False):
+    """batch_norm(is_training=False) + activation with the given moving averages on NHWC x -> y, (y, G8 of y) with want_g8
+    (mpg_bn_infer_act); nothing is updated"""
+    from .ops import G8
+    lib = _lib.load()
+    x = _cont(x, "x")
+    if x.dim() != 4:
+        raise _lib.MpgError("bn_infer_act: expected NHWC, got %s" % (tuple(x.shape),))
+    n, h, w, c = x.shape
+    vecs = [_cont(v.detach(), nm) for v, nm in ((mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"))]
+    if any(v.numel() != c for v in vecs):
+        raise _lib.MpgError("bn_infer_act: per-channel vectors must have %d entries" % c)
+    if not (want_f32 or want_g8):
+        raise _lib.MpgError("bn_infer_act: no output asked for")
+    y = torch.empty_like(x) if want_f32 else None
+    g = G8.empty(n, h, w, c, x.device) if want_g8 else None
+    _lib.check(lib.mpg_bn_infer_act(_stream(), _ptr(x), n, h, w, c, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]),
+                                    _ptr(vecs[3]), float(eps), _lib.act_id(act), leak, _ptr(y),
+                                    _ptr(g.buf) if g is not None else None), "mpg_bn_infer_act")
+    return (y, g) if want_g8 else y
+
+
+def tiles_to_gray8(tiles, rows, cols, channel=0):
+    """[tiles, th, tw, c] device tiles -> uint8 device mosaics [tiles / (rows*cols), rows*th, cols*tw] of one channel,
+    uint8(clip(v, 0, 1) * 255) as tilecreator_t.savePngsGrayscale (mpg_tiles_to_gray8)"""
+    lib = _lib.load()
+    t = _cont(tiles, "tiles")
+    if t.dim() != 4:
+        raise _lib.MpgError("tiles_to_gray8: expected [tiles, th, tw, c], got %s" % (tuple(t.shape),))
+    nt, th, tw, c = t.shape
+    if nt == 0 or nt % (rows * cols):
+        raise _lib.MpgError("tiles_to_gray8: %d tiles do not fill %d x %d mosaics" % (nt, rows, cols))
+    out = torch.empty((nt // (rows * cols), rows * th, cols * tw), dtype=torch.uint8, device=t.device)
+    _lib.check(lib.mpg_tiles_to_gray8(_stream(), _ptr(t), nt, th, tw, c, int(channel), rows, cols, _ptr(out)),
+               "mpg_tiles_to_gray8")
+    return out
