@@ -1,7 +1,8 @@
-// Error state and device probe of libmpgan_hip.so.
+// Error state, device probe and the zeroing helpers of libmpgan_hip.so.
 #include "mpgan_internal.h"
 
 #include <cstring>
+#include <mutex>
 
 namespace mpg {
 
@@ -50,4 +51,28 @@ hipError_t mpg::zero_async(void* ptr, size_t bytes, hipStream_t stream) {
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (unsigned int*)ptr, n);
     return hipGetLastError();
+}
+
+// Allocated on the first call on a device under a lock; the fill is a blocking hipMemset followed by a device
+// synchronise, so the page is zero before ANY stream (torch's side streams are non-blocking) can run a kernel that reads
+// it.  Later calls are a lock-free read.  Must first happen outside a stream capture (Session / Trainer run one eager step
+// before capturing).
+const char* mpg::zero_page() {
+    static std::mutex mu;
+    static char* per_dev[64] = {nullptr};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    char* p = __atomic_load_n(&per_dev[dev], __ATOMIC_ACQUIRE);
+    if (p) return p;
+    std::lock_guard<std::mutex> lock(mu);
+    p = per_dev[dev];
+    if (!p) {
+        if (hipMalloc(&p, 256) != hipSuccess) return nullptr;
+        if (hipMemset(p, 0, 256) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(p);
+            return nullptr;
+        }
+        __atomic_store_n(&per_dev[dev], p, __ATOMIC_RELEASE);
+    }
+    return p;
 }

@@ -23,11 +23,12 @@
 //     keeps hi*hi only;
 //   * partial sums of the pixel ranges are combined with fp32 atomics into dW.
 #include "mpgan_internal.h"
+#include "mpgan_mfma_dev.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace mpg::dev;
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BLK = 256;
@@ -124,20 +125,10 @@ __device__ __forceinline__ void lds_read_tr(u32x2& dst, unsigned addr) {
     static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds_read_b64_tr_b16 offset");
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-// wait until at most N of the LDS reads issued so far are outstanding (they return in order)
+// lgkm_wait<N>, unless the timing experiment MPG_WG_EXP & 1 drops the LDS waits
 template <int N>
-__device__ __forceinline__ void lgkm_wait() {
-#if !(MPG_WG_EXP & 1)
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N < 15 ? N : 15) : "memory");
-#endif
-}
-// no instruction: makes every later use of `frag` depend on the preceding (volatile) wait
-template <class T>
-__device__ __forceinline__ void tie(T& frag) {
-    asm volatile("" : "+v"(frag));
+__device__ __forceinline__ void wg_wait() {
+    if constexpr (!(MPG_WG_EXP & 1)) lgkm_wait<N>();
 }
 
 __device__ __forceinline__ void tr_read_at(u32x2& dst, unsigned addr, int m) {      // m is a constant after unrolling
@@ -148,14 +139,6 @@ __device__ __forceinline__ void tr_read_at(u32x2& dst, unsigned addr, int m) {  
         case 3: lds_read_tr<192>(dst, addr); break;
         case 4: lds_read_tr<256>(dst, addr); break;
         default: lds_read_tr<320>(dst, addr); break;
-    }
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_wg(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_wg<I + 1, N>(f);
     }
 }
 
@@ -289,7 +272,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
     };
 
     auto dma_parts = [&](int buf, int first, int end) {      // parts first .. end-1 (wave-uniform bounds)
-        static_for_wg<0, NPART>([&](auto pc) {
+        static_for<0, NPART>([&](auto pc) {
             constexpr int P = decltype(pc)::value;
             if (first <= P && P < end) dma_part(buf, pc);
         });
@@ -392,7 +375,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
             dma_slot();
             const int jn = j + a.ks < ksteps ? j + a.ks : j;
             half8 ah[KW], bh[COTW];
-            lgkm_wait<(PREC == 3 ? NB + 6 : 0)>();
+            wg_wait<(PREC == 3 ? NB + 6 : 0)>();
 #pragma unroll
             for (int m = 0; m < 6; ++m) tie(wc[m]);
 #pragma unroll
@@ -408,7 +391,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
             if (PREC == 3) {
                 half8 bl[COTW], al[KW];
                 dma_slot();
-                lgkm_wait<6>();
+                wg_wait<6>();
 #pragma unroll
                 for (int t = 0; t < COTW; ++t) { tie(b1[t][0]); tie(b1[t][1]); bl[t] = frag_of(b1[t]); }
 #pragma unroll
@@ -419,7 +402,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
                 read_hi(wn, bn, jn);
                 dma_slot();
-                lgkm_wait<6 + NB>();
+                wg_wait<6 + NB>();
 #pragma unroll
                 for (int m = 0; m < 6; ++m) tie(w1[m]);
                 shifted(w1, al);
@@ -443,7 +426,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
             kstep(w0, b0, w0b, b0b, j);
             if (t + 1 < my_steps) kstep(w0b, b0b, w0, b0, j + a.ks);
         }
-        if (my_steps > 0) lgkm_wait<0>();      // the look-ahead reads of the last k-step
+        if (my_steps > 0) wg_wait<0>();      // the look-ahead reads of the last k-step
         if (has_next) dma_parts(buf ^ 1, next_part, NPART);     // waves without k-steps, or whatever is left
 #if MPG_WG_DIAG
         const unsigned long long t2a = WG_T();
@@ -701,7 +684,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
         for (int j = 0; j < ksteps; ++j) {
             const int jn = j + 1 < ksteps ? j + 1 : j;
             // in flight, oldest first: wh, bh [, bl, wl]
-            lgkm_wait<(PREC == 3 ? NB + NW : 0)>();
+            wg_wait<(PREC == 3 ? NB + NW : 0)>();
 #pragma unroll
             for (int k = 0; k < NKY; ++k)
 #pragma unroll
@@ -710,27 +693,27 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
 #pragma unroll
             for (int c = 0; c < COTW; ++c) { tie(bhq[c][0]); tie(bhq[c][1]); bh[c] = frag_of(bhq[c]); }
             // product-major: consecutive MFMAs go to different accumulators
-            static_for_wg<0, CNT>([&](auto sc) {
+            static_for<0, CNT>([&](auto sc) {
                 constexpr int p = P0 + decltype(sc)::value, ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
                 acc[decltype(sc)::value] = WG_MFMA(shifted(wh[ky - KY0], std::integral_constant<int, kx>{}), bh[c], acc[decltype(sc)::value], 0, 0, 0);
             });
             __builtin_amdgcn_sched_barrier(0);
             if (PREC == 3) {
-                lgkm_wait<NW>();
+                wg_wait<NW>();
 #pragma unroll
                 for (int c = 0; c < COTW; ++c) { tie(blq[c][0]); tie(blq[c][1]); bl[c] = frag_of(blq[c]); }
-                static_for_wg<0, CNT>([&](auto sc) {
+                static_for<0, CNT>([&](auto sc) {
                     constexpr int p = P0 + decltype(sc)::value, ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
                     acc[decltype(sc)::value] = WG_MFMA(shifted(wh[ky - KY0], std::integral_constant<int, kx>{}), bl[c], acc[decltype(sc)::value], 0, 0, 0);
                 });
                 __builtin_amdgcn_sched_barrier(0);
                 read_wh(jn);                        // behind the last reader of this k-step's hi windows
-                lgkm_wait<NW>();                    // ... the lo windows are there
+                wg_wait<NW>();                    // ... the lo windows are there
 #pragma unroll
                 for (int k = 0; k < NKY; ++k)
 #pragma unroll
                     for (int m = 0; m < 6; ++m) tie(wl[k][m]);
-                static_for_wg<0, CNT>([&](auto sc) {
+                static_for<0, CNT>([&](auto sc) {
                     constexpr int p = P0 + decltype(sc)::value, ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
                     acc[decltype(sc)::value] = WG_MFMA(shifted(wl[ky - KY0], std::integral_constant<int, kx>{}), bh[c], acc[decltype(sc)::value], 0, 0, 0);
                 });
@@ -741,7 +724,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
                 read_rest(jn);
             }
         }
-        lgkm_wait<0>();                             // the look-ahead reads of the last k-step
+        wg_wait<0>();                             // the look-ahead reads of the last k-step
     };
 
     for (int oy = row0; oy < row1; ++oy) {
@@ -803,8 +786,6 @@ hipError_t launch(hipStream_t s, const WgArgs& a, int blocks, size_t lds_bytes, 
     const hipError_t e = mpg::launch_dyn_lds<wgrad_mfma_kernel<KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks * windows), dim3(WG_THREADS), lds_bytes, s, a);
     return e != hipSuccess ? e : hipGetLastError();
 }
-
-inline size_t g8_bytes(int n, int h, int w, int c) { return (size_t)n * ((c + 7) / 8) * 2 * h * w * 16; }
 
 // all launches of one weight gradient; dw is zeroed first (the row ranges are combined with atomics)
 int wgrad_launches(hipStream_t s, const char* xg, const char* dg, const float* x_amax, const float* d_amax, int n, int h,
@@ -937,7 +918,7 @@ extern "C" int mpg_absmax(mpg_stream_t stream, const float* x, size_t n, float* 
 
 extern "C" size_t mpg_conv2d_wgrad_mfma_ws_bytes(int n, int h, int w, int cin, int cout) {
     if (n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1) return 0;
-    return 256 + g8_bytes(n, h, w, cin) + g8_bytes(n, h, w, cout);
+    return 256 + mpg_g8_bytes(n, h, w, cin) + mpg_g8_bytes(n, h, w, cout);
 }
 
 static int wgrad_check(int n, int h, int w, int cin, int cout, int kh, int kw, int prec) {
@@ -972,7 +953,7 @@ extern "C" int mpg_conv2d_wgrad_mfma(mpg_stream_t stream, const float* x, int n,
     hipStream_t s = (hipStream_t)stream;
     float* amax = (float*)workspace;
     char* xg = (char*)workspace + 256;
-    char* dg = xg + g8_bytes(n, h, w, cin);
+    char* dg = xg + mpg_g8_bytes(n, h, w, cin);
     // amax[0] / amax[1]: the callers' values where given (one small kernel: device-to-device copies are slower graph
     // nodes than a launch), zero where the reductions below fill them in
     hipLaunchKernelGGL(amax_init_kernel, dim3(1), dim3(64), 0, s, amax, x_amax, dy_amax);

@@ -188,7 +188,7 @@ LDS_TWO_WG = 80 * 1024
 
 
 def pipe(nt, prec):
-    """(tile rows, k-steps per stage, waves, stage bytes, ring bytes) of Pipe<NT, PREC> / Pipe6<NT>"""
+    """(tile rows, k-steps per stage, waves, stage bytes, ring bytes) of Pipe<NT, PREC> / Pipe6<NT> (csrc/mpgan_conv.h)"""
     if prec == 2:
         return dict(th=16, ks=4, waves=4 if nt == 1 else 8, wstage=8 * nt * 1024, ring=3 * 8 * nt * 1024)
     th = 8 if nt >= 3 else 16

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Experiment for profiles/r03/packed_fp32_followup.md: rewrites the device assembly of the SLP build of
-mpgan_conv_mfma.hip.  `expand` replaces packed fp32 instructions by their two scalar halves IN PLACE (same registers,
-same schedule around them), so that the only difference to the failing build is the instruction itself.
+mpgan_conv_small.hip (in round 3: mpgan_conv_mfma.hip, which then held every convolution kernel).  `expand` replaces packed
+fp32 instructions by their two scalar halves IN PLACE (same registers, same schedule around them), so that the only difference to the failing build is the instruction itself.
 usage: slp_asm_edit.py in.s out.s MODE [kernel-substring]
 MODE: nop_pre | nop_post | nop_both | nop8_pre | expand_all | expand_fma | expand_muladd | expand_opsel | expand_plain |
       expand_form=<hi011|sel100|hi101|sel010, or text that must occur in the instruction> | swap (v_pk_fma_f32: exchange the two
