@@ -332,7 +332,9 @@ int mpg_channel_sum_ordered(mpg_stream_t stream, const float* x, size_t npix, in
  * The blocks' partial sums are kept in `partials` (>= mpg_bn_partials_floats(c) floats of device memory) and
  * added in block order, not by atomics: the batch statistics -- and with them every ReLU mask of the step -- are
  * then the same bits on every run (a pre-activation within 1e-6 of zero otherwise changes side now and then, and one
- * flipped mask element moves the gradients upstream of it by 1 / sqrt(elements): DESIGN section 10). */
+ * flipped mask element moves the gradients upstream of it by 1 / sqrt(elements): DESIGN section 10).
+ * The moments come from one pass over x around a per-channel shift (the mean of 64 pixels spread through the batch) that
+ * is kept in batch_mean while x is read: batch_mean and batch_var must not overlap x or each other. */
 size_t mpg_bn_partials_floats(int c);
 int mpg_bn_train_fwd_ordered(mpg_stream_t stream, const float* x, size_t npix, int c, const float* gamma,
                              const float* beta, float eps, int act, float leak, float* y, float* batch_mean,

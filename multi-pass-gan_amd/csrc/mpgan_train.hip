@@ -158,13 +158,30 @@ __global__ void dgrad_kernel(const float* __restrict__ dy, const float* __restri
 // ---------------------------------------------------------------- per-channel sums over pixels
 // MODE 0: sum x
 // MODE 2: sum a, sum a*(x - mean)*invstd  (a = dy; two outputs)
-// MODE 3: sum (x - k), sum (x - k)^2 with k = bn_shift(x, ch): the channel's mean over four pixels spread through the
-//         batch: both batch moments in ONE pass over x.  With k within a few sigma of the mean,
-//         var = E[(x-k)^2] - E[x-k]^2 loses nothing to cancellation (k = the first pixel's value did: a border pixel
-//         can sit many sigma away, and the gradients through the normalisation felt it)
-__device__ __forceinline__ float bn_shift(const float* __restrict__ x, size_t npix, int c, int ch) {
-    const size_t q = npix >> 3;
-    return 0.25f * (x[q * c + ch] + x[3 * q * c + ch] + x[5 * q * c + ch] + x[7 * q * c + ch]);
+// MODE 3: sum (x - k), sum (x - k)^2 with k = aux0[ch], the shift bn_shift_kernel took from the tensor: both batch moments
+//         in ONE pass over x.  With k within a fraction of sigma of the mean, var = E[(x-k)^2] - E[x-k]^2 loses nothing to
+//         cancellation.  k = the first pixel's value did (a border pixel can sit many sigma away, and the gradients through
+//         the normalisation felt it); so did the mean of four pixels when all four were such pixels: the variance error
+//         grows with 1 + ((k - mean) / sigma)^2.
+// k[ch] = the channel's mean over BN_SHIFT_PIX pixels spread evenly through the batch (every pixel once when there are
+// fewer), added in pixel order: a few outliers among them move k by a fraction of sigma only.  A block takes four
+// channels: one thread per (pixel, channel) loads, so the 64 loads of a channel are in flight together (one thread
+// per channel walking them cost 6 us a call), then one thread per channel adds them.
+constexpr int BN_SHIFT_PIX = 64;
+static_assert(BN_SHIFT_PIX * 4 == BLK, "bn_shift_kernel: one thread per (pixel, channel of four)");
+
+__global__ __launch_bounds__(256) void bn_shift_kernel(const float* __restrict__ x, size_t npix, int c, float* __restrict__ k) {
+    __shared__ float samp[BN_SHIFT_PIX][4];
+    const int cl = threadIdx.x & 3, j = threadIdx.x >> 2;
+    const int ch = blockIdx.x * 4 + cl;
+    const int ns = npix < (size_t)BN_SHIFT_PIX ? (int)npix : BN_SHIFT_PIX;
+    if (j < ns && ch < c) samp[j][cl] = x[((size_t)j * npix / ns) * c + ch];
+    __syncthreads();
+    if (j == 0 && ch < c) {
+        float s = 0.f;
+        for (int i = 0; i < ns; ++i) s += samp[i][cl];
+        k[ch] = s / (float)ns;
+    }
 }
 
 template <int MODE>
@@ -184,7 +201,7 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const float* __restrict__
     if (ch < c) {
         float m = 0.f, is = 0.f;
         if (MODE == 2) { m = aux0[ch]; is = rsqrtf(aux1[ch] + eps); }
-        if (MODE == 3) m = bn_shift(a, npix, c, ch);
+        if (MODE == 3) m = aux0[ch];
         for (size_t p = p_begin + row; p < p_end; p += ppi) {
             const float v = a[p * c + ch];
             if (MODE == 0) s0 += v;
@@ -224,7 +241,7 @@ __global__ __launch_bounds__(256) void chan_sum4_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (MODE == 2) { m[j] = aux0[ch + j]; is[j] = rsqrtf(aux1[ch + j] + eps); }
-            if (MODE == 3) m[j] = bn_shift(a, npix, c, ch + j);
+            if (MODE == 3) m[j] = aux0[ch + j];
         }
         auto take = [&](const float4 v4, const float4 x4) {
             const float v[4] = {v4.x, v4.y, v4.z, v4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w};
@@ -302,8 +319,14 @@ constexpr int CHAN_SUM_MAX_BLOCKS = 1024;       // pixel blocks of either kernel
 // The ordered form of the sums: the blocks' partial sums ([block][channel][2]) added in a FIXED order -- 16 interleaved runs
 // of blocks per channel, then the 16 runs in sequence -- so that the result does not depend on the order the blocks ran in
 // (atomics: it does, at 1e-7 relative, enough to flip a ReLU mask element next to zero now and then).
+// BN_FWD: the two sums are those of MODE 3 around the shift k that out0 holds on entry; the kernel leaves the batch mean
+// (sum0 / n + k) and the biased variance (sum1 / n - (sum0 / n)^2) in out0 / out1 and advances the moving averages of
+// tf.contrib batch_norm (moving = decay * moving + (1 - decay) * batch) when their pointers are given
+template <bool BN_FWD>
 __global__ __launch_bounds__(256) void sum_partials_kernel(const float2* __restrict__ partials, int nblocks, int c,
-                                                           float* __restrict__ out0, float* __restrict__ out1) {
+                                                           float* out0, float* __restrict__ out1, float inv_n,
+                                                           float* __restrict__ moving_mean, float* __restrict__ moving_var,
+                                                           float decay) {
     __shared__ float2 red[256];
     const int tid = threadIdx.x, cl = tid & 15, seg = tid >> 4;
     const int ch = blockIdx.x * 16 + cl;
@@ -327,26 +350,16 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float2* __restr
     __syncthreads();
     if (seg == 0 && ch < c) {
         for (int k = 1; k < 16; ++k) { s0 += red[k * 16 + cl].x; s1 += red[k * 16 + cl].y; }
+        if (BN_FWD) {
+            const float m = s0 * inv_n;
+            s1 = fmaxf(s1 * inv_n - m * m, 0.f);
+            s0 = m + out0[ch];
+            if (moving_mean) moving_mean[ch] = decay * moving_mean[ch] + (1.f - decay) * s0;
+            if (moving_var) moving_var[ch] = decay * moving_var[ch] + (1.f - decay) * s1;
+        }
         out0[ch] = s0;
         out1[ch] = s1;
     }
-}
-
-// sums -> batch mean / biased variance, and the moving averages of tf.contrib batch_norm
-// (moving = decay * moving + (1 - decay) * batch) when their pointers are given
-__global__ void bn_finalize_kernel(float* mean, float* var, int c, float inv_n, float* moving_mean,
-                                   float* moving_var, float decay, const float* __restrict__ shift, size_t shift_npix) {
-    const int i = blockIdx.x * BLK + threadIdx.x;
-    if (i >= c) return;
-    float m = mean[i] * inv_n, v = var[i] * inv_n;
-    if (shift != nullptr) {         // sums of (x - k) and (x - k)^2 over the `shift` tensor of shift_npix pixels
-        v = fmaxf(v - m * m, 0.f);
-        m += bn_shift(shift, shift_npix, c, i);
-    }
-    mean[i] = m;
-    var[i] = v;
-    if (moving_mean) moving_mean[i] = decay * moving_mean[i] + (1.f - decay) * m;
-    if (moving_var) moving_var[i] = decay * moving_var[i] + (1.f - decay) * v;
 }
 
 // four channels per thread (c % 4 == 0, c <= 512): the per-channel vectors (possibly unaligned views into a flat parameter
@@ -956,7 +969,8 @@ extern "C" int mpg_channel_sum_ordered(mpg_stream_t stream, const float* x, size
     hipStream_t s = (hipStream_t)stream;
     float* spare = partials + (size_t)CHAN_SUM_MAX_BLOCKS * c * 2;      // sum_partials_kernel writes two vectors: the second goes here
     const int nb = launch_chan_sum<0>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, partials);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, out, spare);
+    hipLaunchKernelGGL(sum_partials_kernel<false>, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, out, spare,
+                       0.f, (float*)nullptr, (float*)nullptr, 0.f);
     MPG_LAUNCH_CHECK("chan_sum_kernel (ordered)");
 }
 
@@ -972,12 +986,11 @@ extern "C" int mpg_bn_train_fwd_ordered(mpg_stream_t stream, const float* x, siz
     MPG_REQUIRE(partials != nullptr && partials_floats >= mpg_bn_partials_floats(c), "mpg_bn_train_fwd_ordered: partials buffer too small");
     hipStream_t s = (hipStream_t)stream;
     const float inv_n = 1.f / (float)npix;
-    // sum_partials_kernel writes every sum: nothing to clear
-    const int nb = launch_chan_sum<3>(s, x, nullptr, npix, c, nullptr, nullptr, 0.f, partials);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, batch_mean,
-                       batch_var);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(grid_for(c)), dim3(BLK), 0, s, batch_mean, batch_var, c, inv_n,
-                       moving_mean, moving_var, decay, x, npix);
+    // the shift waits in batch_mean until sum_partials_kernel, which writes every sum (nothing to clear), replaces it
+    hipLaunchKernelGGL(bn_shift_kernel, dim3((c + 3) / 4), dim3(BLK), 0, s, x, npix, c, batch_mean);
+    const int nb = launch_chan_sum<3>(s, x, nullptr, npix, c, batch_mean, nullptr, 0.f, partials);
+    hipLaunchKernelGGL(sum_partials_kernel<true>, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, batch_mean,
+                       batch_var, inv_n, moving_mean, moving_var, decay);
     const size_t total = npix * c;
     const uintptr_t al = (uintptr_t)x | (uintptr_t)y;
     if ((c % 4) == 0 && c <= BN4_CMAX && (al & 15) == 0) {
@@ -1008,7 +1021,8 @@ extern "C" int mpg_bn_train_bwd_ordered(mpg_stream_t stream, const float* dy, co
     }
     const int nb = launch_chan_sum<2>(s, dy, x, npix, c, batch_mean, batch_var, eps, partials);
     // the blocks' sums in a fixed order (and no atomics queueing on 2 c addresses)
-    hipLaunchKernelGGL(sum_partials_kernel, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, dbeta, dgamma);
+    hipLaunchKernelGGL(sum_partials_kernel<false>, dim3((c + 15) / 16), dim3(256), 0, s, (const float2*)partials, nb, c, dbeta, dgamma,
+                       0.f, (float*)nullptr, (float*)nullptr, 0.f);
     const size_t total = npix * c;
     unsigned g = grid_for(total);
     if (amax != nullptr && g > AMAX_GRID) g = AMAX_GRID;

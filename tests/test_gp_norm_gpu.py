@@ -15,6 +15,8 @@ from oracle import ops as O
 from oracle import train_ref as TR
 from oracle import train_ref8x as TR8
 from oracle.nets import ParamSource
+# grad of <dx, gdx> + <dgamma, gdg> + <dbeta, gdb> with respect to (dz, x, gamma), float64 autograd
+from valu_ref import bn_double_backward_64 as _bn_double_backward_64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,23 +35,6 @@ def _t64(t):
 
 
 # ---------------------------------------------------------------------------------------------- kernels
-def _bn_double_backward_64(dz, x, gamma, gdx, gdg, gdb, eps):
-    """grad of <dx, gdx> + <dgamma, gdg> + <dbeta, gdb> with respect to (dz, x, gamma), float64 autograd"""
-    dz, x, g = _t64(dz).requires_grad_(True), _t64(x).requires_grad_(True), _t64(gamma).requires_grad_(True)
-    mu = x.mean(0)
-    v = ((x - mu) ** 2).mean(0)
-    y = (x - mu) * torch.rsqrt(v + eps) * g
-    dx, dg = torch.autograd.grad(y, (x, g), dz, create_graph=True)
-    db = dz.sum(0)
-    s = torch.zeros((), dtype=DT, device=x.device)
-    if gdx is not None:
-        s = s + (dx * _t64(gdx)).sum()
-    if gdg is not None:
-        s = s + (dg * _t64(gdg)).sum()
-    if gdb is not None:
-        s = s + (db * _t64(gdb)).sum()
-    outs = torch.autograd.grad(s, (dz, x, g), allow_unused=True)
-    return [o if o is not None else torch.zeros_like(t) for o, t in zip(outs, (dz, x, g))]
 
 
 @pytest.mark.parametrize("m,c", [(37, 4), (37, 5), (37, 130), (4099, 32), (16 * 64 * 64, 130), (16 * 128 * 128, 32),
