@@ -132,60 +132,153 @@ struct Pipe6 {
     static_assert(WSTAGE % (WAVES * 1024) == 0, "stage must be a whole number of per-wave pieces");
 };
 
+// What conv_epilogue reads from memory besides post_add, fetched once per block IN FRONT of the K loop (the K loop's
+// drain covers the loads, so no wave waits for memory between its last MFMA and its stores): thread c < cout holds
+// bias[c], every other thread (and every thread of a launch without bias) zero; cout <= 128 <= threads of a block.
+struct EpiPre {
+    float bias;
+    float amax;   // *in_amax, or 0 (pow2_scale(0) == 1)
+};
+__device__ __forceinline__ EpiPre epilogue_prefetch(const KArgs ap, int tid) {
+    const auto& a = *ap;
+    EpiPre pre;
+    pre.bias = (a.bias != nullptr && tid < a.cout) ? a.bias[tid] : 0.f;
+    pre.amax = a.in_amax != nullptr ? *a.in_amax : 0.f;
+    return pre;
+}
+
+// One tile row: acc = act(acc * unscale + bias), zero beyond cout.  bl: the block's 128 staged bias values in LDS, one
+// ds_read_b128 per quad (read again for every tile row: a wave has no registers to keep them in).
+// tanh (the last layer of a network at most) has a branch per element, and unrolled over a tile row its results would
+// not fit beside the accumulators: the row's linear part goes to this lane's slots of the wave's staging rows, tanhf runs
+// over them in a rolled loop, and the row comes back.
+template <int ACT, int NT>
+__device__ __forceinline__ void epilogue_bias_act(f32x16 (&acc)[NT], const float* bl, float* stg_lane, float unscale, float leak, int cout,
+                                                  int hh) {
+    if constexpr (ACT == MPG_ACT_TANH) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const int co0 = nt * 32 + 8 * q4 + 4 * hh;
+                const float4 bq = *reinterpret_cast<const float4*>(bl + co0);
+                *reinterpret_cast<float4*>(stg_lane + co0) =
+                    make_float4(acc[nt][4 * q4] * unscale + bq.x, acc[nt][4 * q4 + 1] * unscale + bq.y,
+                                acc[nt][4 * q4 + 2] * unscale + bq.z, acc[nt][4 * q4 + 3] * unscale + bq.w);
+            }
+#pragma nounroll
+        for (int k = 0; k < NT * 16; ++k) {
+            const int c = (k >> 2) * 8 + 4 * hh + (k & 3);
+            stg_lane[c] = c < cout ? tanhf(stg_lane[c]) : 0.f;
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 v = *reinterpret_cast<const float4*>(stg_lane + nt * 32 + 8 * q4 + 4 * hh);
+                acc[nt][4 * q4] = v.x;
+                acc[nt][4 * q4 + 1] = v.y;
+                acc[nt][4 * q4 + 2] = v.z;
+                acc[nt][4 * q4 + 3] = v.w;
+            }
+        return;
+    }
+    // the bias quads of cout tile nt + 1 are read while tile nt is worked on and no further ahead (the scheduling barriers):
+    // 8 registers per lane in flight instead of the 16 NT an unbounded look-ahead may take beside the accumulators
+    float4 bq[2][4];
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) bq[0][q4] = *reinterpret_cast<const float4*>(bl + 8 * q4 + 4 * hh);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        if (nt + 1 < NT) {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) bq[(nt + 1) & 1][q4] = *reinterpret_cast<const float4*>(bl + (nt + 1) * 32 + 8 * q4 + 4 * hh);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int co0 = nt * 32 + 8 * q4 + 4 * hh;
+            const float b4[4] = {bq[nt & 1][q4].x, bq[nt & 1][q4].y, bq[nt & 1][q4].z, bq[nt & 1][q4].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float v = mpg::apply_act(acc[nt][4 * q4 + i] * unscale + b4[i], ACT, leak);
+                if (co0 + i >= cout) v = 0.f;
+                acc[nt][4 * q4 + i] = v;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The values of one tile row: bias and activation (one uniform switch per tile row around code that holds a single
+// activation), then pixel norm (per-pixel sum over the lane's values + one __shfl_xor 32)
+template <int NT>
+__device__ __forceinline__ void epilogue_row_values(f32x16 (&acc)[NT], const KArgs ap, const float* bl, float* stg_lane, float unscale,
+                                                    int hh) {
+    const auto& a = *ap;
+    switch (a.act) {
+        case MPG_ACT_RELU: epilogue_bias_act<MPG_ACT_RELU>(acc, bl, stg_lane, unscale, a.leak, a.cout, hh); break;
+        case MPG_ACT_LRELU: epilogue_bias_act<MPG_ACT_LRELU>(acc, bl, stg_lane, unscale, a.leak, a.cout, hh); break;
+        case MPG_ACT_TANH: epilogue_bias_act<MPG_ACT_TANH>(acc, bl, stg_lane, unscale, a.leak, a.cout, hh); break;
+        default: epilogue_bias_act<MPG_ACT_NONE>(acc, bl, stg_lane, unscale, a.leak, a.cout, hh); break;
+    }
+    if (a.pn) {
+        float ss = 0.f;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) ss += acc[nt][i] * acc[nt][i];
+        ss += __shfl_xor(ss, 32);
+        const float sc = rsqrtf(ss / (float)a.cout + a.pn_eps);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[nt][i] *= sc;
+    }
+}
+
 // D2S: every output goes to its depth-to-space position (ConvArgsD2S; no pixel norm, no post-add); only the store
-// addresses differ
+// addresses differ.  Both K loops end behind `s_waitcnt vmcnt(0)` + barrier (a launch that skips them, dbg & 1, has not
+// touched LDS at all), so the tap table at the start of LDS is dead: the bias (EpiPre, one value per thread) is staged
+// there for the block.  The launch's output kind is decided once, in front of the tile rows: the G8-only rows and the
+// LDS-staged rows are two loops, so that no load of the staged path (post_add) is pending, as far as the compiler can
+// tell, where the G8-only path writes registers or stores.
 template <int NT, int PT, bool D2S = false>
 __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs ap, char* smem, int n, int y0, int x0,
-                                              int wave, int lane) {
+                                              int wave, int lane, const EpiPre pre) {
     const auto& a = *ap;
     const KArgsD2S dp = reinterpret_cast<KArgsD2S>(ap);
     const int r = lane & 31;
     const int hh = lane >> 5;
     // accumulator element i of n-tile nt: output channel nt*32 + 8*(i>>2) + 4*hh + (i&3), pixel r.
     constexpr int ROWF = epi_rowf(NT);
+    static_assert(128 * sizeof(float) <= TAPOFF_BYTES, "the staged bias must fit in front of the staging rows");
+    float* bl = reinterpret_cast<float*>(smem);
     float* stg = reinterpret_cast<float*>(smem + TAPOFF_BYTES) + wave * (32 * ROWF);
     const int cg_out = (a.cout + 7) >> 3;
-    const float unscale = a.in_amax != nullptr ? 1.f / mpg::pow2_scale(*a.in_amax) : 1.f;
+    const float unscale = 1.f / mpg::pow2_scale(pre.amax);
+    {
+        // every thread takes its prefetched value here: behind the drain the counter is at zero, and a register the
+        // compiler still believed to be waiting for its load would cost a wait wherever it is written next
+        float bv = pre.bias;
+        asm volatile("" : "+v"(bv));
+        if (wave < 2) bl[wave * 64 + lane] = bv;
+    }
+    __syncthreads();
+    const int npx = min(32, a.w - x0);
+    const size_t plane_px = (size_t)a.h * a.w;
+    if (a.y == nullptr && a.post_add == nullptr) {
+        // G8 output only (every launch between two fused convolutions): no LDS staging and no load from memory, so
+        // nothing waits between the tile rows and their stores leave back to back.  An accumulator quad holds
+        // channels 8 q + 4 hh .. + 3 of pixel r, i.e. the two lanes (r, hh = 0 / 1) share every 8-channel group.
+        // v_permlane32_swap trades the upper half-wave of one quad register with the lower half-wave of another:
+        // after four swaps lane (r, 0) holds all 8 channels of group gA and lane (r, 1) all 8 of group gB, ready
+        // to be split into the hi / lo planes and stored as 512-byte runs per plane and half-wave.
 #pragma unroll
-    for (int pt = 0; pt < PT; ++pt) {
-        const int py = y0 + PT * wave + pt;
-        float ss = 0.f;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int co0 = nt * 32 + 8 * q4 + 4 * hh;
-                float b4[4] = {0.f, 0.f, 0.f, 0.f};
-                if (a.bias != nullptr) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (co0 + i < a.cout) b4[i] = a.bias[co0 + i];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v = mpg::apply_act(acc[pt][nt][4 * q4 + i] * unscale + b4[i], a.act, a.leak);
-                    if (co0 + i >= a.cout) v = 0.f;
-                    acc[pt][nt][4 * q4 + i] = v;
-                    ss += v * v;
-                }
-            }
-        if (a.pn) {
-            ss += __shfl_xor(ss, 32);
-            const float sc = rsqrtf(ss / (float)a.cout + a.pn_eps);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[pt][nt][i] *= sc;
-        }
-        if (a.y == nullptr && a.post_add == nullptr) {
-            // G8 output only (every launch between two fused convolutions): no LDS staging.  An accumulator quad holds
-            // channels 8 q + 4 hh .. + 3 of pixel r, i.e. the two lanes (r, hh = 0 / 1) share every 8-channel group.
-            // v_permlane32_swap trades the upper half-wave of one quad register with the lower half-wave of another:
-            // after four swaps lane (r, 0) holds all 8 channels of group gA and lane (r, 1) all 8 of group gB, ready
-            // to be split into the hi / lo planes and stored as 512-byte runs per plane and half-wave.
-            const int npx = min(32, a.w - x0);
+        for (int pt = 0; pt < PT; ++pt) {
+            const int py = y0 + PT * wave + pt;
+            epilogue_row_values<NT>(acc[pt], ap, bl, stg + r * ROWF, unscale, hh);
             if (py < a.h && r < npx && !(a.dbg & 2)) {
-                const size_t plane_px = (size_t)a.h * a.w;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -221,8 +314,13 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                         }
                     }
             }
-            continue;
         }
+        return;
+    }
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) {
+        const int py = y0 + PT * wave + pt;
+        epilogue_row_values<NT>(acc[pt], ap, bl, stg + r * ROWF, unscale, hh);
         // stage this wave's 32 pixels x cout through LDS ([pixel][cout] rows padded by 16 B); the 32
         // pixels of a tile row are contiguous in every output layout, so all stores are whole runs
 #pragma unroll
@@ -234,15 +332,28 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                     make_float4(acc[pt][nt][4 * q4], acc[pt][nt][4 * q4 + 1], acc[pt][nt][4 * q4 + 2], acc[pt][nt][4 * q4 + 3]);
             }
         if (py < a.h && !(a.dbg & 2)) {
-            const int npx = min(32, a.w - x0);
             const size_t pix0 = ((size_t)n * a.h + py) * a.w + x0;
             if (a.post_add != nullptr) {
                 // add into the staged tile first, so both output formats carry it
                 const float* pa = a.post_add + pix0 * a.pa_stride + a.pa_coff;
-                for (int f = lane; f < npx * a.cout; f += 64) {
-                    const int p = f / a.cout;
-                    const int c = f - p * a.cout;
-                    stg[p * ROWF + c] += pa[(size_t)p * a.pa_stride + c];
+                // four loads in flight per lane; an index past the tile re-reads the tile's last element and adds nothing
+                const int total = npx * a.cout;
+                for (int f0 = lane; f0 < total; f0 += 256) {
+                    float pv[4];
+                    int so[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int f = min(f0 + 64 * j, total - 1);
+                        const int p = f / a.cout;
+                        const int c = f - p * a.cout;
+                        so[j] = p * ROWF + c;
+                        pv[j] = pa[(size_t)p * a.pa_stride + c];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        asm volatile("" : "+v"(pv[j]));      // all four are taken here: none stays pending behind the loop
+                        if (f0 + 64 * j < total) stg[so[j]] += pv[j];
+                    }
                 }
             }
             if (D2S && a.y != nullptr) {
@@ -284,7 +395,6 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                 // lane (pixel r, half hh) converts channel group 2 i + hh and writes BOTH of its planes (hi16, lo16): no
                 // divergence between the halves, 512-byte runs per plane and half-wave; streamed (read once or twice by
                 // the next launch), so the stores do not push the weights out of L2
-                const size_t plane_px = (size_t)a.h * a.w;
                 if (r < npx) {
                     for (int cg = hh; cg < cg_out; cg += 2) {
                         const float4 v0 = *reinterpret_cast<const float4*>(stg + r * ROWF + cg * 8);

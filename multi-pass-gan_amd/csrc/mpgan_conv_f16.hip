@@ -55,6 +55,7 @@ __global__ __launch_bounds__(256, (NT >= 2 ? 2 : 3)) void conv_mfma_kernel(const
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[pt][nt][i] = 0.f;
 
+    const EpiPre pre = epilogue_prefetch(ap, tid);   // bias and input scale of the epilogue: landed long before it runs
     for (int s = 0; s < ((a.dbg & 1) ? 0 : a.nseg); ++s) {
         const auto& sg = ap->seg[s];
         const int CGC = sg.cgc;
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256, (NT >= 2 ? 2 : 3)) void conv_mfma_kernel(const
         __syncthreads();
     }
 
-    conv_epilogue<NT, PT, D2S>(acc, ap, smem, n, y0, x0, wave, lane);
+    conv_epilogue<NT, PT, D2S>(acc, ap, smem, n, y0, x0, wave, lane, pre);
 }
 
 template <bool D2S>

@@ -197,6 +197,7 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, 2) void conv_mfma_f6_kernel(
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[pt][nt][i] = 0.f;
 
+    const EpiPre pre = epilogue_prefetch(ap, tid);   // bias and input scale of the epilogue: landed long before it runs
     // The K segments are independent partial sums.  Blocks that share a CU (workgroups go round-robin over the 8
     // XCDs, then over the 32 CUs of an XCD: co-resident blocks differ in bit 8 of the id) walk them in opposite
     // orders, so one block's HBM-bound direct 1x1 segment runs under the other's LDS / MFMA-bound 5x5 segment.
@@ -612,7 +613,7 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, 2) void conv_mfma_f6_kernel(
         }
 #endif
     }
-    conv_epilogue<NT, PT>(acc, ap, smem, n, y0, x0, wave, lane);
+    conv_epilogue<NT, PT>(acc, ap, smem, n, y0, x0, wave, lane, pre);
 }
 
 }  // namespace

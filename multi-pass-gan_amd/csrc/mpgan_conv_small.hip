@@ -60,6 +60,29 @@ constexpr int SM_TW = 64, SM_RPT = MPG_SM_RPT, SM_TH = 4 * SM_RPT, SM_KMAX = 7;
 __device__ unsigned g_small_diag[2];
 #endif
 
+// The <= 8 bias values of a small layer, read once per thread in front of every loop (uniform addresses; index clamped
+// to the last channel instead of a branch per value: nothing at or beyond bias + cout is read, and channels beyond cout
+// are never used).  Zeros without a bias.
+template <int C>
+__device__ __forceinline__ void small_bias(const float* bias, int cout, float (&bq)[C]) {
+#pragma unroll
+    for (int q = 0; q < C; ++q) bq[q] = 0.f;
+    if (bias != nullptr) {
+#pragma unroll
+        for (int q = 0; q < C; ++q) bq[q] = bias[q < cout ? q : cout - 1];
+    }
+}
+// run f(std::integral_constant<int, act>): one uniform switch around code that holds a single activation
+template <class F>
+__device__ __forceinline__ void with_act(int act, F&& f) {
+    switch (act) {
+        case MPG_ACT_RELU: f(std::integral_constant<int, MPG_ACT_RELU>{}); break;
+        case MPG_ACT_LRELU: f(std::integral_constant<int, MPG_ACT_LRELU>{}); break;
+        case MPG_ACT_TANH: f(std::integral_constant<int, MPG_ACT_TANH>{}); break;
+        default: f(std::integral_constant<int, MPG_ACT_NONE>{}); break;
+    }
+}
+
 // COUT / CINB: output channels / input channels per segment rounded up to 1, 2, 4, 8 (compile-time loop bounds: the
 // weight table holds zeros beyond cin and cout, a G8 group holds zeros beyond its channels)
 template <int COUT, int CINB>
@@ -75,6 +98,9 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
 #if MPG_SMALL_INV
     asm volatile("buffer_inv sc0 sc1" ::: "memory");
 #endif
+    float bq[COUT];
+    small_bias(a.bias, a.cout, bq);
+    const float amax = a.in_amax != nullptr ? *a.in_amax : 0.f;     // pow2_scale(0) == 1
     float acc[SM_RPT][COUT];
 #pragma unroll
     for (int j = 0; j < SM_RPT; ++j)
@@ -181,31 +207,36 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
     }
     const int x = x0 + lx;
     if (x >= a.w) return;
-    const float unscale = a.in_amax != nullptr ? 1.f / mpg::pow2_scale(*a.in_amax) : 1.f;
+    const float unscale = 1.f / mpg::pow2_scale(amax);
     const size_t plane_px = (size_t)a.h * a.w;
+    // the values of the thread's SM_RPT pixels under the launch's activation (the only code that differs between the
+    // activations), then the stores
+    float o[SM_RPT][8];
+    with_act(a.act, [&](auto actc) {
+        constexpr int ACT = decltype(actc)::value;
+#pragma unroll
+        for (int j = 0; j < SM_RPT; ++j)
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                o[j][q] = (q < COUT && q < a.cout) ? mpg::apply_act(acc[j][q < COUT ? q : 0] * unscale + bq[q < COUT ? q : 0], ACT, a.leak) : 0.f;
+    });
 #pragma unroll
     for (int j = 0; j < SM_RPT; ++j) {
         const int y = y0 + yg * SM_RPT + j;
         if (y >= a.h) break;
-        float o[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            o[q] = (q < COUT && q < a.cout) ? mpg::apply_act(acc[j][q < COUT ? q : 0] * unscale + (a.bias != nullptr ? a.bias[q] : 0.f),
-                                                              a.act, a.leak)
-                                            : 0.f;
         const size_t pix = (size_t)y * a.w + x;
         if (a.y != nullptr) {
             float* dst = a.y + ((size_t)b * plane_px + pix) * a.cout;
 #pragma unroll
             for (int q = 0; q < 8; ++q)
-                if (q < a.cout) dst[q] = o[q];
+                if (q < a.cout) dst[q] = o[j][q];
         }
         if (a.y_g8 != nullptr) {
             half8 hi, lo;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                hi[q] = (_Float16)o[q];
-                lo[q] = (_Float16)(o[q] - (float)hi[q]);
+                hi[q] = (_Float16)o[j][q];
+                lo[q] = (_Float16)(o[j][q] - (float)hi[q]);
             }
             char* dst = a.y_g8 + ((size_t)b * 2 * plane_px + pix) * 16;
             *reinterpret_cast<half8*>(dst) = hi;
@@ -236,7 +267,7 @@ struct PairArgs {
     const float *bias_a, *bias_b;
     int act_a, act_b;
     float leak_a, leak_b;
-    int cout;
+    int cmid, cout;
     float* y;
     char* y_g8;
     int x_px, mid_px;              // pixels of the input tile / of the middle tile (LDS plane sizes)
@@ -294,6 +325,9 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
     float* wls = wlb + a.khb * a.kwb * CMIDB * COUTB;                 // [tap][CINB][COUTB]
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * SM_TW, y0 = blockIdx.y * SM_TH, b = blockIdx.z;
+    float bqa[CMIDB], bqb[COUTB];
+    small_bias(a.bias_a, a.cmid, bqa);    // (middle channels beyond cmid meet zero weights in stage B)
+    small_bias(a.bias_b, a.cout, bqb);
     const int mw = SM_TW + a.kwb - 1, mh = SM_TH + a.khb - 1;         // middle tile
     const int xw = mw + a.kwa - 1, xh = mh + a.kha - 1;               // input tile
     const int mx0 = x0 - a.plb, my0 = y0 - a.ptb;                     // image coordinates of the tiles' first pixels
@@ -339,18 +373,23 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
 #pragma unroll
             for (int c = 0; c < CMIDB; ++c) acc[j][c] = 0.f;
         small_column<CINB, CMIDB>(xt, xw, a.x_px, rg * SM_RPT, col, wla, a.kha, a.kwa, acc);
+        float o[SM_RPT][8];
+        with_act(a.act_a, [&](auto actc) {
+            constexpr int ACT = decltype(actc)::value;
+#pragma unroll
+            for (int j = 0; j < SM_RPT; ++j)
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    o[j][c] = c < CMIDB ? mpg::apply_act(acc[j][c < CMIDB ? c : 0] + bqa[c < CMIDB ? c : 0], ACT, a.leak_a) : 0.f;
+        });
 #pragma unroll
         for (int j = 0; j < SM_RPT; ++j) {
             const int row = rg * SM_RPT + j;
             if (row < mh) {
                 const int yy = my0 + row, xx = mx0 + col;
                 const bool in = yy >= 0 && yy < a.h && xx >= 0 && xx < a.w;
-                float o[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    o[c] = (c < CMIDB && in) ? mpg::apply_act(acc[j][c < CMIDB ? c : 0] + (a.bias_a != nullptr ? a.bias_a[c] : 0.f), a.act_a, a.leak_a) : 0.f;
-                mt[row * mw + col] = make_float4(o[0], o[1], o[2], o[3]);
-                if (PLM > 1) mt[a.mid_px + row * mw + col] = make_float4(o[4], o[5], o[6], o[7]);
+                mt[row * mw + col] = in ? make_float4(o[j][0], o[j][1], o[j][2], o[j][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (PLM > 1) mt[a.mid_px + row * mw + col] = in ? make_float4(o[j][4], o[j][5], o[j][6], o[j][7]) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
     }
@@ -368,27 +407,32 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
     const int x = x0 + lx;
     if (x >= a.w) return;
     const size_t plane_px = (size_t)a.h * a.w;
+    float o[SM_RPT][8];
+    with_act(a.act_b, [&](auto actc) {
+        constexpr int ACT = decltype(actc)::value;
+#pragma unroll
+        for (int j = 0; j < SM_RPT; ++j)
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                o[j][q] = (q < COUTB && q < a.cout) ? mpg::apply_act(acc[j][q < COUTB ? q : 0] + bqb[q < COUTB ? q : 0], ACT, a.leak_b) : 0.f;
+    });
 #pragma unroll
     for (int j = 0; j < SM_RPT; ++j) {
         const int y = y0 + yg * SM_RPT + j;
         if (y >= a.h) break;
-        float o[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            o[q] = (q < COUTB && q < a.cout) ? mpg::apply_act(acc[j][q < COUTB ? q : 0] + (a.bias_b != nullptr ? a.bias_b[q] : 0.f), a.act_b, a.leak_b) : 0.f;
         const size_t pix = (size_t)y * a.w + x;
         if (a.y != nullptr) {
             float* dst = a.y + ((size_t)b * plane_px + pix) * a.cout;
 #pragma unroll
             for (int q = 0; q < 8; ++q)
-                if (q < a.cout) dst[q] = o[q];
+                if (q < a.cout) dst[q] = o[j][q];
         }
         if (a.y_g8 != nullptr) {
             half8 hi, lo;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                hi[q] = (_Float16)o[q];
-                lo[q] = (_Float16)(o[q] - (float)hi[q]);
+                hi[q] = (_Float16)o[j][q];
+                lo[q] = (_Float16)(o[j][q] - (float)hi[q]);
             }
             char* dst = a.y_g8 + ((size_t)b * 2 * plane_px + pix) * 16;
             *reinterpret_cast<half8*>(dst) = hi;
@@ -471,7 +515,7 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
     a.khb = d->kh_b; a.kwb = d->kw_b; a.ptb = pad_before(d->kh_b, 0); a.plb = pad_before(d->kw_b, 0);
     a.khs = d->wpack_s ? d->kh_s : 1; a.kws = d->wpack_s ? d->kw_s : 1; a.pts = pad_before(a.khs, 0); a.pls = pad_before(a.kws, 0);
     a.bias_a = d->bias_a; a.bias_b = d->bias_b; a.act_a = d->act_a; a.act_b = d->act_b; a.leak_a = d->leak_a; a.leak_b = d->leak_b;
-    a.cout = d->cout; a.y = d->y; a.y_g8 = (char*)d->y_g8;
+    a.cmid = d->cmid; a.cout = d->cout; a.y = d->y; a.y_g8 = (char*)d->y_g8;
     const int mw = SM_TW + a.kwb - 1, mh = SM_TH + a.khb - 1;
     const int mgroups = (mh + SM_RPT - 1) / SM_RPT;
     const int xw = mw + a.kwa - 1, xh = mgroups * SM_RPT + a.kha - 1;      // rows past the middle tile are read, never used
