@@ -3,13 +3,11 @@
 // plain fp32 direct convolution on the vector ALUs (strided / odd shapes and an
 // independent check of the MFMA kernel).  One thread per output element with
 // the channel (or x) index fastest, so wave accesses are contiguous.
-#include "mpgan_internal.h"
+#include "mpgan_valu.h"
+
+using namespace mpg::valu;
 
 namespace {
-
-constexpr int BLK = 256;
-
-inline unsigned grid_for(size_t n) { return (unsigned)((n + BLK - 1) / BLK); }
 
 // ---------------------------------------------------------------- direct conv (tf.nn.conv2d SAME, GAN.py:686-691)
 __global__ void conv_direct_kernel(const float* __restrict__ x, int n, int h, int w, int cin,
@@ -205,7 +203,7 @@ __global__ void pixel_norm_kernel(const float* __restrict__ x, size_t npix, int 
 // stat[m] = mean over (h, w, c) of sqrt(var over g + 1e-8).  Pass 1 accumulates the per-m sums.
 __global__ __launch_bounds__(256) void mbstd_stat_kernel(const float* __restrict__ x, int g, int m, size_t hwc,
                                                          float* __restrict__ stat) {
-    __shared__ float red[BLK];
+    __shared__ float red[1][BLK];
     const int mi = blockIdx.y;
     float s = 0.f;
     for (size_t i = (size_t)blockIdx.x * BLK + threadIdx.x; i < hwc; i += (size_t)gridDim.x * BLK) {
@@ -219,13 +217,9 @@ __global__ __launch_bounds__(256) void mbstd_stat_kernel(const float* __restrict
         }
         s += sqrtf(var / (float)g + 1e-8f);
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = BLK / 2; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd(stat + mi, red[0]);
+    red[0][threadIdx.x] = s;
+    block_tree_sum(red);
+    if (threadIdx.x == 0) atomicAdd(stat + mi, red[0][0]);
 }
 
 // pass 2: y[n, p, 0..c-1] = x, y[n, p, c] = stat[n % m] / hwc
@@ -242,7 +236,7 @@ __global__ void mbstd_concat_kernel(const float* __restrict__ x, const float* __
 // backward.  dstat[m] = sum over the group's members and pixels of dy[.., c] (the broadcast statistic's gradient).
 __global__ __launch_bounds__(256) void mbstd_bwd_stat_kernel(const float* __restrict__ dy, int n, int m, size_t npix_per, int c,
                                                              float* __restrict__ dstat) {
-    __shared__ float red[BLK];
+    __shared__ float red[1][BLK];
     const int mi = blockIdx.y;
     const int g = n / m;
     float s = 0.f;
@@ -251,13 +245,9 @@ __global__ __launch_bounds__(256) void mbstd_bwd_stat_kernel(const float* __rest
         const size_t k = i / npix_per, p = i - k * npix_per;
         s += dy[(((size_t)k * m + mi) * npix_per + p) * (c + 1) + c];
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = BLK / 2; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd(dstat + mi, red[0]);
+    red[0][threadIdx.x] = s;
+    block_tree_sum(red);
+    if (threadIdx.x == 0) atomicAdd(dstat + mi, red[0][0]);
 }
 
 // dx[k,i] = dy[k,i (channels < c)] + dstat[m] / hwc * (x[k,i] - mean_i) / (g * sqrt(var_i + 1e-8))
@@ -311,6 +301,16 @@ __global__ void axis_zoom_kernel(const float* __restrict__ v, size_t outer, int 
     const double a = v[(ou * n + i0) * inner + in];
     const double b = v[(ou * n + i1) * inner + in];
     out[idx] = (float)(a * (1.0 - t) + b * t);
+}
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// values below the cutoff become 0
+__device__ __forceinline__ float cut_below(float x, float cutoff) { return x < cutoff ? 0.f : x; }
+__device__ __forceinline__ f4v cut_below(f4v x, float cutoff) {
+    x.x = x.x < cutoff ? 0.f : x.x; x.y = x.y < cutoff ? 0.f : x.y;
+    x.z = x.z < cutoff ? 0.f : x.z; x.w = x.w < cutoff ? 0.f : x.w;
+    return x;
 }
 
 struct PermArgs {
@@ -397,10 +397,8 @@ __global__ __launch_bounds__(256) void transpose_tiled_kernel(const float* __res
 // The XOR swizzle makes both the LDS writes (16 lanes of one row: 16 distinct quads) and the LDS reads (16 lanes with
 // ag = 0..15 and one bq: quads bq ^ ag, all distinct) conflict-free without padding.  Needs every extent and stride
 // to be a multiple of 4 elements and 16-byte aligned pointers; the scalar kernel above takes the rest.
-typedef float f4t __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void transpose_tiled4_kernel(const float* __restrict__ v, TileArgs a, float* __restrict__ out) {
-    __shared__ f4t tile4[64][16];
+    __shared__ f4v tile4[64][16];
     int bid = blockIdx.x;
     const int tb = bid % a.tiles_b; bid /= a.tiles_b;
     const int ta = bid % a.tiles_a;
@@ -413,15 +411,15 @@ __global__ __launch_bounds__(256) void transpose_tiled4_kernel(const float* __re
         for (int k = 0; k < 4; ++k) {
             const int la = ar + 16 * k;
             const int ia = a0 + la, ib = b0 + 4 * b4;
-            f4t x = {0.f, 0.f, 0.f, 0.f};
-            if (ia < a.da && ib < a.db) x = __builtin_nontemporal_load(reinterpret_cast<const f4t*>(src + (size_t)ia * a.sin_a + ib));
+            f4v x = {0.f, 0.f, 0.f, 0.f};
+            if (ia < a.da && ib < a.db) x = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(src + (size_t)ia * a.sin_a + ib));
             tile4[la][b4 ^ (la >> 2)] = x;
         }
     }
     __syncthreads();
     float* dst = out + (size_t)rr * a.sout_r;
     const int ag = threadIdx.x & 15, bq = threadIdx.x >> 4;
-    f4t r[4];
+    f4v r[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = tile4[4 * ag + i][bq ^ ag];
     const int ia = a0 + 4 * ag;
@@ -430,12 +428,9 @@ __global__ __launch_bounds__(256) void transpose_tiled4_kernel(const float* __re
         for (int j = 0; j < 4; ++j) {
             const int ib = b0 + 4 * bq + j;
             if (ib < a.db) {
-                f4t o = {r[0][j], r[1][j], r[2][j], r[3][j]};
-                if (a.cutoff > 0.f) {
-                    o.x = o.x < a.cutoff ? 0.f : o.x; o.y = o.y < a.cutoff ? 0.f : o.y;
-                    o.z = o.z < a.cutoff ? 0.f : o.z; o.w = o.w < a.cutoff ? 0.f : o.w;
-                }
-                __builtin_nontemporal_store(o, reinterpret_cast<f4t*>(dst + (size_t)ib * a.sout_b + ia));
+                f4v o = {r[0][j], r[1][j], r[2][j], r[3][j]};
+                if (a.cutoff > 0.f) o = cut_below(o, a.cutoff);
+                __builtin_nontemporal_store(o, reinterpret_cast<f4v*>(dst + (size_t)ib * a.sout_b + ia));
             }
         }
     }
@@ -457,23 +452,16 @@ __global__ void add_adjacent_kernel(const float* __restrict__ in, int s_total, s
     out[idx] = v;
 }
 
-__global__ void cutoff_kernel(const float* __restrict__ v, size_t n, float cutoff, float* __restrict__ out) {
+// V = 4: 16 bytes per lane, streamed once (nv = n / 4; the tail goes through V = 1)
+template <int V>
+__global__ void cutoff_kernel(const float* __restrict__ v, size_t nv, float cutoff, float* __restrict__ out) {
     const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
-    if (idx >= n) return;
-    const float x = v[idx];
-    out[idx] = x < cutoff ? 0.f : x;
-}
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// 16 bytes per lane, streamed once (n4 = n / 4; the tail goes through cutoff_kernel)
-__global__ void cutoff4_kernel(const f4v* __restrict__ v, size_t n4, float cutoff, f4v* __restrict__ out) {
-    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
-    if (idx >= n4) return;
-    f4v x = __builtin_nontemporal_load(v + idx);
-    x.x = x.x < cutoff ? 0.f : x.x; x.y = x.y < cutoff ? 0.f : x.y;
-    x.z = x.z < cutoff ? 0.f : x.z; x.w = x.w < cutoff ? 0.f : x.w;
-    __builtin_nontemporal_store(x, out + idx);
+    if (idx >= nv) return;
+    if constexpr (V == 4) {
+        const f4v x = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(v) + idx);
+        __builtin_nontemporal_store(cut_below(x, cutoff), reinterpret_cast<f4v*>(out) + idx);
+    } else
+        out[idx] = cut_below(v[idx], cutoff);
 }
 
 // transposes that keep the last axis (perm (1,0,2)) are row copies: out[i1][i0][:] = in[i0][i1][:], 16 bytes per lane
@@ -486,10 +474,7 @@ __global__ void swap01_rows_kernel(const f4v* __restrict__ v, int d0, int d1, in
     const int i0 = r % d0;
     const int i1 = r / d0;
     f4v x = __builtin_nontemporal_load(v + ((size_t)i0 * d1 + i1) * row4 + q);
-    if (cutoff > 0.f) {
-        x.x = x.x < cutoff ? 0.f : x.x; x.y = x.y < cutoff ? 0.f : x.y;
-        x.z = x.z < cutoff ? 0.f : x.z; x.w = x.w < cutoff ? 0.f : x.w;
-    }
+    if (cutoff > 0.f) x = cut_below(x, cutoff);
     __builtin_nontemporal_store(x, out + idx);
 }
 
@@ -548,36 +533,24 @@ __global__ void depth_to_space_kernel(const float* __restrict__ x, int n, int h,
     y[idx] = x[(((size_t)b * h + q) * w + pp) * ((size_t)c_out * r * r) + (size_t)(i * r + j) * c_out + c];
 }
 
-// the adjoint of depth_to_space_kernel (its gradient): y[b, q, p, (i*r + j)*C + c] = x[b, r*q + i, r*p + j, c], one float4 of
-// 4 channels per thread (C % 4 == 0), stores in y order
-__global__ void space_to_depth4_kernel(const float4* __restrict__ x, int n, int h, int w, int c4, int r, float4* __restrict__ y) {
+// the adjoint of depth_to_space_kernel (its gradient): y[b, q, p, (i*r + j)*C + c] = x[b, r*q + i, r*p + j, c], V channels
+// per thread (V = 4: C % 4 == 0, one float4), cv = C / V, stores in y order
+template <int V>
+__global__ void space_to_depth_kernel(const float* __restrict__ x, int n, int h, int w, int cv, int r, float* __restrict__ y) {
     const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
     const int oh = h / r, ow = w / r;
-    const size_t total = (size_t)n * oh * ow * r * r * c4;
+    const size_t total = (size_t)n * oh * ow * r * r * cv;
     if (idx >= total) return;
-    const int c = idx % c4;
-    size_t p = idx / c4;
+    const int c = idx % cv;
+    size_t p = idx / cv;
     const int k = p % (r * r); p /= r * r;
     const int px = p % ow; p /= ow;
     const int qy = p % oh;
     const int b = p / oh;
     const int i = k / r, j = k - i * r;
-    y[idx] = x[(((size_t)b * h + r * qy + i) * w + r * px + j) * c4 + c];
-}
-
-__global__ void space_to_depth_kernel(const float* __restrict__ x, int n, int h, int w, int c, int r, float* __restrict__ y) {
-    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
-    const int oh = h / r, ow = w / r;
-    const size_t total = (size_t)n * oh * ow * r * r * c;
-    if (idx >= total) return;
-    const int ci = idx % c;
-    size_t p = idx / c;
-    const int k = p % (r * r); p /= r * r;
-    const int px = p % ow; p /= ow;
-    const int qy = p % oh;
-    const int b = p / oh;
-    const int i = k / r, j = k - i * r;
-    y[idx] = x[(((size_t)b * h + r * qy + i) * w + r * px + j) * c + ci];
+    float t[V];
+    ldv<V>(x + ((((size_t)b * h + r * qy + i) * w + r * px + j) * cv + c) * V, t);
+    stv<V>(y + idx * V, t);
 }
 
 }  // namespace
@@ -826,13 +799,12 @@ extern "C" int mpg_cutoff(mpg_stream_t stream, const float* v, size_t n, float c
     if (n == 0) return MPG_OK;
     if (n >= 1024 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)out & 15) == 0) {
         const size_t n4 = n / 4;
-        hipLaunchKernelGGL(cutoff4_kernel, dim3(grid_for(n4)), dim3(BLK), 0, (hipStream_t)stream,
-                           reinterpret_cast<const f4v*>(v), n4, cutoff, reinterpret_cast<f4v*>(out));
+        hipLaunchKernelGGL(cutoff_kernel<4>, dim3(grid_for(n4)), dim3(BLK), 0, (hipStream_t)stream, v, n4, cutoff, out);
         if (n4 * 4 < n)
-            hipLaunchKernelGGL(cutoff_kernel, dim3(1), dim3(BLK), 0, (hipStream_t)stream, v + n4 * 4, n - n4 * 4, cutoff, out + n4 * 4);
-        MPG_LAUNCH_CHECK("cutoff4_kernel");
+            hipLaunchKernelGGL(cutoff_kernel<1>, dim3(1), dim3(BLK), 0, (hipStream_t)stream, v + n4 * 4, n - n4 * 4, cutoff, out + n4 * 4);
+        MPG_LAUNCH_CHECK("cutoff_kernel<4>");
     }
-    hipLaunchKernelGGL(cutoff_kernel, dim3(grid_for(n)), dim3(BLK), 0, (hipStream_t)stream, v, n, cutoff, out);
+    hipLaunchKernelGGL(cutoff_kernel<1>, dim3(grid_for(n)), dim3(BLK), 0, (hipStream_t)stream, v, n, cutoff, out);
     MPG_LAUNCH_CHECK("cutoff_kernel");
 }
 
@@ -866,10 +838,10 @@ extern "C" int mpg_space_to_depth(mpg_stream_t stream, const float* x, int n, in
                 "mpg_space_to_depth: %dx%d is not a multiple of the block size %d", h, w, r);
     const size_t total = (size_t)n * h * w * c;
     if (c % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-        hipLaunchKernelGGL(space_to_depth4_kernel, dim3(grid_for(total / 4)), dim3(BLK), 0, (hipStream_t)stream,
-                           reinterpret_cast<const float4*>(x), n, h, w, c / 4, r, reinterpret_cast<float4*>(y));
-        MPG_LAUNCH_CHECK("space_to_depth4_kernel");
+        hipLaunchKernelGGL(space_to_depth_kernel<4>, dim3(grid_for(total / 4)), dim3(BLK), 0, (hipStream_t)stream, x, n, h, w,
+                           c / 4, r, y);
+        MPG_LAUNCH_CHECK("space_to_depth_kernel<4>");
     }
-    hipLaunchKernelGGL(space_to_depth_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, x, n, h, w, c, r, y);
+    hipLaunchKernelGGL(space_to_depth_kernel<1>, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, x, n, h, w, c, r, y);
     MPG_LAUNCH_CHECK("space_to_depth_kernel");
 }

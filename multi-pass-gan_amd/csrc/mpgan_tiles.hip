@@ -5,12 +5,11 @@
 // All of it is HBM-bound gather work on small tiles; one thread per output element, channels fastest.
 // The random decisions (which frame, which offset, retries on the density test, augmentation parameters) stay on the
 // host in multi-pass-gan_amd/tiles_device.py so that the reference's random streams are consumed identically.
-#include "mpgan_internal.h"
+#include "mpgan_valu.h"
+
+using namespace mpg::valu;
 
 namespace {
-
-constexpr int BLK = 256;
-inline unsigned grid_for(size_t n) { return (unsigned)((n + BLK - 1) / BLK); }
 
 // one row per tile: frame, first channel, z0, y0, x0 (low-res or high-res offsets, as the caller computed them)
 __global__ void tile_gather_kernel(const float* __restrict__ frames, int Z, int Y, int X, int Cf, const int* __restrict__ table,

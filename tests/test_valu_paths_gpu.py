@@ -1,30 +1,31 @@
-"""Every dispatch branch of the vector-ALU kernels (mpgan_elem.hip, mpgan_train.hip) called directly and held against the
-plain references of tests/valu_ref.py (checked on the CPU by test_valu_ref_host.py).
+"""Every dispatch branch of the vector-ALU kernels (mpgan_elem.hip, mpgan_bn.hip, mpgan_train_conv.hip, mpgan_train_elem.hip)
+called directly and held against the plain references of tests/valu_ref.py (checked on the CPU by test_valu_ref_host.py).
 
 The host entry points choose a kernel by channel count, 16-byte pointer alignment, element count or a grid cap with a
 grid-stride loop.  The conditions are copied here; a case names the one it is there for in its id.  When a constant changes
-in the source, this table says which shapes have to move with it.
+in the source, this table says which shapes have to move with it.  ("chan_sum4", "apply4", "cutoff4", "space_to_depth4":
+the V = 4 instantiation of chan_sum_kernel, bn_apply_kernel, cutoff_kernel, space_to_depth_kernel.)
 
-  constant                  value   source                        cases that cross it
-  BLK                       256     mpgan_elem.hip:10, mpgan_train.hip:10
-  chan_sum4 condition       c >= 16, c % 4 == 0, 16-byte pointers     mpgan_train.hip:290   BN_SHAPES ("chan_sum4" / "scalar")
-  chan_sum4 block cap       512     mpgan_train.hip:296           (66001, 128): ppi 8 -> 516 blocks asked
-  chan_sum block cap        1024    mpgan_train.hip:309           (530001, 5): ppi 32 -> 1036 blocks asked
-  CHAN_SUM_MAX_BLOCKS       1024    mpgan_train.hip:317
-  chan_sum4 unroll          8 pixels in flight (MODE 0, 3), 4 (MODE 2)   mpgan_train.hip:257   (4099, 32): 456 pixels a block, ppi 32
-  sum_partials 8-deep loop  nblocks > 7 * 16 = 112    mpgan_train.hip:336           both capped cases
-  BN4_CMAX                  512     mpgan_train.hip:368, :996     (300, 516), (64, 1028) take bn_apply_kernel
-  lanes cap                 256 channel quads a block  mpgan_train.hip:292  (64, 1028): 257 quads, two channel blocks
-  BN_SHIFT_PIX              64 pixels, every pixel when npix < 64   mpgan_train.hip:170   npix 1, 5, 7, 37: fewer than 64
-  AMAX_GRID                 2048    mpgan_train.hip:410, :1028, :1044   bn_bwd: npix * c > 524288; act_bwd: n > 2097152
-  act_bwd float4 body       16-byte dy, y, dx; tail n % 4   mpgan_train.hip:459-466
-  pair_reduce cap           1024 blocks of 8 * BLK    mpgan_train.hip:1116-1117      n = 2100003 asks 1026
-  channel_gather cap        16384 blocks  mpgan_elem.hip:819      1050000 * 5 > 16384 * 256
-  cutoff4                   n >= 1024, 16-byte pointers; tail n % 4   mpgan_elem.hip:827-832
-  transpose_tiled4          c == 1, perm[2] != 2, extents % 4 == 0, 16-byte pointers, 64 x 64 tiles   mpgan_elem.hip:754-755
-  swap01_rows               perm (1, 0, 2), d2 % 4 == 0, 16-byte pointers   mpgan_elem.hip:768-769
-  space_to_depth4           c % 4 == 0, 16-byte x and y   mpgan_elem.hip:868
-  bn_infer / bwd2 float4    c % 4 == 0, 16-byte pointers  mpgan_train.hip:1503, :1718
+  constant                  value   source (file: constant or function)          cases that cross it
+  BLK                       256     mpgan_valu.h: BLK
+  chan_sum4 condition       c >= 16, c % 4 == 0, 16-byte pointers     mpgan_bn.hip: launch_chan_sum   BN_SHAPES ("chan_sum4" / "scalar")
+  chan_sum4 block cap       512     mpgan_bn.hip: launch_chan_sum (mpgan_valu.h: split_pixels)   (66001, 128): ppi 8 -> 516 blocks asked
+  chan_sum block cap        1024    mpgan_bn.hip: launch_chan_sum, CHAN_SUM_MAX_BLOCKS           (530001, 5): ppi 32 -> 1036 blocks asked
+  CHAN_SUM_MAX_BLOCKS       1024    mpgan_bn.hip: CHAN_SUM_MAX_BLOCKS
+  chan_sum4 unroll          8 pixels in flight (MODE 0, 3), 4 (MODE 2)   mpgan_bn.hip: chan_sum_kernel, UN   (4099, 32): 456 pixels a block, ppi 32
+  sum_partials 8-deep loop  nblocks > 7 * 16 = 112    mpgan_valu.h: ordered_partials_sum           both capped cases
+  BN4_CMAX                  512     mpgan_valu.h: BN4_CMAX; mpgan_bn.hip: launch_bn_apply     (300, 516), (64, 1028) take bn_apply_kernel<1>
+  lanes cap                 256 channel quads a block  mpgan_valu.h: split_pixels  (64, 1028): 257 quads, two channel blocks
+  BN_SHIFT_PIX              64 pixels, every pixel when npix < 64   mpgan_bn.hip: BN_SHIFT_PIX   npix 1, 5, 7, 37: fewer than 64
+  AMAX_GRID                 2048    mpgan_valu.h: AMAX_GRID; mpgan_bn.hip: mpg_bn_train_bwd_ordered; mpgan_train_elem.hip: mpg_act_bwd   bn_bwd: npix * c > 524288; act_bwd: n > 2097152
+  act_bwd float4 body       16-byte dy, y, dx; tail n % 4   mpgan_train_elem.hip: act_bwd_kernel
+  pair_reduce cap           1024 blocks of 8 * BLK    mpgan_train_elem.hip: mpg_pair_reduce      n = 2100003 asks 1026
+  channel_gather cap        16384 blocks  mpgan_elem.hip: mpg_channel_gather      1050000 * 5 > 16384 * 256
+  cutoff4                   n >= 1024, 16-byte pointers; tail n % 4   mpgan_elem.hip: mpg_cutoff
+  transpose_tiled4          c == 1, perm[2] != 2, extents % 4 == 0, 16-byte pointers, 64 x 64 tiles   mpgan_elem.hip: mpg_volume_transpose
+  swap01_rows               perm (1, 0, 2), d2 % 4 == 0, 16-byte pointers   mpgan_elem.hip: mpg_volume_transpose
+  space_to_depth4           c % 4 == 0, 16-byte x and y   mpgan_elem.hip: mpg_space_to_depth
+  bn_infer / bwd2 float4    c % 4 == 0, 16-byte pointers  mpgan_bn.hip: mpg_bn_train_bwd2_ordered, mpg_bn_infer_act
 
 Tolerances are the project's: 1e-5 relative L2 for fp32 kernels whose accumulation order differs (tests/test_train_gpu.py),
 1e-4 on the variance (test_conv_layer_fn), 1e-6 for elementwise kernels and the ordered channel sum, exact where a kernel

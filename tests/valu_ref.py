@@ -1,4 +1,4 @@
-"""Plain references for the vector-ALU kernels (mpgan_elem.hip, mpgan_train.hip): numpy / torch-CPU restatements of the
+"""Plain references for the vector-ALU kernels (mpgan_elem.hip, mpgan_bn.hip, mpgan_train_*.hip): numpy / torch-CPU restatements of the
 formulas in include/mpgan.h, written from the header and not from the kernels.  No GPU imports: test_valu_ref_host.py
 checks them on the CPU (float64 autograd, numpy.transpose), test_valu_paths_gpu.py holds the kernels against them."""
 import numpy as np
