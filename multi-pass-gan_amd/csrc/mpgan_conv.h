@@ -118,7 +118,8 @@ struct Pipe {
 
 template <int NT>
 struct Pipe6 {
-    static constexpr int WAVES = (NT == 1) ? 4 : 8;
+    static constexpr int WAVES = 8;
+    static constexpr int OCC = (NT == 1) ? 4 : 2;          // waves per SIMD the kernel is compiled for (256 or 128 registers)
     static constexpr int PT = 16 / WAVES;                  // tile rows per wave
     static constexpr int TH = 16;
     static constexpr int KS = 4;                           // fp16 k-steps per stage: 8 tap slots

@@ -15,8 +15,8 @@
 // corrections (the fixed exponents of the fp8 flavour lost them outside |v| in 1e-2..112).
 // Weights: bf6 planes packed per stage with one E8M0 byte per (output channel, K block of 32) and plane.
 //
-// One workgroup = WAVES waves = 16 tile rows x 32 pixels; a weight stage is one macro-step of 8 tap slots
-// (K = 64): [4 fp16 k-steps][w_hi6][w_lo6].  The slots of a segment form one stream over its channel groups
+// One workgroup = 8 waves = 16 tile rows x 32 pixels, two tile rows per wave; a weight stage is one macro-step of 8 tap
+// slots (K = 64): [4 fp16 k-steps][w_hi6][w_lo6].  The slots of a segment form one stream over its channel groups
 // (slot = group * tp + tap), so a stage may end one group and begin the next; every group has its own LDS image.
 // ---------------------------------------------------------------------------------------------
 #include "mpgan_conv.h"
@@ -160,14 +160,19 @@ __device__ __forceinline__ v8i bf6_of(const half32& v, int e8m0) {
 }
 constexpr int BF6 = 3;     // cbsz / blgp code of e3m2
 
+// Two blocks share a CU.  With two to four cout tiles the 64 to 128 accumulator registers of a wave leave room for two waves
+// per SIMD; with ONE cout tile a wave has 32, and the kernel is compiled for 128 registers (Pipe6<1>::OCC = 4): four waves
+// per SIMD, so that the in-order chain of a wave's stage (fragment reads, fp16 MFMAs, block maxima and conversions, a_lo
+// reads, bf6 MFMAs, barrier) runs under the MFMAs of three other waves instead of one.
 template <int NT>
-__global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, 2) void conv_mfma_f6_kernel(const ConvArgs a_unused) {
+__global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mfma_f6_kernel(const ConvArgs a_unused) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const KArgs ap = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
     const auto& a = *ap;
     using P = Pipe6<NT>;
     constexpr int WAVES = P::WAVES, PT = P::PT, TH = P::TH, WF16 = P::WF16, WF6 = P::WF6, WSTAGE = P::WSTAGE;
     constexpr int NI = P::NI, R = P::R, D = P::D, THREADS = WAVES * 64;
+    constexpr bool FLAT = NT == 1;      // the 128-register kernel: one tile row at a time in the direct path, no if / else below
 
     int* tap16 = reinterpret_cast<int*>(smem);
     char* img_lds = smem + a.tap_bytes;
@@ -237,9 +242,68 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, 2) void conv_mfma_f6_kernel(
                 const char* wb = w_lds + (st % R) * WSTAGE;
                 const char* xs = xb + (size_t)st * 8 * gstride;   // uniform: first group of this macro-step
                 const int grem = glast - st * 8;
-                // one (four tile rows per wave) or two tile rows at a time: all 32 operand fragments of a macro-step would not
-                // fit next to the accumulators (the weights are re-read from LDS for every part)
-                constexpr int PH = PT == 4 ? 1 : 2;
+                if constexpr (FLAT) {
+                    // One tile row at a time, on the explicit reads and counted waits of the image path: the weight fragments
+                    // of a row are read again for the next one and live in eight registers, both planes of a pixel share
+                    // the lane's offset.  LDS reads in order: A(0) A(1) | A(2) | A(3) | w_lo6 | w_hi6, each group behind
+                    // the MFMA that frees its registers.
+                    const unsigned a_base = lds_off(wb) + (unsigned)lane * 16u;
+                    // (opaque, so that they stay the scalar bases of the loads: folded into the lanes' offsets they would
+                    // cost a 64-bit address per load)
+                    const char* xs_hi = xs;
+                    const char* xs_lo = xs + plane_bytes;
+                    asm volatile("" : "+s"(xs_hi), "+s"(xs_lo));
+                    static_for<0, PT>([&](auto qc) {
+                        constexpr int q = decltype(qc)::value;
+                        half8 b_hi[4], b_lo[4], aq[2];
+                        v4i wl[2], wh[2];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            int g = 2 * j + hh;
+                            g = g < grem ? g : grem;                 // groups past the segment: zero weights
+                            const unsigned vo = pixo[q] + g * gstride;
+                            typedef const __attribute__((address_space(1))) half8* gmem;     // (the asm hid where they point)
+                            b_hi[j] = __builtin_nontemporal_load((gmem)(xs_hi + vo));   // read once
+                            b_lo[j] = __builtin_nontemporal_load((gmem)(xs_lo + vo));
+                        }
+                        ds_read16<0>(aq[0], a_base);
+                        ds_read16<1024>(aq[1], a_base);
+                        static_for<0, 4>([&](auto jc) {
+                            constexpr int j = decltype(jc)::value;
+                            lgkm_wait<(j < 3 ? 1 : 2)>();           // behind A(j): A(j + 1), or the two halves of w_lo6
+                            tie(aq[j & 1]);
+                            acc[q][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq[j & 1], b_hi[j], acc[q][0], 0, 0, 0);
+                            if constexpr (j < 2) {
+                                ds_read16<(j + 2) * 1024>(aq[j & 1], a_base);
+                            } else if constexpr (j == 2) {
+                                ds_read16<WF16 + WF6>(wl[0], a_base);
+                                ds_read16<WF16 + WF6 + 1024>(wl[1], a_base);
+                            } else {
+                                ds_read16<WF16>(wh[0], a_base);
+                                ds_read16<WF16 + 1024>(wh[1], a_base);
+                            }
+                        });
+                        const half32 bh = cat32(b_hi[0], b_hi[1], b_hi[2], b_hi[3]);
+                        const int e = block_exp16(bh);
+                        const v8i hi6 = bf6_of(bh, e + 109);
+                        const v8i lo6 = bf6_of(cat32(b_lo[0], b_lo[1], b_lo[2], b_lo[3]), e + 97);
+                        const int sb = (e + 109) | (e + 97) << 8;
+                        lgkm_wait<2>();
+                        tie(wl[0]);
+                        tie(wl[1]);
+                        const v8i w_lo = __builtin_shufflevector(wl[0], wl[1], 0, 1, 2, 3, 4, 5, 6, 7);
+                        acc[q][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w_lo, hi6, acc[q][0], BF6, BF6, 1, w_lo[6], 0, sb);
+                        lgkm_wait<0>();
+                        tie(wh[0]);
+                        tie(wh[1]);
+                        const v8i w_hi = __builtin_shufflevector(wh[0], wh[1], 0, 1, 2, 3, 4, 5, 6, 7);
+                        acc[q][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(w_hi, lo6, acc[q][0], BF6, BF6, 0, w_hi[6], 1, sb);
+                    });
+                    continue;
+                }
+                // two tile rows at a time: all 32 operand fragments of a macro-step would not fit next to the accumulators
+                // (the weights are re-read from LDS for every part)
+                constexpr int PH = 2;
                 static_for<0, PT / PH>([&](auto hc) {
                     constexpr int p0 = decltype(hc)::value * PH;
                     half8 b_hi[4][PH], b_lo[4][PH];
@@ -288,7 +352,13 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, 2) void conv_mfma_f6_kernel(
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            continue;
+            if constexpr (!FLAT) continue;
+        }
+        // FLAT: two `if`s in a row, the second on a value the compiler cannot tell from the first.  As the two arms of ONE
+        // branch the accumulators that enter the segment stay allocated next to the ones the direct loop works on (the
+        // arm that does not run hands them on): 32 registers the 128 do not have.
+        if constexpr (FLAT) {
+            if (__builtin_amdgcn_readfirstlane(sg.direct)) continue;
         }
         // K is ONE stream of tap slots over the channel groups of the segment: slot q = (group q / tp, tap q % tp),
         // eight slots per weight stage, so a stage may finish one group and start the next (25 taps x 16 groups =
@@ -323,7 +393,8 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, 2) void conv_mfma_f6_kernel(
         // Every group's image has the same per-lane source offsets (only the group's base address differs): they are
         // worked out once per segment, so that inside the stage loop an image piece costs a select and one DMA
         // instruction.  -1: the pixel lies outside the image (or past the halo rows): it is fetched from the zero page.
-        constexpr int MAXI = (WAVES == 8) ? 4 : 7;       // pieces per wave and image: 2 planes x <= 14 KiB over WAVES waves
+        constexpr int MAXI = 4;                          // pieces per wave and image: 2 planes x <= 14 KiB over 8 waves
+        static_assert(WAVES == 8, "MAXI");
         int img_src[MAXI];
 #pragma unroll
         for (int i = 0; i < MAXI; ++i) {

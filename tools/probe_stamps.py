@@ -1,6 +1,7 @@
 """diagnostic: per-phase cycle sums of the F16F6 K loop (library built with -DMPG_STAMPS=1, MPGAN_LIB_OVERRIDE), b1.B and
 b2.A, one launch each: per wave and stage, s_memtime cycles from the barrier release to the first satisfied fragment wait,
-through the fp16 groups, through the correction steps, and waiting at the next barrier"""
+through the fp16 groups, through the correction steps, and waiting at the next barrier.  argv[1]: waves per block of the
+one-cout-tile kernel of the library under test (8; 4 before round 5)"""
 import os
 import sys
 import numpy as np, torch
@@ -9,7 +10,8 @@ import mpgan_amd
 from mpgan_amd import ops
 dev = "cuda:0"
 N, H = 8, 256
-for name, cin, cout, waves in (("b1.B 128->128", 128, 128, 8), ("b2.A 128->32", 128, 32, 4), ("96->96 3x3", 96, 96, 8)):
+W1 = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+for name, cin, cout, waves in (("b1.B 128->128", 128, 128, 8), ("b2.A 128->32", 128, 32, W1), ("96->96 3x3", 96, 96, 8)):
     k = 3 if "3x3" in name else 5
     g = torch.Generator(device=dev).manual_seed(1)
     x = torch.randn((N, H, H, cin), device=dev, generator=g).relu_()
