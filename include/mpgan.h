@@ -145,6 +145,19 @@ int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* desc);
  * MPG_ERR_ARG, and the caller runs mpg_conv2d_fused and mpg_depth_to_space. */
 int mpg_conv2d_fused_d2s(mpg_stream_t stream, const mpg_conv_desc* desc, int r, int c_total, int co_off);
 
+/* Convolutions wider than 128 outputs (the first growing level of the 8x generators at the driver's own defaults,
+ * startFms 512 / maxFms 256: RES(256,256), GAN/multipassGAN-8x.py; Session._match_fused, ops.conv2d_fused_wide):
+ * the launch mpg_conv2d_fused(desc) would run, desc->cout in 1..128, with its outputs stored as channels
+ * [co_off, co_off + cout) of tensors that have c_total channels: desc->y is fp32 [N,H,W,c_total], desc->y_g8 a G8
+ * tensor of ceil(c_total/8) groups, both given by their base address.  Nothing outside the window is written, so the
+ * windows of a wide layer are launches into the same tensors, in any order.  Every precision.  post_add is allowed
+ * (post_add_coff addresses its window); pixel_norm is not (MPG_ERR_ARG): a window does not hold all channels of a
+ * pixel, see mpg_pixel_norm_g8.  co_off + cout <= c_total.  A G8 output needs co_off % 8 == 0, and cout % 8 == 0
+ * unless the window ends the tensor: the last group is then zero padded like that of a plain G8 output; a ragged
+ * window anywhere else is MPG_ERR_ARG.  The launch stays on the matrix-core kernels whatever its width (the
+ * small-channel kernel writes whole tensors only). */
+int mpg_conv2d_fused_window(mpg_stream_t stream, const mpg_conv_desc* desc, int c_total, int co_off);
+
 /* A whole residual block whose three convolutions have <= 8 channels on either side, as ONE launch:
  *     y = act_b( conv_b( act_a( conv_a(up(x)) + bias_a ) ) + conv_s(up(x)) + bias_b )
  * (resBlock 0 and 3 of gen_resnet, 1 -> 2 -> 8 and 8 -> 2 -> 1 channels: GAN/multipassGAN-4x.py:505-526,560,564).
@@ -215,6 +228,11 @@ int mpg_max_pool_bwd(mpg_stream_t stream, const float* dy, const unsigned char* 
 int mpg_avg_pool2(mpg_stream_t stream, const float* x, int n, int h, int w, int c, float* y);
 /* GAN.pixel_norm standalone (GAN.py:472-474) */
 int mpg_pixel_norm(mpg_stream_t stream, const float* x, size_t npix, int c, float eps, float* y);
+/* GAN.pixel_norm of a G8 tensor (MPG_G8_F16, c <= 512 channels) in place, behind the window launches of a wide layer
+ * (ops.conv2d_fused_wide): x = hi + lo, y = x * rsqrt(mean_c(x^2) + eps) accumulated in fp32, written back as hi / lo
+ * planes and, when y is not NULL, as fp32 NHWC [n,h,w,c] too.  The padding channels of the last group do not enter
+ * the mean (the divisor is c) and stay zero. */
+int mpg_pixel_norm_g8(mpg_stream_t stream, void* g8, int n, int h, int w, int c, float eps, float* y);
 /* GAN.minibatch_stddev_layer (GAN.py:476-488): y[n,h,w,c+1] = concat(x, s[n % M]) with s[m] the mean over
  * (h,w,c) of the standard deviation over the G = min(group_size, n) members {g*M + m} of group m, M = n / G.
  * stat: M floats of scratch. */

@@ -111,6 +111,7 @@ PROTOTYPES = {
     "mpg_conv_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _Z]),
     "mpg_conv2d_fused": (_I, [_P, ctypes.POINTER(ConvDesc)]),
     "mpg_conv2d_fused_d2s": (_I, [_P, ctypes.POINTER(ConvDesc), _I, _I, _I]),
+    "mpg_conv2d_fused_window": (_I, [_P, ctypes.POINTER(ConvDesc), _I, _I]),
     "mpg_conv2d_small_pair": (_I, [_P, ctypes.POINTER(SmallPairDesc)]),
     "mpg_conv2d_direct": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P, _I, _F, _P]),
     "mpg_resize_nearest": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
@@ -120,6 +121,7 @@ PROTOTYPES = {
     "mpg_max_pool": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mpg_max_pool_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mpg_pixel_norm": (_I, [_P, _P, _Z, _I, _F, _P]),
+    "mpg_pixel_norm_g8": (_I, [_P, _P, _I, _I, _I, _I, _F, _P]),
     "mpg_minibatch_stddev": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mpg_minibatch_stddev_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mpg_minibatch_stddev_bwd2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z]),

@@ -56,8 +56,13 @@ struct ConvArgs {
     float pn_eps;
     const float* post_add;
     int pa_stride, pa_coff;
-    float* y;             // fp32 NHWC output or null
-    char* y_g8;           // G8 output (planes hi16, lo16) or null
+    // The outputs may be a channel window of wider tensors (mpg_conv2d_fused_window): the host folds the window's first
+    // channel into y and y_g8, and what the stores still need of the whole tensor are these two strides (cout and
+    // ceil(cout / 8) in a launch of mpg_conv2d_fused).  Kernel arguments like the rest: they stay in SGPRs.
+    int y_stride;         // floats per pixel of the fp32 output
+    int cg_img;           // channel groups per image of the G8 output
+    float* y;             // fp32 NHWC output or null (channel 0 of the launch)
+    char* y_g8;           // G8 output (planes hi16, lo16) or null (group 0 of the launch)
     const float* in_amax; // inputs were multiplied by pow2_scale(*in_amax): the accumulators are divided by it
     const char* zeros;    // >= 16 zero bytes (source of out-of-image pixels)
     int img_bytes;        // bytes of one LDS image buffer (max over segments)
@@ -302,7 +307,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                                 plane_out = 4 * plane_px;
                                 dst = a.y_g8 + ((((size_t)n * dp->cg + (q.cc >> 3)) * 2) * plane_out + q.pix) * 16;
                             } else {
-                                dst = a.y_g8 + ((((size_t)n * cg_out + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
+                                dst = a.y_g8 + ((((size_t)n * a.cg_img + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
                             }
                             half8 hi, lo;
 #pragma unroll
@@ -377,18 +382,21 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                     }
                 }
             } else if (a.y != nullptr) {
-                float* dst = a.y + pix0 * a.cout;
+                // runs of cout channels per pixel, y_stride floats apart (one run of npx * cout where the launch owns the
+                // whole tensor); float4 when every run starts and ends on 16 bytes
+                float* dst = a.y + pix0 * a.y_stride;
                 const int total = npx * a.cout;
-                if ((a.cout & 3) == 0) {
+                if (((a.cout | a.y_stride) & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & 15) == 0) {
                     for (int f = lane * 4; f < total; f += 256) {
                         const int p = f / a.cout;
                         const int c = f - p * a.cout;
-                        *reinterpret_cast<float4*>(dst + f) = *reinterpret_cast<const float4*>(stg + p * ROWF + c);
+                        *reinterpret_cast<float4*>(dst + p * a.y_stride + c) = *reinterpret_cast<const float4*>(stg + p * ROWF + c);
                     }
                 } else {
                     for (int f = lane; f < total; f += 64) {
                         const int p = f / a.cout;
-                        dst[f] = stg[p * ROWF + (f - p * a.cout)];
+                        const int c = f - p * a.cout;
+                        dst[p * a.y_stride + c] = stg[p * ROWF + c];
                     }
                 }
             }
@@ -408,7 +416,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[PT][NT], const KArgs
                             plane_out = 4 * plane_px;
                             dst = a.y_g8 + ((((size_t)n * dp->cg + (q.cc >> 3)) * 2) * plane_out + q.pix) * 16;
                         } else {
-                            dst = a.y_g8 + ((((size_t)n * cg_out + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
+                            dst = a.y_g8 + ((((size_t)n * a.cg_img + cg) * 2) * plane_px + (size_t)py * a.w + x0 + r) * 16;
                         }
                         half8 hi, lo;
 #pragma unroll

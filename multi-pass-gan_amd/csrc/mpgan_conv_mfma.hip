@@ -1,5 +1,5 @@
 // Host side of the fused convolution (mpgan_conv.h): how a launch is cut into segments, chunks and weight stages, its LDS
-// plan, and the two entry points.  No kernels here: they live in mpgan_conv_f16.hip, mpgan_conv_f6.hip and
+// plan, and the three entry points.  No kernels here: they live in mpgan_conv_f16.hip, mpgan_conv_f6.hip and
 // mpgan_conv_small.hip, each behind its launch function.
 #include "mpgan_conv.h"
 
@@ -80,6 +80,12 @@ struct D2SOut {
     int cs, coff;
 };
 
+// the channel window [co_off, co_off + cout) of c_total-channel outputs (mpg_conv2d_fused_window); mpg_conv2d_fused is
+// the window {cout, 0}
+struct WinOut {
+    int c_total, co_off;
+};
+
 }  // namespace
 
 const Shape& mpg::conv::pipe_shape(int nt, int prec) { return SHAPES[prec - 1][nt - 1]; }
@@ -126,8 +132,9 @@ int mpg::conv::check_segment(const mpg_conv_desc* d, int s) {
     return MPG_OK;
 }
 
-// conv_mfma_kernel / conv_mfma_f6_kernel; d2s: the depth-to-space store of mpg_conv2d_fused_d2s
-static int launch_mfma(hipStream_t stream, const mpg_conv_desc* d, const D2SOut* d2s) {
+// conv_mfma_kernel / conv_mfma_f6_kernel; d2s: the depth-to-space store of mpg_conv2d_fused_d2s; win: where the outputs
+// lie in their tensors
+static int launch_mfma(hipStream_t stream, const mpg_conv_desc* d, const D2SOut* d2s, const WinOut& win) {
     const int nt = (d->cout + 31) / 32;
     const Shape& ps = pipe_shape(nt, d->prec);
     ConvArgs a;
@@ -160,8 +167,11 @@ static int launch_mfma(hipStream_t stream, const mpg_conv_desc* d, const D2SOut*
     a.bias = d->bias; a.in_amax = d->in_amax; a.act = d->act; a.leak = d->leak; a.pn = d->pixel_norm; a.pn_eps = d->pn_eps;
     a.post_add = d->post_add; a.pa_stride = d->post_add_stride; a.pa_coff = d->post_add_coff;
     MPG_REQUIRE(!d->post_add || d->post_add_coff + d->cout <= d->post_add_stride, "mpg_conv2d_fused: post_add channel range");
-    a.y = d->y;
-    a.y_g8 = (char*)d->y_g8;
+    // the window's first channel goes into the two pointers; the kernels keep the strides of the whole tensors
+    a.y_stride = win.c_total;
+    a.cg_img = (win.c_total + 7) / 8;
+    a.y = d->y != nullptr ? d->y + win.co_off : nullptr;
+    a.y_g8 = d->y_g8 != nullptr ? (char*)d->y_g8 + (size_t)(win.co_off / 8) * 2 * d->h * d->w * 16 : nullptr;
     MPG_REQUIRE((((uintptr_t)d->y) & 15) == 0 && (((uintptr_t)d->y_g8) & 15) == 0,
                 "mpg_conv2d_fused: misaligned output");
     a.zeros = mpg::zero_page();
@@ -193,7 +203,7 @@ static int launch_mfma(hipStream_t stream, const mpg_conv_desc* d, const D2SOut*
     MPG_LAUNCH_CHECK("conv_mfma_kernel");
 }
 
-static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOut* d2s) {
+static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOut* d2s, const WinOut* window = nullptr) {
     MPG_REQUIRE(d != nullptr, "mpg_conv2d_fused: null desc");
     MPG_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1, "mpg_conv2d_fused: bad shape %d x %d x %d", d->n, d->h, d->w);
     MPG_REQUIRE(d->cout >= 1 && d->cout <= 128, "mpg_conv2d_fused: cout %d not in 1..128", d->cout);
@@ -203,9 +213,12 @@ static int conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d, const D2SOu
                 "mpg_conv2d_fused: bad prec %d", d->prec);
     MPG_REQUIRE(d->act >= MPG_ACT_NONE && d->act <= MPG_ACT_TANH, "mpg_conv2d_fused: bad act %d", d->act);
     // (the depth-to-space store is an epilogue of the MFMA kernels only: such a launch stays on them)
-    bool small = d->cout <= 8 && !d->pixel_norm && d->post_add == nullptr && d->reserved == 0 && d2s == nullptr;
+    // (a window store likewise: conv_small_kernel writes whole tensors, and callers cut wide layers so that no window is
+    // that narrow, ops.wide_chunks)
+    bool small = d->cout <= 8 && !d->pixel_norm && d->post_add == nullptr && d->reserved == 0 && d2s == nullptr && window == nullptr;
     for (int s = 0; s < d->nseg && small; ++s) small = d->seg[s].cin <= 8;
-    return small ? launch_small((hipStream_t)stream, d) : launch_mfma((hipStream_t)stream, d, d2s);
+    const WinOut whole = {d->cout, 0};
+    return small ? launch_small((hipStream_t)stream, d) : launch_mfma((hipStream_t)stream, d, d2s, window != nullptr ? *window : whole);
 }
 
 extern "C" int mpg_conv2d_fused(mpg_stream_t stream, const mpg_conv_desc* d) {
@@ -233,4 +246,19 @@ extern "C" int mpg_conv2d_fused_d2s(mpg_stream_t stream, const mpg_conv_desc* d,
     MPG_REQUIRE((size_t)4 * d->h * d->w < ((size_t)1 << 31), "mpg_conv2d_fused_d2s: %dx%d too large", d->h, d->w);
     const D2SOut o = {cs, co_off};
     return conv2d_fused(stream, d, &o);
+}
+
+extern "C" int mpg_conv2d_fused_window(mpg_stream_t stream, const mpg_conv_desc* d, int c_total, int co_off) {
+    MPG_REQUIRE(d != nullptr, "mpg_conv2d_fused_window: null desc");
+    MPG_REQUIRE(c_total >= 1 && co_off >= 0 && d->cout >= 1 && co_off + d->cout <= c_total,
+                "mpg_conv2d_fused_window: channels [%d, %d) outside 0..%d", co_off, co_off + d->cout, c_total);
+    // the pixel norm of the whole tensor is mpg_pixel_norm_g8 behind the last window
+    MPG_REQUIRE(!d->pixel_norm, "mpg_conv2d_fused_window: no pixel norm (a window does not hold the pixel's channels)");
+    // a group of 8 channels belongs to one window; only the tensor's last group may be ragged (zero padded, like the
+    // last group of a plain G8 output)
+    MPG_REQUIRE(d->y_g8 == nullptr || (co_off % 8 == 0 && (d->cout % 8 == 0 || co_off + d->cout == c_total)),
+                "mpg_conv2d_fused_window: G8 output needs co_off (%d) a multiple of 8, and cout (%d) too unless the window ends the tensor",
+                co_off, d->cout);
+    const WinOut o = {c_total, co_off};
+    return conv2d_fused(stream, d, nullptr, &o);
 }

@@ -1,5 +1,5 @@
 // fp32 NHWC <-> G8 ([N][ceil(C/8)][2 planes: hi, lo][H][W][8 x fp16], value = hi + lo), the tensor layout of the fused
-// convolutions and the weight gradient.
+// convolutions and the weight gradient; and the pixel norm of a G8 tensor wider than one fused launch (mpg_pixel_norm_g8).
 #include "mpgan_internal.h"
 #include "mpgan_mfma_dev.h"
 
@@ -103,6 +103,86 @@ __global__ void g8_to_f32_kernel(const _Float16* __restrict__ g, int n, int h, i
     y[idx] = (float)src[0] + (float)src[plane_px * 8];
 }
 
+// GAN.pixel_norm (GAN.py:472-474) of a G8 tensor in place: y = x * rsqrt(mean_c(x^2) + eps) with x = hi + lo, written
+// back as hi / lo planes and, when y32 is given, as fp32 NHWC too.  The fused epilogue does this for up to 128 channels
+// inside the launch; a wider layer is several window launches (mpg_conv2d_fused_window) and this pass behind them.
+// A block takes 64 consecutive pixels of one image; wave s of its S waves takes the channel groups s, s + S, ... (at
+// most PN_GPT of them: c <= 64 S), so a wave's 64 lanes read 1 KiB of consecutive 16-byte pixels of a group plane per
+// access and every value is read from memory once and kept in registers until it is scaled.  The S partial sums of a
+// pixel meet in LDS and are added in the same order by every wave.  Channels beyond c (padding of the last group) are
+// taken as zero and written as zero.
+constexpr int PN_PX = 64, PN_GPT = 8;
+
+template <int S>
+__global__ __launch_bounds__(PN_PX * S) void pixel_norm_g8_kernel(_Float16* __restrict__ g, int h, int w, int c, float eps,
+                                                                  float* __restrict__ y32) {
+    __shared__ float part[S][PN_PX];
+    const int cg_n = (c + 7) >> 3;
+    const size_t plane_px = (size_t)h * w;
+    const int lane = threadIdx.x & (PN_PX - 1), slice = threadIdx.x / PN_PX;
+    const size_t px = (size_t)blockIdx.x * PN_PX + lane;
+    const int b = blockIdx.y;
+    const bool ok = px < plane_px;
+    float v[PN_GPT][8];
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < PN_GPT; ++k) {
+        const int cg = slice + k * S;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[k][j] = 0.f;
+        if (ok && cg < cg_n) {
+            const _Float16* src = g + ((((size_t)b * cg_n + cg) * 2) * plane_px + px) * 8;
+            const half8 hi = *reinterpret_cast<const half8*>(src);
+            const half8 lo = *reinterpret_cast<const half8*>(src + plane_px * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float x = (cg * 8 + j < c) ? (float)hi[j] + (float)lo[j] : 0.f;
+                v[k][j] = x;
+                ss = fmaf(x, x, ss);
+            }
+        }
+    }
+    part[slice][lane] = ss;
+    __syncthreads();
+    if (!ok) return;
+    float tot = 0.f;
+#pragma unroll
+    for (int s = 0; s < S; ++s) tot += part[s][lane];
+    const float sc = rsqrtf(tot / (float)c + eps);
+#pragma unroll
+    for (int k = 0; k < PN_GPT; ++k) {
+        const int cg = slice + k * S;
+        if (cg < cg_n) {
+            // lo is the rest behind the hi that is STORED: the compiler is kept from forming hi a second time for the
+            // subtraction (it folds the scaling into the conversion, v_fma_mixlo_f16, whose rounding of the product
+            // need not be that of v_cvt_pk_f16_f32 on the rounded product: a pair off by an fp16 ulp now and then)
+            half8 hi, lo;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                v[k][j] *= sc;
+                hi[j] = (_Float16)v[k][j];
+            }
+            asm volatile("" : "+v"(hi));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) lo[j] = (_Float16)(v[k][j] - (float)hi[j]);
+            _Float16* dst = g + ((((size_t)b * cg_n + cg) * 2) * plane_px + px) * 8;
+            *reinterpret_cast<half8*>(dst) = hi;
+            *reinterpret_cast<half8*>(dst + plane_px * 8) = lo;
+            if (y32 != nullptr) {
+                float* q = y32 + ((size_t)b * plane_px + px) * c + cg * 8;
+                if (cg * 8 + 8 <= c && (c & 3) == 0) {
+                    *reinterpret_cast<float4*>(q) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
+                    *reinterpret_cast<float4*>(q + 4) = make_float4(v[k][4], v[k][5], v[k][6], v[k][7]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (cg * 8 + j < c) q[j] = v[k][j];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" size_t mpg_g8_bytes(int n, int h, int w, int c) {
@@ -139,4 +219,20 @@ extern "C" int mpg_g8_to_f32(mpg_stream_t stream, const void* g8, int n, int h, 
     hipLaunchKernelGGL(g8_to_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const _Float16*)g8, n, h, w, c, y);
     MPG_LAUNCH_CHECK("g8_to_f32_kernel");
+}
+
+extern "C" int mpg_pixel_norm_g8(mpg_stream_t stream, void* g8, int n, int h, int w, int c, float eps, float* y) {
+    MPG_REQUIRE(g8 != nullptr, "mpg_pixel_norm_g8: null pointer");
+    MPG_REQUIRE(n >= 1 && n <= 65535 && h >= 1 && w >= 1 && c >= 1, "mpg_pixel_norm_g8: bad shape");
+    // a thread keeps PN_GPT groups of its pixel: 8 waves cover 64 groups
+    MPG_REQUIRE(c <= 8 * PN_GPT * 8, "mpg_pixel_norm_g8: %d channels (at most %d)", c, 8 * PN_GPT * 8);
+    MPG_REQUIRE((((uintptr_t)g8) & 15) == 0 && (((uintptr_t)y) & 15) == 0, "mpg_pixel_norm_g8: misaligned tensor");
+    const size_t blocks = ((size_t)h * w + PN_PX - 1) / PN_PX;
+    MPG_REQUIRE(blocks < ((size_t)1 << 31), "mpg_pixel_norm_g8: %dx%d too large", h, w);
+    const dim3 grid((unsigned)blocks, (unsigned)n);
+    if ((c + 7) / 8 <= 4 * PN_GPT)
+        hipLaunchKernelGGL(pixel_norm_g8_kernel<4>, grid, dim3(PN_PX * 4), 0, (hipStream_t)stream, (_Float16*)g8, h, w, c, eps, y);
+    else
+        hipLaunchKernelGGL(pixel_norm_g8_kernel<8>, grid, dim3(PN_PX * 8), 0, (hipStream_t)stream, (_Float16*)g8, h, w, c, eps, y);
+    MPG_LAUNCH_CHECK("pixel_norm_g8_kernel");
 }

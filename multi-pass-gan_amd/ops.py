@@ -278,6 +278,80 @@ def conv2d_fused_d2s(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, out
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
+WIDE_MAX_COUT = 512
+
+
+def wide_chunks(c_total):
+    """the output windows [(co_off, width), ...] a convolution of c_total > 128 outputs runs as: as few launches as 128
+    outputs each allow, of equal width rounded up to a G8 group.  No window is narrower than 57 channels (136 outputs run
+    as 72 + 64, not 128 + 8), so none falls to the small-channel kernel, which has no window store."""
+    k = -(-c_total // 128)
+    width = -(-c_total // (8 * k)) * 8
+    return [(co, min(width, c_total - co)) for co in range(0, c_total, width)]
+
+
+def pixel_norm_g8(g, eps=1e-8, want_f32=False, out=None):
+    """GAN.pixel_norm of the G8 tensor `g` in place (mpg_pixel_norm_g8); with want_f32 / out the fp32 NHWC result too,
+    which is returned (else g)"""
+    lib = _lib.load()
+    if g.flavour != G8_F16:
+        raise _lib.MpgError("pixel_norm_g8: only the fp16 hi/lo flavour")
+    y = None
+    if want_f32 or out is not None:
+        y, _, _ = _alloc_outputs((g.n, g.h, g.w, g.c), g.buf.device, True, False, out, "pixel_norm_g8")
+    _lib.check(lib.mpg_pixel_norm_g8(_stream(), _ptr(g.buf), g.n, g.h, g.w, g.c, eps, _ptr(y)), "mpg_pixel_norm_g8")
+    return y if y is not None else g
+
+
+def conv2d_fused_wide(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, pixel_norm=False, pn_eps=1e-8,
+                      post_add=None, post_add_coff=0, want_f32=True, want_g8=False, out=None):
+    """conv2d_fused for c_total > 128 output channels, given as output windows [(segments, co_off), ...] (each window's
+    weights packed for its own <= 128 output channels, see wide_chunks): one mpg_conv2d_fused_window launch per window
+    into the same tensors, with the bias sliced per window and post_add read at the window's channels.  The reference
+    applies the activation, then the pixel norm (GAN.py:472-474 behind the layer), which needs every channel of a pixel:
+    the windows then write G8 only (the working form, also when only fp32 is wanted) and mpg_pixel_norm_g8 runs last,
+    rewriting that tensor in place and writing the fp32 result.  Returns like conv2d_fused."""
+    lib = _lib.load()
+    if not chunks:
+        raise _lib.MpgError("conv2d_fused_wide: no chunks")
+    h, w = out_hw
+    segs0 = chunks[0][0]
+    n, dev = segs0[0].x.n, segs0[0].x.buf.device
+    co = 0
+    for segments, co_off in sorted(chunks, key=lambda ch: ch[1]):
+        if co_off != co:
+            break
+        co += segments[0].packed.cout
+    if co != c_total:
+        raise _lib.MpgError("conv2d_fused_wide: the chunks do not cover channels 0..%d once" % c_total)
+    if bias is not None:
+        bias = _dev(bias, "bias")
+        if bias.numel() != c_total:
+            raise _lib.MpgError("conv2d_fused_wide: bias has %d entries, expected %d" % (bias.numel(), c_total))
+    shape = (n, h, w, c_total)
+    if not (want_f32 or want_g8 or out is not None):
+        raise _lib.MpgError("conv2d_fused_wide: no output requested")
+    pa = None
+    if post_add is not None:
+        if pixel_norm:
+            raise _lib.MpgError("conv2d_fused_wide: post_add follows the pixel norm, which runs behind the window launches")
+        pa = _dev(post_add, "post_add")
+        if pa.dim() != 4 or tuple(pa.shape[:3]) != shape[:3] or post_add_coff + c_total > pa.shape[3]:
+            raise _lib.MpgError("conv2d_fused_wide: post_add %s does not match output" % (tuple(pa.shape),))
+    y, y8, outs = _alloc_outputs(shape, dev, want_f32, want_g8 or bool(pixel_norm), out, "conv2d_fused_wide")
+    for segments, co_off in chunks:
+        cw = segments[0].packed.cout
+        d = _conv_desc(segments, out_hw, bias[co_off:co_off + cw].contiguous() if bias is not None else None, act, leak)
+        if pa is not None:
+            d.post_add, d.post_add_stride, d.post_add_coff = pa.data_ptr(), pa.shape[3], post_add_coff + co_off
+        d.y, d.y_g8 = _ptr(None if pixel_norm else y), _ptr(y8)
+        _lib.check(lib.mpg_conv2d_fused_window(_stream(), ctypes.byref(d), c_total, co_off), "mpg_conv2d_fused_window")
+    if pixel_norm:
+        _lib.check(lib.mpg_pixel_norm_g8(_stream(), _ptr(y8.buf), n, h, w, c_total, pn_eps, _ptr(y)), "mpg_pixel_norm_g8")
+        outs = [o for o in (y, y8 if want_g8 else None) if o is not None]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
 def space_to_depth(x, r):
     """the adjoint of depth_to_space (mpg_space_to_depth): [N,H,W,C] -> [N,H/r,W/r,C*r^2]"""
     lib = _lib.load()

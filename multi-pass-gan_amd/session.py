@@ -11,7 +11,10 @@ Fusion rules (all arithmetic stays in the kernels of libmpgan_hip.so):
   * ``chain + tensor`` with a linear chain on one side is the epilogue post-add
     (addBicubicUpsample, multipassGAN-out.py:327-332);
   * ``depth_to_space(2)`` of a linear 1x1 convolution with 4C outputs, C % 8 == 0 (GAN.pixel_shuffle,
-    GAN.py:554-560), is one ``mpg_conv2d_fused_d2s`` launch per 128 outputs writing the shuffled tensor.
+    GAN.py:554-560), is one ``mpg_conv2d_fused_d2s`` launch per 128 outputs writing the shuffled tensor;
+  * a fused convolution of more than 128 outputs (the 256-wide first level of the 8x generators at the driver's
+    defaults) is one step of ``mpg_conv2d_fused_window`` launches into the same tensors, its pixel norm one
+    ``mpg_pixel_norm_g8`` pass behind them (``ops.conv2d_fused_wide``).
 Everything else falls back to one kernel per node.
 """
 import re
@@ -379,8 +382,11 @@ class Session(object):
 
     # ---- pattern matching -------------------------------------------------
     def _match_term(self, n, single_use):
-        """bn?(bias_add?(conv2d)) with stride 1, cout <= 128, k <= 7.  The root n may have any
-        number of consumers (the caller decides); every inner node must feed this chain only."""
+        """bn?(bias_add?(conv2d)) with stride 1, cout <= 512, k <= 7.  The root n may have any
+        number of consumers (the caller decides); every inner node must feed this chain only.
+        More than 128 outputs are several window launches (_match_fused); ops.WIDE_MAX_COUT = 512 is the widest layer the
+        reference can ask for: a level is min(startFms / 2^j, maxFms) wide (arch.level_fms), so startFms 512, the 8x
+        driver's default, bounds every level for any maxFms."""
         m = G.match_layer(n, single_use)
         if m is None:
             return None
@@ -388,7 +394,7 @@ class Session(object):
         if act is not None or (bn is not None and bn.attrs["training"]) or conv.attrs["stride"] != (1, 1):
             return None
         kh, kw, cin, cout = conv.inputs[1].shape
-        if cout > 128 or kh > 7 or kw > 7 or conv.inputs[1].op != "variable":
+        if cout > ops.WIDE_MAX_COUT or kh > 7 or kw > 7 or conv.inputs[1].op != "variable":
             return None
         return _Term(conv, bias, bn)
 
@@ -436,6 +442,10 @@ class Session(object):
         out_hw = (n.shape[1], n.shape[2])
 
         lead = terms[0].conv.inputs[1].attrs["var"]
+        if cout > 128:
+            if pn and post_add is not None:      # the post-add follows the pixel norm, which follows the last window
+                return None
+            return self._wide_step(n, deps, terms, segs, lead, cout, out_hw, act, leak, pn, pn_eps, post_add)
         prec = self._launch_prec(lead, cout, segs)
 
         emit = {"f32": True, "g8": False}
@@ -472,6 +482,38 @@ class Session(object):
                          for (src, c_off_src, up, term, w_off, cin) in segs],
         }
         return _Step(n, deps, run, info, emit, parts)
+
+    def _wide_step(self, n, deps, terms, segs, lead, cout, out_hw, act, leak, pn, pn_eps, post_add):
+        """the step of a fused convolution of more than 128 outputs: one window launch per entry of ops.wide_chunks, each
+        with its own precision and its own packed weights (output channels [co, co + cw) of every segment, the folded
+        batch-norm scale sliced with them), the pixel norm behind the last one (ops.conv2d_fused_wide)"""
+        chunks = ops.wide_chunks(cout)
+        precs = [self._launch_prec(lead, cw, segs) for _, cw in chunks]
+        emit = {"f32": True, "g8": False}
+
+        def run(env):
+            launches = []
+            for (co, cw), prec in zip(chunks, precs):
+                seg_objs = []
+                for (src, c_off_src, up, term, w_off, cin) in segs:
+                    pk = self._packed_chunk(term, w_off, cin, prec, co, cw)
+                    g8, off = self._g8(env, src, c_off_src, cin, ops.flavour_for(prec))
+                    seg_objs.append(ops.Segment(g8, pk, off, up))
+                launches.append((seg_objs, co))
+            pa = self._f32(env, post_add) if post_add is not None else None
+            return self._boxed(ops.conv2d_fused_wide(
+                launches, out_hw, cout, bias=self._bias_for(terms), act=act, leak=leak, pixel_norm=pn, pn_eps=pn_eps,
+                post_add=pa, want_f32=emit["f32"], want_g8=emit["g8"], out=self._dst(env, emit, n.shape)), emit)
+
+        info = {
+            "kind": "conv2d_fused", "cout": cout, "launches": len(chunks), "act": act, "pixel_norm": pn, "prec": precs[0],
+            "post_add": post_add.name if post_add is not None else None,
+            "post_add_id": post_add.id if post_add is not None else None,
+            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, up_log2=up, w_off=w_off,
+                              kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
+                         for (src, c_off_src, up, term, w_off, cin) in segs],
+        }
+        return _Step(n, deps, run, info, emit)
 
     def _launch_prec(self, lead, cout, segs):
         """the precision of a fused launch of `cout` outputs over segments `segs` whose leading weight is `lead`"""
@@ -647,12 +689,16 @@ class Session(object):
         return pk
 
     def _packed_chunk(self, term, w_off, cin, prec, co, cw):
-        """output channels [co, co + cw) of a wide convolution, packed as a launch of their own (no batch norm)"""
+        """output channels [co, co + cw) of a wide convolution, packed as a launch of their own, with those channels of
+        the folded batch-norm scale"""
         key = ("pack", term.conv.id, w_off, cin, prec, co, cw)
         pk = self._packed.get(key)
         if pk is None:
             w = self.vars.get(term.conv.inputs[1].attrs["var"])[..., co:co + cw].contiguous()
-            pk = ops.pack_conv_weights(w, wscale=term.conv.attrs["wscale"], c_off=w_off, cin=cin, prec=prec)
+            scale, _ = self._bn_scale_shift(term)
+            if scale is not None:
+                scale = scale[co:co + cw].contiguous()
+            pk = ops.pack_conv_weights(w, wscale=term.conv.attrs["wscale"], cout_scale=scale, c_off=w_off, cin=cin, prec=prec)
             self._packed[key] = pk
         return pk
 
@@ -744,7 +790,7 @@ class Session(object):
         raise G.GraphError("no HIP lowering for node %r (inputs %r)" % (n, n.inputs))
 
     def _match_direct(self, n, single_use):
-        """[act](bn?(bias_add?(conv2d | matmul))) on the vector-ALU kernel: strided convs, cout > 128, FC."""
+        """[act](bn?(bias_add?(conv2d | matmul))) on the vector-ALU kernel: strided convs, cout > 512, FC."""
         m = G.match_layer(n, single_use, ("conv2d", "matmul", "conv2d_transpose"))
         if m is None:
             return None
