@@ -10,6 +10,16 @@ reference (example_run_output.py:4-8):
   upsamplingMode 1, upsampledData 1 : slices along x          -> density_low_1x1_%04d.uni
   upsamplingMode 3, upsampledData 1 : slices along y          -> density_low_0x0_%04d.uni   (third network, :1121-1124)
 
+and the pipeline in which nothing is zoomed along z and the second network upsamples that axis itself
+(multipass.plane_pass_4x / upsample_pass_4x; :1105-1111, 1136-1142, 1162, 1166):
+
+  upsamplingMode 2, upsampleFirst 0 : the simSize slices along z       -> density_low_2x2x1_%04d.uni
+  upsamplingMode 0, upsampledData 1 : planes (y, z_low) along x        -> density_low_1x1x1_%04d.uni
+
+One deviation: the reference stamps dimZ = simSizeHigh on every file it writes (:1151-1154), also on the ``2x2x1`` one,
+which holds only simSize slices, and its own reader cannot reshape such a file.  Here the header's dimZ is the number
+of slices in the file.
+
 Training mode (``out 0``) trains the first network (upsamplingMode 2, upsampledData 0) or the second one
 (upsamplingMode 1, upsampledData 1: slices of the zoomed volumes with the first network's output as density) the way
 the reference loop does (:196-300 data, :728-902 graph, :1300-1360 iteration): FluidDataLoader slices ->
@@ -62,6 +72,7 @@ simSizeLow, upRes = int(P["simSize"]), int(P["upRes"])
 fromSim, frame_min, frame_max = int(P["fromSim"]), int(P["frame_min"]), int(P["frame_max"])
 useVelocities, velScale = int(P["useVelocities"]), float(P["velScale"])
 upsampling_mode, upsampled_data = int(P["upsamplingMode"]), int(P["upsampledData"])
+upsample_first = int(P["upsampleFirst"])
 generateUni = int(P["genUni"])
 batch_norm = int(P["batchNorm"]) > 0
 load_model_test, load_model_no = int(P["load_model_test"]), int(P["load_model_no"])
@@ -284,9 +295,11 @@ if not outputOnly:
     device = "cuda:0"
     train_main()
     exit(0)
-if upsampling_mode not in (1, 2, 3) or int(P["dataDim"]) != 2 or int(P["useAvgDepool"]):
-    print("ERROR: upsamplingMode 2 (first network), 1 (second) and 3 (third network) of the 2D slice path are implemented; "
-          "mode 0 (linear interpolation between the networks) is used by no example run")
+if upsampling_mode not in (0, 1, 2, 3) or int(P["dataDim"]) != 2 or int(P["useAvgDepool"]):
+    print("ERROR: upsamplingMode 0 to 3 of the 2D slice path are implemented; useAvgDepool and dataDim 3 are not")
+    exit(1)
+if upsampling_mode == 0 and not upsampled_data:
+    print("ERROR: upsamplingMode 0 refines the volumes of density_low_2x2x1_%04d.uni (upsampledData 1)")
     exit(1)
 simSizeHigh = simSizeLow * upRes
 n_ch = 4 if useVelocities else 1
@@ -302,7 +315,8 @@ x_2 = None
 if upsampled_data:
     # the previous network's volumes (4x.py:180-185)
     fl2 = FDL.FluidDataLoader(print_info=1, base_path=packedSimPath, numpy_seed=int(P["randSeed"]),
-                              filename="density_low_1x1_%04d.uni" if upsampling_mode == 3 else "density_low_2x2_%04d.uni",
+                              filename={3: "density_low_1x1_%04d.uni", 0: "density_low_2x2x1_%04d.uni"}.get(
+                                  upsampling_mode, "density_low_2x2_%04d.uni"),
                               filename_index_min=frame_min, oldNamingScheme=False,
                               filename_index_max=frame_max, indices=[fromSim], data_fraction=1.0, multi_file_list=["density"])
     x_2, _, _ = fl2.get()
@@ -325,7 +339,16 @@ for layerno in range(frame_min, frame_max):
     i = layerno - frame_min
     start = time.time()
     low = torch.as_tensor(np.ascontiguousarray(x[i])).to(device)
-    if upsampling_mode == 2:
+    slices = simSizeHigh
+    if upsampling_mode == 2 and not upsample_first:
+        vol = multipass.plane_pass_4x(gen, low, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni))
+        name = 'density_low_2x2x1_%04d.uni'
+        slices = simSizeLow
+    elif upsampling_mode == 0:
+        v1 = torch.as_tensor(np.ascontiguousarray(x_2[i][..., 0])).to(device)
+        vol = multipass.upsample_pass_4x(gen, low, v1, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni))
+        name = 'density_low_1x1x1_%04d.uni'
+    elif upsampling_mode == 2:
         if n_ch > 1:
             low[..., 1:4] *= velScale                                        # 4x.py:283
         xs = ops.axis_zoom_linear(low, 0, upRes)                             # 4x.py:1103
@@ -342,7 +365,8 @@ for layerno in range(frame_min, frame_max):
     print(time.time() - start)
     if generateUni:
         head, _ = uniio.readUni(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, layerno))
-        head['dimX'] = head['dimY'] = head['dimZ'] = simSizeHigh
+        head['dimX'] = head['dimY'] = simSizeHigh
+        head['dimZ'] = slices                                                # 2x2x1: the slices the file holds (see above)
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/' % fromSim + name % layerno, head, vol)
     print('')
 print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))

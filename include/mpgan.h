@@ -79,20 +79,23 @@ int mpg_g8_to_f32(mpg_stream_t stream, const void* g8, int n, int h, int w, int 
  * stride 1, SAME padding (pad_before = (k-1)/2, extra pad bottom/right).
  * Each segment s contributes one K-slice of the implicit GEMM: a residual
  * shortcut is a 1x1 segment, a channel concat is two segments with the same
- * kernel size, a fused nearest upsample is up_log2 > 0.
+ * kernel size, a fused nearest upsample is up_log2 > 0 (of both axes, or with
+ * up_x_only of the columns alone; segments of one launch may differ in both).
  * The result is written as fp32 NHWC (y), as G8 (y_g8), or both.
  * ------------------------------------------------------------------------ */
 #define MPG_MAX_SEG 4
 
 typedef struct mpg_conv_seg {
-    const void* x;       /* G8 [N][cgroups][2][H>>up_log2][W>>up_log2][8] */
+    const void* x;       /* G8 [N][cgroups][2][H>>up_log2][W>>up_log2][8]; up_x_only: [N][cgroups][2][H][W>>up_log2][8] */
     const void* wpack;   /* from mpg_conv_pack_weights (same cout and prec as the launch) */
     int32_t cin;         /* channels consumed, starting at channel 8*g_off of x */
     int32_t cgroups;     /* channel groups of x */
     int32_t g_off;       /* first group consumed */
     int32_t kh, kw;      /* kernel size, 1..7 */
     int32_t up_log2;     /* fused nearest upsample: src = (y >> up_log2, x >> up_log2) */
-    int32_t reserved0;   /* must be 0 */
+    int32_t up_x_only;   /* 0: both axes as above (h and w multiples of 1 << up_log2); 1: columns only,
+                          * src = (y, x >> up_log2), only w a multiple (max_depool(height_factor=1, width_factor=upRes),
+                          * GAN/multipassGAN-4x.py:558: the 4x network that upsamples z itself); other values: MPG_ERR_ARG */
     int32_t pad_hi;           /* 0: TF SAME, pad_before = (k-1)/2; 1: pad_before = k/2 (the data gradient of an even filter) */
 } mpg_conv_seg;
 
@@ -166,7 +169,8 @@ int mpg_conv2d_fused_window(mpg_stream_t stream, const mpg_conv_desc* desc, int 
  * with that `prec` (the fp32 tables of small layers follow the matrix-core image).  Odd filters only. */
 typedef struct mpg_small_pair_desc {
     int32_t n, h, w;          /* output batch / height / width */
-    const void* x;            /* G8 input [N][cgroups][2][H>>up_log2][W>>up_log2][8]; one channel group is read */
+    const void* x;            /* G8 input [N][cgroups][2][H>>up_log2][W>>up_log2][8] ([H][W>>up_log2] with up_x_only); one
+                               * channel group is read */
     int32_t cin, cgroups, g_off, up_log2;
     const void* wpack_a;      /* conv_a: kh_a x kw_a, cin -> cmid */
     int32_t kh_a, kw_a, cmid;
@@ -184,7 +188,7 @@ typedef struct mpg_small_pair_desc {
     float*  y;                /* fp32 NHWC [N,H,W,cout] or NULL */
     void*   y_g8;             /* G8 (one group) or NULL; at least one of the two */
     int32_t prec;             /* MPG_PREC_* the weights were packed for */
-    int32_t reserved;         /* must be 0 */
+    int32_t up_x_only;        /* as mpg_conv_seg.up_x_only: 1 = the upsample repeats columns only; 0 or 1 */
 } mpg_small_pair_desc;
 int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_desc* desc);
 

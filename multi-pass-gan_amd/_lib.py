@@ -42,7 +42,7 @@ class ConvSeg(ctypes.Structure):
         ("kh", ctypes.c_int32),
         ("kw", ctypes.c_int32),
         ("up_log2", ctypes.c_int32),
-        ("reserved0", ctypes.c_int32),
+        ("up_x_only", ctypes.c_int32),
         ("pad_hi", ctypes.c_int32),
     ]
 
@@ -88,7 +88,7 @@ class SmallPairDesc(ctypes.Structure):
         ("act_b", ctypes.c_int32), ("leak_b", ctypes.c_float), ("cout", ctypes.c_int32),
         ("y", ctypes.c_void_p),
         ("y_g8", ctypes.c_void_p),
-        ("prec", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("prec", ctypes.c_int32), ("up_x_only", ctypes.c_int32),
     ]
 
 

@@ -34,11 +34,12 @@ struct SegArgs {
     const char* w;        // packed weights
     int cg_seg;           // channel groups consumed
     int cg_total, g_off;  // groups of the tensor, first group consumed
-    int kh, kw, up;
+    int kh, kw;
+    int up, upy;          // source pixel = (y >> upy, x >> up): upy == up, or 0 for a column-only upsample (up_x_only)
     int cgc, nchunks, sc; // groups per chunk, chunks, weight stages per chunk
     int ih, iw;           // LDS image: (TH + kh - 1) x (TW + kw - 1) pixels
     int pt, pl;           // SAME padding before
-    int hs, ws;           // source height / width (h >> up, w >> up)
+    int hs, ws;           // source height / width (h >> upy, w >> up)
     int np;               // pixels per image plane, padded to a multiple of 64
     int ni_img;           // image DMA instructions per thread per chunk
     int direct;           // F16F6, 1x1 over >= 2 groups: B fragments straight from memory, K runs over groups

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, (NT >= 2 ? 2 : 3)) void conv_mfma_kernel(const
                 if (g < CGC && grp < sg.cg_seg && hy < sg.ih && yy >= 0 && yy < a.h && xx >= 0 && xx < a.w &&
                     (PREC == 3 || pl == 0))
                     src = sg.x + ((((size_t)n * sg.cg_total + sg.g_off + grp) * 2 + pl) * plane_px +
-                                  (size_t)(yy >> sg.up) * sg.ws + (xx >> sg.up)) * 16;
+                                  (size_t)(yy >> sg.upy) * sg.ws + (xx >> sg.up)) * 16;
                 dma16(src, buf + pc * 1024);
             }
         };

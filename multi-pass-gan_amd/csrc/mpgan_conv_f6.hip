@@ -222,7 +222,7 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
 #pragma unroll
             for (int pt = 0; pt < PT; ++pt) {
                 int yy = y0 + PT * wave + pt, xx = x0 + r;
-                yy = (yy < a.h ? yy : a.h - 1) >> sg.up;
+                yy = (yy < a.h ? yy : a.h - 1) >> sg.upy;
                 xx = (xx < a.w ? xx : a.w - 1) >> sg.up;
                 pixo[pt] = (unsigned)(yy * sg.ws + xx) * 16u;
             }
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
             const int yy = y0 - sg.pt + hy;
             const int xx = x0 - sg.pl + hx;
             const bool ok = pl < 2 && hy < sg.ih && yy >= 0 && yy < a.h && xx >= 0 && xx < a.w;
-            img_src[i] = ok ? (int)(((size_t)pl * plane_px + (size_t)(yy >> sg.up) * sg.ws + (xx >> sg.up)) * 16) : -1;
+            img_src[i] = ok ? (int)(((size_t)pl * plane_px + (size_t)(yy >> sg.upy) * sg.ws + (xx >> sg.up)) * 16) : -1;
         }
         const size_t group_bytes = 2 * plane_px * 16;
         const char* const x_first = sg.x + ((size_t)n * sg.cg_total + sg.g_off) * group_bytes;   // uniform

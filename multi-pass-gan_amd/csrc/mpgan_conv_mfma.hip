@@ -126,7 +126,9 @@ int mpg::conv::check_segment(const mpg_conv_desc* d, int s) {
     MPG_REQUIRE(g.cin >= 1 && g.g_off >= 0 && g.g_off + (g.cin + 7) / 8 <= g.cgroups,
                 "mpg_conv2d_fused: segment %d channel-group range", s);
     MPG_REQUIRE(g.up_log2 >= 0 && g.up_log2 <= 4, "mpg_conv2d_fused: segment %d up_log2 %d", s, g.up_log2);
-    MPG_REQUIRE((d->h % (1 << g.up_log2)) == 0 && (d->w % (1 << g.up_log2)) == 0,
+    MPG_REQUIRE(g.up_x_only == 0 || g.up_x_only == 1, "mpg_conv2d_fused: segment %d up_x_only %d (0 or 1)", s, g.up_x_only);
+    // a column-only upsample leaves the rows alone: only w has to divide
+    MPG_REQUIRE((g.up_x_only || (d->h % (1 << g.up_log2)) == 0) && (d->w % (1 << g.up_log2)) == 0,
                 "mpg_conv2d_fused: segment %d: %dx%d not divisible by upsample %d", s, d->h, d->w, 1 << g.up_log2);
     MPG_REQUIRE((((uintptr_t)g.x) & 15) == 0 && (((uintptr_t)g.wpack) & 15) == 0, "mpg_conv2d_fused: segment %d misaligned", s);
     return MPG_OK;
@@ -149,15 +151,15 @@ static int launch_mfma(hipStream_t stream, const mpg_conv_desc* d, const D2SOut*
         SegArgs& o = a.seg[s];
         o.x = (const char*)g.x; o.w = (const char*)g.wpack;
         o.cg_seg = (g.cin + 7) / 8; o.cg_total = g.cgroups; o.g_off = g.g_off;
-        o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2;
+        o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2; o.upy = g.up_x_only ? 0 : g.up_log2;
         o.cgc = ss.cgc; o.nchunks = ss.nchunks; o.sc = ss.sc;
         o.ih = ps.th + g.kh - 1; o.iw = TW + g.kw - 1;
         o.pt = pad_before(g.kh, g.pad_hi); o.pl = pad_before(g.kw, g.pad_hi);
-        o.hs = d->h >> g.up_log2; o.ws = d->w >> g.up_log2;
+        o.hs = d->h >> o.upy; o.ws = d->w >> o.up;
         o.np = ss.np; o.ni_img = ss.ni_img;
         o.direct = ss.direct;
         o.tp = ss.tp;
-        MPG_REQUIRE(!ss.direct || (size_t)(d->h >> g.up_log2) * (d->w >> g.up_log2) * 16 * 16 < ((size_t)1 << 31),
+        MPG_REQUIRE(!ss.direct || (size_t)o.hs * o.ws * 16 * 16 < ((size_t)1 << 31),
                     "mpg_conv2d_fused: segment %d: %dx%d too large for the 1x1 path (32-bit group offsets)", s, d->h, d->w);
         o.pref = ss.pref;
         max_img = ss.img_bytes > max_img ? ss.img_bytes : max_img;

@@ -19,7 +19,7 @@ namespace {
 struct SmallSeg {
     const char* x;
     const float* w;       // [tap][8][8]
-    int cg_total, g_off, kh, kw, up, pt, pl, hs, ws, cin;
+    int cg_total, g_off, kh, kw, up, upy, pt, pl, hs, ws, cin;
 };
 
 struct SmallArgs {
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
             const int yy = y0 - g.pt + hy, xx = x0 - g.pl + hx;
             float v[8];
             if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) {
-                g8_load8(base + ((size_t)(yy >> g.up) * g.ws + (xx >> g.up)) * 16, plane_bytes, v);
+                g8_load8(base + ((size_t)(yy >> g.upy) * g.ws + (xx >> g.up)) * 16, plane_bytes, v);
             } else {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = 0.f;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
                 const int yy = y0 - g.pt + hy, xx = x0 - g.pl + hx;
                 float v[8];
                 if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) {
-                    g8_load8(base + ((size_t)(yy >> g.up) * g.ws + (xx >> g.up)) * 16, plane_bytes, v);
+                    g8_load8(base + ((size_t)(yy >> g.upy) * g.ws + (xx >> g.up)) * 16, plane_bytes, v);
                 } else {
                     for (int q = 0; q < 8; ++q) v[q] = 0.f;
                 }
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
 struct PairArgs {
     int n, h, w;
     const char* x;                 // G8 input, one channel group
-    int cg_total, g_off, up, hs, ws;
+    int cg_total, g_off, up, upy, hs, ws;
     const float *wa, *wb, *wsc;    // [tap][8][8] tables: stage A (cin -> cmid), stage B (cmid -> cout), shortcut (cin -> cout) or null
     int kha, kwa, pta, pla;        // filter A and its SAME padding before
     int khb, kwb, ptb, plb;
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
             const int yy = xy0 + hy, xx = xx0 + hx;
             float v[8];
             if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) {
-                g8_load8(base + ((size_t)(yy >> a.up) * a.ws + (xx >> a.up)) * 16, plane_bytes, v);
+                g8_load8(base + ((size_t)(yy >> a.upy) * a.ws + (xx >> a.up)) * 16, plane_bytes, v);
             } else {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = 0.f;
@@ -454,9 +454,9 @@ int mpg::conv::launch_small(hipStream_t stream, const mpg_conv_desc* d) {
         SmallSeg& o = sa.seg[s];
         o.x = (const char*)g.x;
         o.w = (const float*)((const char*)g.wpack + pack_base_bytes(g.kh, g.kw, g.cin, d->cout, d->prec));
-        o.cg_total = g.cgroups; o.g_off = g.g_off; o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2;
+        o.cg_total = g.cgroups; o.g_off = g.g_off; o.kh = g.kh; o.kw = g.kw; o.up = g.up_log2; o.upy = g.up_x_only ? 0 : g.up_log2;
         o.pt = pad_before(g.kh, g.pad_hi); o.pl = pad_before(g.kw, g.pad_hi);
-        o.hs = d->h >> g.up_log2; o.ws = d->w >> g.up_log2; o.cin = g.cin;
+        o.hs = d->h >> o.upy; o.ws = d->w >> o.up; o.cin = g.cin;
         cmax = g.cin > cmax ? g.cin : cmax;
         tmax = g.kh * g.kw > tmax ? g.kh * g.kw : tmax;
         const int px = (SM_TH + g.kh - 1) * (SM_TW + g.kw - 1);
@@ -499,15 +499,16 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
                                           (d->kh_s & 1) && (d->kw_s & 1) && ((d->kh_a + d->kh_b) & 1) == 0 && ((d->kw_a + d->kw_b) & 1) == 0),
                 "mpg_conv2d_small_pair: the shortcut filter must be odd and fit inside the input tile of two odd filters");
     MPG_REQUIRE(d->g_off >= 0 && d->g_off < d->cgroups, "mpg_conv2d_small_pair: channel-group range");
-    MPG_REQUIRE(d->up_log2 >= 0 && d->up_log2 <= 4 && (d->h % (1 << d->up_log2)) == 0 && (d->w % (1 << d->up_log2)) == 0,
+    MPG_REQUIRE(d->up_x_only == 0 || d->up_x_only == 1, "mpg_conv2d_small_pair: up_x_only %d (0 or 1)", d->up_x_only);
+    MPG_REQUIRE(d->up_log2 >= 0 && d->up_log2 <= 4 && (d->up_x_only || (d->h % (1 << d->up_log2)) == 0) && (d->w % (1 << d->up_log2)) == 0,
                 "mpg_conv2d_small_pair: upsample %d", d->up_log2);
     MPG_REQUIRE(d->act_a >= MPG_ACT_NONE && d->act_a <= MPG_ACT_TANH && d->act_b >= MPG_ACT_NONE && d->act_b <= MPG_ACT_TANH, "mpg_conv2d_small_pair: bad act");
     MPG_REQUIRE(d->prec == MPG_PREC_F16X1 || d->prec == MPG_PREC_F16X3 || d->prec == MPG_PREC_F16F6, "mpg_conv2d_small_pair: bad prec %d", d->prec);
     MPG_REQUIRE((((uintptr_t)d->x) & 15) == 0 && (((uintptr_t)d->y_g8) & 15) == 0, "mpg_conv2d_small_pair: misaligned tensor");
     PairArgs a;
     a.n = d->n; a.h = d->h; a.w = d->w;
-    a.x = (const char*)d->x; a.cg_total = d->cgroups; a.g_off = d->g_off; a.up = d->up_log2;
-    a.hs = d->h >> d->up_log2; a.ws = d->w >> d->up_log2;
+    a.x = (const char*)d->x; a.cg_total = d->cgroups; a.g_off = d->g_off; a.up = d->up_log2; a.upy = d->up_x_only ? 0 : d->up_log2;
+    a.hs = d->h >> a.upy; a.ws = d->w >> a.up;
     a.wa = (const float*)((const char*)d->wpack_a + pack_base_bytes(d->kh_a, d->kw_a, d->cin, d->cmid, d->prec));
     a.wb = (const float*)((const char*)d->wpack_b + pack_base_bytes(d->kh_b, d->kw_b, d->cmid, d->cout, d->prec));
     a.wsc = d->wpack_s ? (const float*)((const char*)d->wpack_s + pack_base_bytes(d->kh_s, d->kw_s, d->cin, d->cout, d->prec)) : nullptr;

@@ -79,7 +79,8 @@ def slice_range(total, comm):
 # ----------------------------------------------------------------------------
 class Generator(object):
     """One generator network: private graph + session.  Call with device tensors
-    x [N,h,w,C] (and y [N,H,W] for the later 8x generators); returns [N,H,W]."""
+    x [N,h,w,C] (and y [N,H,W] for the later 8x generators); returns [N,H,W].
+    gen_resnet with upsampling_mode 0 takes planes x [N, high, low, C]: its first layer repeats the columns only."""
 
     def __init__(self, kind, cfg, params=None, prec=None, device="cuda:0", seed=777, prec_map=None):
         prec = ops.INFERENCE_PREC if prec is None else prec
@@ -94,8 +95,9 @@ class Generator(object):
             self.y = None
             if kind == "gen_resnet":
                 mode = c.get("upsampling_mode", 2)
-                side = low if mode == 2 else self.high
-                self.x = G.placeholder([None, side * side * nch], name="x")
+                rows = low if mode == 2 else self.high
+                cols = low if mode in (2, 0) else self.high
+                self.x = G.placeholder([None, rows * cols * nch], name="x")
                 self.sampler = arch.gen_resnet(self.x, low, up, nch, mode, use_batch_norm=c.get("batch_norm", True))
             elif kind == "growing_gen":
                 first = c.get("first_gen", True)
@@ -277,6 +279,62 @@ def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend
     out = _run_pass(gen, xin, None, lo, hi, batch)
     vol = comm.all_gather_slabs(out, s)
     return backend.volume_transpose(vol, back, cutoff=CUTOFF if apply_cutoff else 0.0)
+
+
+def _single_process(comm, what):
+    comm = comm or LocalComm()
+    if comm.world > 1:
+        raise ValueError("%s runs in one process (world %d): its slices are not sharded" % (what, comm.world))
+    return comm
+
+
+def plane_pass_4x(gen1, low, up_res=4, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True):
+    """upsamplingMode 2 with upsampleFirst 0 (4x.py:1105,1136,1162): the network runs over the z_low slices of the
+    low-res array as they are, nothing is zoomed.  low: [z_low, y, x, C]; returns [z_low, Y, X] (density_low_2x2x1).
+    The velocities are scaled as in pass 1 of two_pass_4x (4x.py:283, first run)."""
+    _single_process(comm, "plane_pass_4x")
+    nch = low.shape[3]
+    low1 = low
+    if nch > 1 and vel_scale != 1.0:
+        low1 = backend.channel_gather(low, None, list(range(nch)), [1.0] + [vel_scale] * 3 + [1.0] * (nch - 4))
+    out = _run_pass(gen1, low1, None, 0, low.shape[0], batch)        # [z_low, Y, X]
+    return backend.cutoff(out, CUTOFF) if apply_cutoff else out
+
+
+def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True):
+    """upsamplingMode 0 (4x.py:277-283,1097,1107-1111,1139-1142,1166): the second network upsamples z itself.  prev: the
+    [z_low, Y, X] volume of plane_pass_4x; gen0: Generator("gen_resnet", upsampling_mode=0).  The velocities are taken
+    without the upres factor of modes 1 / 3 (:280); vy and vz times the velocity scale (:283 indexes the three-channel
+    array with 1:4); zoomed along y and x only (:1097); concatenated behind prev; planes [x][y][z_low] (:1107); channels
+    1 and 2 times upRes (:1108), channels 1 and 3 swapped (:1109-1111): (d, vz, vy * upRes, vx * upRes).
+    The output stack [x][y][z] goes through transpose(1, 2, 0) as :1141-1142 writes it.  That transpose was written for
+    the [x][z][y] stack of mode 1; for mode 0 it leaves the axes as (y, z, x), and so does this function: the returned
+    volume (density_low_1x1x1) is what the reference stores, not a [z, y, x] one."""
+    _single_process(comm, "upsample_pass_4x")
+    nch = low.shape[3]
+    zl = low.shape[0]
+    s = zl * up_res
+    if nch > 1:
+        s2 = None if vel_scale == 1.0 else [1.0, vel_scale, vel_scale]
+        vel = backend.channel_gather(low, None, [1, 2, 3], None, s2)
+        for ax in (1, 2):
+            vel = backend.axis_zoom_linear(vel, ax, up_res)          # [z_low, Y, X, 3]
+        up = float(up_res)
+        xin = backend.channel_gather(prev.reshape(zl, s, s, 1), vel, [0, 3, 2, 1], [1.0, 1.0, up, up])
+        xin = backend.volume_transpose(xin, (2, 1, 0))               # [x][y][z_low][4]
+    else:
+        xin = backend.volume_transpose(prev.reshape(zl, s, s), (2, 1, 0)).reshape(s, s, zl, 1)
+    out = _run_pass(gen0, xin, None, 0, s, batch)                    # [x][y][z]
+    return backend.volume_transpose(out, (1, 2, 0), cutoff=CUTOFF if apply_cutoff else 0.0)
+
+
+def two_pass_4x_axis(gen1, gen0, low, up_res=4, batch=8, comm=None, backend=ops, vel_scale=1.0):
+    """plane_pass_4x then upsample_pass_4x: the 4x pipeline in which nothing is zoomed along z (sim + sim * upRes
+    generator slices instead of 2 * sim * upRes).  Returns (final volume as upsample_pass_4x leaves it, pass-1 volume
+    [z_low, Y, X]), both with the cutoff of the files the reference writes."""
+    _single_process(comm, "two_pass_4x_axis")
+    v1 = plane_pass_4x(gen1, low, up_res, batch, None, backend, vel_scale)
+    return upsample_pass_4x(gen0, low, v1, up_res, batch, None, backend, vel_scale), v1
 
 
 def two_pass_4x(gen1, gen2, low, up_res=4, batch=8, comm=None, backend=ops, vel_scale=1.0, exchange="all_gather"):

@@ -151,12 +151,14 @@ def pack_conv_weights(w_hwio, wscale=1.0, cout_scale=None, c_off=0, cin=None, pr
 
 class Segment(object):
     """One K-slice of a fused convolution: G8 source (an fp32 NHWC tensor is converted on the
-    fly), first channel group consumed, packed weights, fused nearest upsample."""
+    fly), first channel group consumed, packed weights, fused nearest upsample (up_x_only=1: of the columns alone,
+    the source is [N, H, W >> up_log2])."""
 
-    __slots__ = ("x", "packed", "g_off", "up_log2", "pad_hi")
+    __slots__ = ("x", "packed", "g_off", "up_log2", "up_x_only", "pad_hi")
 
-    def __init__(self, x, packed, c_off=0, up_log2=0, pad_hi=0):
+    def __init__(self, x, packed, c_off=0, up_log2=0, pad_hi=0, up_x_only=0):
         self.pad_hi = int(pad_hi)
+        self.up_x_only = int(up_x_only)
         if isinstance(x, torch.Tensor):
             x = to_g8(x, c_off, packed.cin, flavour_for(packed.prec))
             c_off = 0
@@ -182,16 +184,16 @@ def _conv_desc(segments, out_hw, bias, act, leak):
         if g8.flavour != flavour_for(pk.prec):
             raise _lib.MpgError("conv2d_fused: segment %d input has G8 flavour %d, precision %d reads flavour %d"
                                 % (i, g8.flavour, pk.prec, flavour_for(pk.prec)))
-        if g8.n != n or g8.h << s.up_log2 != h or g8.w << s.up_log2 != w:
-            raise _lib.MpgError("conv2d_fused: segment %d input %dx%dx%d does not match output %dx%dx%d (up 2^%d)"
-                                % (i, g8.n, g8.h, g8.w, n, h, w, s.up_log2))
+        if g8.n != n or g8.h << (0 if s.up_x_only else s.up_log2) != h or g8.w << s.up_log2 != w:
+            raise _lib.MpgError("conv2d_fused: segment %d input %dx%dx%d does not match output %dx%dx%d (up 2^%d%s)"
+                                % (i, g8.n, g8.h, g8.w, n, h, w, s.up_log2, " of the columns" if s.up_x_only else ""))
         if s.g_off * 8 + pk.cin > g8.c:
             raise _lib.MpgError("conv2d_fused: segment %d channel window [%d,%d) exceeds %d"
                                 % (i, s.g_off * 8, s.g_off * 8 + pk.cin, g8.c))
         g = d.seg[i]
         g.x, g.wpack = g8.buf.data_ptr(), pk.buf.data_ptr()
         g.cin, g.cgroups, g.g_off = pk.cin, g8.groups, s.g_off
-        g.kh, g.kw, g.up_log2 = pk.kh, pk.kw, s.up_log2
+        g.kh, g.kw, g.up_log2, g.up_x_only = pk.kh, pk.kw, s.up_log2, s.up_x_only
         g.pad_hi = s.pad_hi
     if bias is not None:
         if bias.numel() != p0.cout:
@@ -383,9 +385,10 @@ def small_pair_ok(cin, cmid, cout, ka, kb, ks=None, planner=False):
 
 
 def conv2d_small_pair(x, c_off, up_log2, pk_a, pk_b, pk_s, out_hw, bias_a=None, act_a=None, leak_a=0.2, bias_b=None,
-                      act_b=None, leak_b=0.2, want_f32=True, want_g8=False, out=None):
+                      act_b=None, leak_b=0.2, want_f32=True, want_g8=False, out=None, up_x_only=0):
     """y = act_b(conv_b(act_a(conv_a(up(x)) + bias_a)) + conv_s(up(x)) + bias_b): a residual block of <= 8-channel
-    convolutions as one launch (mpg_conv2d_small_pair); x: G8 (or fp32 NHWC, converted), pk_*: PackedWeights."""
+    convolutions as one launch (mpg_conv2d_small_pair); x: G8 (or fp32 NHWC, converted), pk_*: PackedWeights;
+    up_x_only=1: the upsample repeats columns only (x is [N, H, W >> up_log2])."""
     lib = _lib.load()
     if isinstance(x, torch.Tensor):
         x = to_g8(x, c_off, pk_a.cin)
@@ -393,8 +396,9 @@ def conv2d_small_pair(x, c_off, up_log2, pk_a, pk_b, pk_s, out_hw, bias_a=None, 
     if c_off % 8:
         raise _lib.MpgError("conv2d_small_pair: channel offset %d of a G8 source is not a multiple of 8" % c_off)
     h, w = out_hw
-    if x.h << up_log2 != h or x.w << up_log2 != w:
-        raise _lib.MpgError("conv2d_small_pair: input %dx%d does not match output %dx%d (up 2^%d)" % (x.h, x.w, h, w, up_log2))
+    if x.h << (0 if up_x_only else up_log2) != h or x.w << up_log2 != w:
+        raise _lib.MpgError("conv2d_small_pair: input %dx%d does not match output %dx%d (up 2^%d%s)"
+                            % (x.h, x.w, h, w, up_log2, " of the columns" if up_x_only else ""))
     if pk_b.cin != pk_a.cout or (pk_s is not None and (pk_s.cin != pk_a.cin or pk_s.cout != pk_b.cout)):
         raise _lib.MpgError("conv2d_small_pair: channel counts of the three convolutions do not chain")
     if len(set(p.prec for p in (pk_a, pk_b) + ((pk_s,) if pk_s is not None else ()))) != 1:
@@ -405,6 +409,7 @@ def conv2d_small_pair(x, c_off, up_log2, pk_a, pk_b, pk_s, out_hw, bias_a=None, 
     d = _lib.SmallPairDesc()
     d.n, d.h, d.w = x.n, h, w
     d.x, d.cin, d.cgroups, d.g_off, d.up_log2 = x.buf.data_ptr(), pk_a.cin, x.groups, c_off // 8, up_log2
+    d.up_x_only = int(up_x_only)          # the library refuses anything but 0 and 1
     d.wpack_a, d.kh_a, d.kw_a, d.cmid = pk_a.buf.data_ptr(), pk_a.kh, pk_a.kw, pk_a.cout
     d.wpack_b, d.kh_b, d.kw_b, d.cout = pk_b.buf.data_ptr(), pk_b.kh, pk_b.kw, pk_b.cout
     if pk_s is not None:

@@ -103,6 +103,12 @@ def _is_pow2(v):
     return v >= 1 and (v & (v - 1)) == 0
 
 
+def _up_info(up):
+    """the fused upsample (up_log2, up_x_only) of a segment as plan_summary shows it: `up_x_only` appears next to
+    `up_log2` where it is set, so the plans of networks without a column-only upsample read as they always did"""
+    return dict(up_log2=up[0], up_x_only=1) if up[1] else dict(up_log2=up[0])
+
+
 class _Step(object):
     """One entry of a launch plan: `run(env)` computes `node` from the env entries of `deps`.  A fused convolution
     launch also carries `info` (its plan_summary entry), `emit` (which output formats it writes) and, where it may
@@ -336,7 +342,7 @@ class Session(object):
             if p2 is None or p2["pn"] or p2["post_add"] is not None or p2["cout"] > 8 or not 1 <= len(p2["segs"]) <= 2:
                 continue
             src1, c_off1, up1, term_b, w_off_b, cin_b = p2["segs"][0]
-            if src1.id not in by_id or c_off1 != 0 or up1 != 0 or w_off_b != 0:
+            if src1.id not in by_id or c_off1 != 0 or up1 != (0, 0) or w_off_b != 0:
                 continue
             s1 = by_id[src1.id]
             n1, p1 = s1.node, s1.parts
@@ -371,7 +377,7 @@ class Session(object):
             pk_s = self._packed_for(term_s, 0, cin_a, prec) if term_s is not None else None
             g8, off = self._g8(env, src0, c_off0, cin_a, ops.G8_F16)
             return self._boxed(ops.conv2d_small_pair(
-                g8, off, up0, pk_a, pk_b, pk_s, p2["out_hw"], bias_a=self._bias_for(p1["terms"]), act_a=p1["act"],
+                g8, off, up0[0], pk_a, pk_b, pk_s, p2["out_hw"], up_x_only=up0[1], bias_a=self._bias_for(p1["terms"]), act_a=p1["act"],
                 leak_a=p1["leak"], bias_b=self._bias_for(p2["terms"]), act_b=p2["act"], leak_b=p2["leak"],
                 want_f32=emit["f32"], want_g8=emit["g8"], out=self._dst(env, emit, s2.node.shape)), emit)
 
@@ -455,7 +461,7 @@ class Session(object):
             for (src, c_off_src, up, term, w_off, cin) in segs:
                 pk = self._packed_for(term, w_off, cin, prec)
                 g8, off = self._g8(env, src, c_off_src, cin, ops.flavour_for(prec))
-                seg_objs.append(ops.Segment(g8, pk, off, up))
+                seg_objs.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
             bias = self._bias_for(terms)
             pa = self._f32(env, post_add) if post_add is not None else None
             if self.tap is not None and self.tap in lead:
@@ -477,7 +483,7 @@ class Session(object):
             "kind": "conv2d_fused", "cout": cout, "act": act, "pixel_norm": pn, "prec": prec,
             "post_add": post_add.name if post_add is not None else None,
             "post_add_id": post_add.id if post_add is not None else None,
-            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, up_log2=up, w_off=w_off,
+            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, w_off=w_off, **_up_info(up),
                               kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
                          for (src, c_off_src, up, term, w_off, cin) in segs],
         }
@@ -498,7 +504,7 @@ class Session(object):
                 for (src, c_off_src, up, term, w_off, cin) in segs:
                     pk = self._packed_chunk(term, w_off, cin, prec, co, cw)
                     g8, off = self._g8(env, src, c_off_src, cin, ops.flavour_for(prec))
-                    seg_objs.append(ops.Segment(g8, pk, off, up))
+                    seg_objs.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
                 launches.append((seg_objs, co))
             pa = self._f32(env, post_add) if post_add is not None else None
             return self._boxed(ops.conv2d_fused_wide(
@@ -509,7 +515,7 @@ class Session(object):
             "kind": "conv2d_fused", "cout": cout, "launches": len(chunks), "act": act, "pixel_norm": pn, "prec": precs[0],
             "post_add": post_add.name if post_add is not None else None,
             "post_add_id": post_add.id if post_add is not None else None,
-            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, up_log2=up, w_off=w_off,
+            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, w_off=w_off, **_up_info(up),
                               kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
                          for (src, c_off_src, up, term, w_off, cin) in segs],
         }
@@ -566,7 +572,7 @@ class Session(object):
                 for (src, c_off_src, up, t, w_off, ci) in segs:
                     pk = self._packed_chunk(t, w_off, ci, prec, co, cw)
                     g8, off = self._g8(env, src, c_off_src, ci, ops.flavour_for(prec))
-                    seg_objs.append(ops.Segment(g8, pk, off, up))
+                    seg_objs.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
                 launches.append((seg_objs, co))
             return self._boxed(ops.conv2d_fused_d2s(launches, out_hw, c_total, bias=self._bias_for([term]), want_f32=emit["f32"],
                                                     want_g8=emit["g8"], out=self._dst(env, emit, n.shape)), emit)
@@ -574,7 +580,7 @@ class Session(object):
         info = {
             "kind": "conv2d_fused_d2s", "cout": c_total // 4, "conv_cout": c_total, "launches": len(chunks), "act": None,
             "pixel_norm": False, "prec": precs[0], "post_add": None, "post_add_id": None,
-            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=ci, up_log2=up, w_off=w_off, kernel=(1, 1),
+            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=ci, w_off=w_off, **_up_info(up), kernel=(1, 1),
                               weight=lead) for (src, c_off_src, up, t, w_off, ci) in segs],
         }
         return _Step(n, [s[0] for s in segs], run, info, emit)
@@ -618,8 +624,10 @@ class Session(object):
         return terms, act, leak, pn, pn_eps
 
     def _segments_of(self, term):
-        """Resolve the conv input into (source node, channel offset in source, up_log2, term,
-        weight channel offset, channel count) tuples, looking through concat / nearest resize / slice."""
+        """Resolve the conv input into (source node, channel offset in source, (up_log2, up_x_only), term,
+        weight channel offset, channel count) tuples, looking through concat / nearest resize / slice.  The fused
+        upsample repeats both axes 2^up_log2 times, or with up_x_only = 1 the columns alone (max_depool(height_factor=1,
+        width_factor=upRes), the first layer of the upsampling_mode 0 generator)."""
         out_h, out_w = term.conv.shape[1], term.conv.shape[2]
         out = []
 
@@ -638,22 +646,22 @@ class Session(object):
             if node.op == "slice":
                 b = node.attrs["begin"]
                 return resolve(node.inputs[0], c_lo + b, c_hi + b, w_off, up)
-            if node.op == "resize" and node.attrs["method"] == 1 and up == 0:
+            if node.op == "resize" and node.attrs["method"] == 1 and up == (0, 0):
                 src = node.inputs[0]
                 fy, fx = node.attrs["oh"] // src.shape[1], node.attrs["ow"] // src.shape[2]
-                if (fy == fx and _is_pow2(fy) and fy <= 16 and src.shape[1] * fy == node.attrs["oh"]
+                if (fy in (fx, 1) and _is_pow2(fx) and fx <= 16 and src.shape[1] * fy == node.attrs["oh"]
                         and src.shape[2] * fx == node.attrs["ow"]):
-                    return resolve(src, c_lo, c_hi, w_off, fy.bit_length() - 1)
+                    return resolve(src, c_lo, c_hi, w_off, (fx.bit_length() - 1, int(fy != fx)))
             if node.op == "reshape" and len(node.shape) == 4 and node.inputs[0].shape is not None \
                     and len(node.inputs[0].shape) == 4 and tuple(node.inputs[0].shape[1:]) == tuple(node.shape[1:]):
                 return resolve(node.inputs[0], c_lo, c_hi, w_off, up)
-            if len(node.shape) != 4 or (node.shape[1] << up) != out_h or (node.shape[2] << up) != out_w:
+            if len(node.shape) != 4 or (node.shape[1] << (0 if up[1] else up[0])) != out_h or (node.shape[2] << up[0]) != out_w:
                 return False
             out.append((node, c_lo, up, term, w_off, c_hi - c_lo))
             return True
 
         src = term.conv.inputs[0]
-        if not resolve(src, 0, src.shape[3], 0, 0):
+        if not resolve(src, 0, src.shape[3], 0, (0, 0)):
             return None
         return out
 
