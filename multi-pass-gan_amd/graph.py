@@ -216,6 +216,29 @@ def match_layer(n, single_use, convs=("conv2d",)):
     return (cur, bias, bn, act, leak) if cur.op in convs else None
 
 
+def consumers(fetches):
+    """node id -> the nodes that read it, over everything the `fetches` depend on.  A node lists a reader once per input
+    slot it fills there; a fetched node also lists None, once per time it is fetched."""
+    cons, seen, stack = {}, set(), list(fetches)
+    for f in fetches:
+        cons.setdefault(f.id, []).append(None)
+    while stack:
+        n = stack.pop()
+        if n.id in seen:
+            continue
+        seen.add(n.id)
+        for i in n.inputs:
+            cons.setdefault(i.id, []).append(n)
+            stack.append(i)
+    return cons
+
+
+def sole_reader(cons, n):
+    """the one node that reads n according to `cons` (of consumers()), or None: n is fetched, unread, or read twice"""
+    readers = cons.get(n.id, ())
+    return readers[0] if len(readers) == 1 else None
+
+
 def activation_name(activation):
     """Map an activation callable (as passed to GAN.convolutional_layer) to a kernel id."""
     if activation is None:

@@ -73,11 +73,6 @@ class G8(object):
         return G8(buf, n, h, w, c, flavour)
 
 
-def flavour_for(prec):
-    """the G8 flavour a launch of precision `prec` reads: every precision reads (hi16, lo16) since round 3"""
-    return G8_F16
-
-
 def f6_available(cout, segments=()):
     """MPG_PREC_F16F6 is built for every output width of the fused convolution (1..128); a segment (kh, kw, cin)
     whose LDS images do not fit at that width (7x7 with four cout tiles) answers 0 to the pack-size query"""
@@ -160,7 +155,7 @@ class Segment(object):
         self.pad_hi = int(pad_hi)
         self.up_x_only = int(up_x_only)
         if isinstance(x, torch.Tensor):
-            x = to_g8(x, c_off, packed.cin, flavour_for(packed.prec))
+            x = to_g8(x, c_off, packed.cin)
             c_off = 0
         if c_off % 8:
             raise _lib.MpgError("Segment: channel offset %d of a G8 source is not a multiple of 8" % c_off)
@@ -181,9 +176,9 @@ def _conv_desc(segments, out_hw, bias, act, leak):
         g8, pk = s.x, s.packed
         if (pk.cout, pk.prec) != (p0.cout, p0.prec):
             raise _lib.MpgError("conv2d_fused: segments packed with different cout/prec")
-        if g8.flavour != flavour_for(pk.prec):
-            raise _lib.MpgError("conv2d_fused: segment %d input has G8 flavour %d, precision %d reads flavour %d"
-                                % (i, g8.flavour, pk.prec, flavour_for(pk.prec)))
+        if g8.flavour != G8_F16:
+            raise _lib.MpgError("conv2d_fused: segment %d input has G8 flavour %d, every precision reads flavour %d"
+                                % (i, g8.flavour, G8_F16))
         if g8.n != n or g8.h << (0 if s.up_x_only else s.up_log2) != h or g8.w << s.up_log2 != w:
             raise _lib.MpgError("conv2d_fused: segment %d input %dx%dx%d does not match output %dx%dx%d (up 2^%d%s)"
                                 % (i, g8.n, g8.h, g8.w, n, h, w, s.up_log2, " of the columns" if s.up_x_only else ""))
@@ -222,6 +217,15 @@ def _alloc_outputs(shape, dev, want_f32, want_g8, out, what):
     return y, y8, outs
 
 
+def _checked_post_add(post_add, coff, shape, what):
+    """post_add as the epilogue reads it: a contiguous fp32 NHWC GPU tensor over the pixels of the output `shape` that
+    holds channels [coff, coff + shape[3])"""
+    pa = _dev(post_add, "post_add")
+    if pa.dim() != 4 or tuple(pa.shape[:3]) != tuple(shape[:3]) or coff + shape[3] > pa.shape[3]:
+        raise _lib.MpgError("%s: post_add %s does not match output" % (what, tuple(pa.shape)))
+    return pa
+
+
 def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=False, pn_eps=1e-8,
                  post_add=None, post_add_coff=0, out=None, want_f32=True, want_g8=False, reserved=0,
                  in_amax=None):
@@ -233,9 +237,7 @@ def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=Fal
     shape = (d.n, d.h, d.w, d.cout)
     d.pixel_norm, d.pn_eps = int(bool(pixel_norm)), pn_eps
     if post_add is not None:
-        pa = _dev(post_add, "post_add")
-        if pa.dim() != 4 or tuple(pa.shape[:3]) != shape[:3] or post_add_coff + d.cout > pa.shape[3]:
-            raise _lib.MpgError("conv2d_fused: post_add %s does not match output" % (tuple(pa.shape),))
+        pa = _checked_post_add(post_add, post_add_coff, shape, "conv2d_fused")
         d.post_add, d.post_add_stride, d.post_add_coff = pa.data_ptr(), pa.shape[3], post_add_coff
     y, y8, outs = _alloc_outputs(shape, segments[0].x.buf.device, want_f32, want_g8, out, "conv2d_fused")
     d.y, d.y_g8 = _ptr(y), _ptr(y8)
@@ -246,37 +248,57 @@ def conv2d_fused(segments, out_hw, bias=None, act=None, leak=0.2, pixel_norm=Fal
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
-def conv2d_fused_d2s(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, out=None, want_f32=True, want_g8=False):
-    """GAN.pixel_shuffle (GAN.py:554-560) with the shuffle in the store: depth_to_space(conv(...) + bias, 2) of a
-    c_total-channel convolution given as 128-wide output chunks [(segments, co_off), ...] (each chunk's weights packed
-    for its own output channels), one mpg_conv2d_fused_d2s launch per chunk into the same tensors.  Returns fp32
-    [N, 2H, 2W, c_total/4] and / or G8, like conv2d_fused.  Raises MpgError where the launch refuses (G8 output with
-    c_total/4 not a multiple of 8): the caller then runs conv2d_fused and depth_to_space."""
+def _launch_windows(what, entry, lead_args, chunks, out_hw, c_total, out_c, bias, act, leak, want_f32, want_g8, out,
+                    post_add=None, post_add_coff=0, g8_only=False):
+    """What conv2d_fused_wide and conv2d_fused_d2s share: the output windows `chunks` = [(segments, co_off), ...] of one
+    c_total-channel convolution (each window's weights packed for its own output channels) as one launch each of the
+    library's `entry`(stream, desc, *lead_args, c_total, co_off) into the same tensors of out_c = (rows and columns per
+    input pixel, channels).  Checked once: the windows cover channels 0..c_total, the bias has c_total entries, the
+    outputs; per window the bias is sliced and post_add read at the window's channels.  g8_only: the windows write the
+    G8 tensor alone, which exists then whether it was asked for or not.  Returns (fp32 or None, G8 or None, [those
+    requested]) like _alloc_outputs."""
     lib = _lib.load()
-    if c_total % 4 or not chunks:
-        raise _lib.MpgError("conv2d_fused_d2s: %d channels are not a multiple of 4" % c_total)
-    h, w = out_hw
-    segs0 = chunks[0][0]
-    n, dev, cs = segs0[0].x.n, segs0[0].x.buf.device, c_total // 4
-    if want_g8 and cs % 8:
-        raise _lib.MpgError("conv2d_fused_d2s: G8 output of %d channels (not a multiple of 8)" % cs)
+    if not chunks:
+        raise _lib.MpgError("%s: no chunks" % what)
     co = 0
     for segments, co_off in sorted(chunks, key=lambda ch: ch[1]):
         if co_off != co:
             break
         co += segments[0].packed.cout
     if co != c_total:
-        raise _lib.MpgError("conv2d_fused_d2s: the chunks do not cover channels 0..%d once" % c_total)
+        raise _lib.MpgError("%s: the chunks do not cover channels 0..%d once" % (what, c_total))
     if bias is not None:
         bias = _dev(bias, "bias")
         if bias.numel() != c_total:
-            raise _lib.MpgError("conv2d_fused_d2s: bias has %d entries, expected %d" % (bias.numel(), c_total))
-    y, y8, outs = _alloc_outputs((n, 2 * h, 2 * w, cs), dev, want_f32, want_g8, out, "conv2d_fused_d2s")
+            raise _lib.MpgError("%s: bias has %d entries, expected %d" % (what, bias.numel(), c_total))
+    x0 = chunks[0][0][0].x
+    shape = (x0.n, out_c[0] * out_hw[0], out_c[0] * out_hw[1], out_c[1])
+    y, y8, outs = _alloc_outputs(shape, x0.buf.device, want_f32, want_g8, out, what)
+    pa = _checked_post_add(post_add, post_add_coff, shape, what) if post_add is not None else None
+    if g8_only and y8 is None:
+        y8 = G8.empty(*shape, x0.buf.device, G8_F16)
     for segments, co_off in chunks:
         cw = segments[0].packed.cout
         d = _conv_desc(segments, out_hw, bias[co_off:co_off + cw].contiguous() if bias is not None else None, act, leak)
-        d.y, d.y_g8 = _ptr(y), _ptr(y8)
-        _lib.check(lib.mpg_conv2d_fused_d2s(_stream(), ctypes.byref(d), 2, c_total, co_off), "mpg_conv2d_fused_d2s")
+        if pa is not None:
+            d.post_add, d.post_add_stride, d.post_add_coff = pa.data_ptr(), pa.shape[3], post_add_coff + co_off
+        d.y, d.y_g8 = _ptr(None if g8_only else y), _ptr(y8)
+        _lib.check(getattr(lib, entry)(_stream(), ctypes.byref(d), *lead_args, c_total, co_off), entry)
+    return y, y8, outs
+
+
+def conv2d_fused_d2s(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, out=None, want_f32=True, want_g8=False):
+    """GAN.pixel_shuffle (GAN.py:554-560) with the shuffle in the store: depth_to_space(conv(...) + bias, 2) of a
+    c_total-channel convolution given as 128-wide output chunks [(segments, co_off), ...] (each chunk's weights packed
+    for its own output channels), one mpg_conv2d_fused_d2s launch per chunk into the same tensors.  Returns fp32
+    [N, 2H, 2W, c_total/4] and / or G8, like conv2d_fused.  Raises MpgError where the launch refuses (G8 output with
+    c_total/4 not a multiple of 8): the caller then runs conv2d_fused and depth_to_space."""
+    if c_total % 4 or not chunks:
+        raise _lib.MpgError("conv2d_fused_d2s: %d channels are not a multiple of 4" % c_total)
+    if want_g8 and (c_total // 4) % 8:
+        raise _lib.MpgError("conv2d_fused_d2s: G8 output of %d channels (not a multiple of 8)" % (c_total // 4))
+    outs = _launch_windows("conv2d_fused_d2s", "mpg_conv2d_fused_d2s", (2,), chunks, out_hw, c_total, (2, c_total // 4), bias,
+                           act, leak, want_f32, want_g8, out)[2]
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 
@@ -313,44 +335,13 @@ def conv2d_fused_wide(chunks, out_hw, c_total, bias=None, act=None, leak=0.2, pi
     applies the activation, then the pixel norm (GAN.py:472-474 behind the layer), which needs every channel of a pixel:
     the windows then write G8 only (the working form, also when only fp32 is wanted) and mpg_pixel_norm_g8 runs last,
     rewriting that tensor in place and writing the fp32 result.  Returns like conv2d_fused."""
-    lib = _lib.load()
-    if not chunks:
-        raise _lib.MpgError("conv2d_fused_wide: no chunks")
-    h, w = out_hw
-    segs0 = chunks[0][0]
-    n, dev = segs0[0].x.n, segs0[0].x.buf.device
-    co = 0
-    for segments, co_off in sorted(chunks, key=lambda ch: ch[1]):
-        if co_off != co:
-            break
-        co += segments[0].packed.cout
-    if co != c_total:
-        raise _lib.MpgError("conv2d_fused_wide: the chunks do not cover channels 0..%d once" % c_total)
-    if bias is not None:
-        bias = _dev(bias, "bias")
-        if bias.numel() != c_total:
-            raise _lib.MpgError("conv2d_fused_wide: bias has %d entries, expected %d" % (bias.numel(), c_total))
-    shape = (n, h, w, c_total)
-    if not (want_f32 or want_g8 or out is not None):
-        raise _lib.MpgError("conv2d_fused_wide: no output requested")
-    pa = None
-    if post_add is not None:
-        if pixel_norm:
-            raise _lib.MpgError("conv2d_fused_wide: post_add follows the pixel norm, which runs behind the window launches")
-        pa = _dev(post_add, "post_add")
-        if pa.dim() != 4 or tuple(pa.shape[:3]) != shape[:3] or post_add_coff + c_total > pa.shape[3]:
-            raise _lib.MpgError("conv2d_fused_wide: post_add %s does not match output" % (tuple(pa.shape),))
-    y, y8, outs = _alloc_outputs(shape, dev, want_f32, want_g8 or bool(pixel_norm), out, "conv2d_fused_wide")
-    for segments, co_off in chunks:
-        cw = segments[0].packed.cout
-        d = _conv_desc(segments, out_hw, bias[co_off:co_off + cw].contiguous() if bias is not None else None, act, leak)
-        if pa is not None:
-            d.post_add, d.post_add_stride, d.post_add_coff = pa.data_ptr(), pa.shape[3], post_add_coff + co_off
-        d.y, d.y_g8 = _ptr(None if pixel_norm else y), _ptr(y8)
-        _lib.check(lib.mpg_conv2d_fused_window(_stream(), ctypes.byref(d), c_total, co_off), "mpg_conv2d_fused_window")
+    if post_add is not None and pixel_norm:
+        raise _lib.MpgError("conv2d_fused_wide: post_add follows the pixel norm, which runs behind the window launches")
+    y, y8, outs = _launch_windows("conv2d_fused_wide", "mpg_conv2d_fused_window", (), chunks, out_hw, c_total, (1, c_total),
+                                  bias, act, leak, want_f32, want_g8, out, post_add, post_add_coff, g8_only=bool(pixel_norm))
     if pixel_norm:
-        _lib.check(lib.mpg_pixel_norm_g8(_stream(), _ptr(y8.buf), n, h, w, c_total, pn_eps, _ptr(y)), "mpg_pixel_norm_g8")
-        outs = [o for o in (y, y8 if want_g8 else None) if o is not None]
+        _lib.check(_lib.load().mpg_pixel_norm_g8(_stream(), _ptr(y8.buf), y8.n, y8.h, y8.w, c_total, pn_eps, _ptr(y)),
+                   "mpg_pixel_norm_g8")
     return outs[0] if len(outs) == 1 else tuple(outs)
 
 

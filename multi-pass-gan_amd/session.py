@@ -15,6 +15,7 @@ Fusion rules (all arithmetic stays in the kernels of libmpgan_hip.so):
   * a fused convolution of more than 128 outputs (the 256-wide first level of the 8x generators at the driver's
     defaults) is one step of ``mpg_conv2d_fused_window`` launches into the same tensors, its pixel norm one
     ``mpg_pixel_norm_g8`` pass behind them (``ops.conv2d_fused_wide``).
+The matchers only recognise these patterns; ``Session._fused_step`` makes the step of every one of them.
 Everything else falls back to one kernel per node.
 """
 import re
@@ -103,16 +104,20 @@ def _is_pow2(v):
     return v >= 1 and (v & (v - 1)) == 0
 
 
-def _up_info(up):
-    """the fused upsample (up_log2, up_x_only) of a segment as plan_summary shows it: `up_x_only` appears next to
-    `up_log2` where it is set, so the plans of networks without a column-only upsample read as they always did"""
-    return dict(up_log2=up[0], up_x_only=1) if up[1] else dict(up_log2=up[0])
+def _segments_info(segs):
+    """resolved segments (Session._segments_of) as plan_summary shows them.  `up_x_only` appears next to `up_log2` where
+    it is set, so the plans of networks without a column-only upsample read as they always did"""
+    return [dict(src=src.name, src_id=src.id, c_off=c_off, cin=cin, w_off=w_off, up_log2=up[0],
+                 **(dict(up_x_only=1) if up[1] else {}),
+                 kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
+            for (src, c_off, up, term, w_off, cin) in segs]
 
 
 class _Step(object):
     """One entry of a launch plan: `run(env)` computes `node` from the env entries of `deps`.  A fused convolution
-    launch also carries `info` (its plan_summary entry), `emit` (which output formats it writes) and, where it may
-    still become half of a small pair, `parts` (its operands); these are None on every other step."""
+    step (Session._fused_step) also carries `info` (its plan_summary entry), `emit` (which output formats it writes)
+    and, where it is one plain launch and so may still become half of a small pair, `parts` (its operands); these are
+    None on every other step."""
 
     __slots__ = ("node", "deps", "run", "info", "emit", "parts")
 
@@ -213,53 +218,41 @@ class Session(object):
         return node
 
     # ------------------------------------------------------------------ tensor formats
-    # A fused convolution can emit fp32 NHWC and / or the G8 layout (in either flavour) its consumers
-    # DMA from; its env entry is a dict {"f32": tensor | None, "g8": {flavour: G8}}.  Every other
-    # node holds an fp32 tensor.
+    # A fused convolution can emit fp32 NHWC and / or the G8 layout its consumers DMA from; its env
+    # entry is a dict {"f32": tensor | None, "g8": G8 | None}.  Every other node holds an fp32 tensor.
     @staticmethod
     def _f32(env, node):
         v = env[node.id]
         if isinstance(v, dict):
             if v["f32"] is None:
-                v["f32"] = ops.from_g8(v["g8"][ops.G8_F16])
+                v["f32"] = ops.from_g8(v["g8"])
             return v["f32"]
         return v
 
     @staticmethod
-    def _g8(env, node, c_off, cin, flavour):
+    def _g8(env, node, c_off, cin):
         """(G8 tensor, channel offset inside it) holding channels [c_off, c_off+cin) of `node`"""
         v = env[node.id]
-        if isinstance(v, dict) and flavour in v["g8"] and c_off % 8 == 0:
-            return v["g8"][flavour], c_off
-        key = ("g8", node.id, c_off, cin, flavour)
+        if isinstance(v, dict) and v["g8"] is not None and c_off % 8 == 0:
+            return v["g8"], c_off
+        key = ("g8", node.id, c_off, cin)
         g = env.get(key)
         if g is None:
-            g = ops.to_g8(Session._f32(env, node), c_off, cin, flavour)
+            g = ops.to_g8(Session._f32(env, node), c_off, cin)
             env[key] = g
         return g, 0
 
     # ------------------------------------------------------------------ compile
     def _compile(self, fetch):
-        consumers = {}
-        seen = set()
-
-        def visit(n):
-            if n.id in seen:
-                return
-            seen.add(n.id)
-            for i in n.inputs:
-                consumers.setdefault(i.id, []).append(n)
-                visit(i)
-
-        visit(fetch)
+        consumers = G.consumers([fetch])
         plan = _Plan()
         done = set()
         fused = []             # the steps that are fused convolutions, consumer before producer
         need_f32 = {fetch.id}  # nodes somebody reads as fp32 NHWC
-        need_g8 = set()        # (node id, flavour) of fused outputs read by another fused convolution
+        need_g8 = set()        # fused outputs read by another fused convolution
 
         def single_use(n):
-            return len(consumers.get(n.id, [])) == 1 and n is not fetch
+            return G.sole_reader(consumers, n) is not None
 
         def emit(n):
             if n.id in done:
@@ -286,21 +279,20 @@ class Session(object):
             plan.steps.append(step)
 
         emit(fetch)
-        absorbed = self._fuse_small_pairs(fused, consumers, fetch)
+        absorbed = self._fuse_small_pairs(fused, single_use)
         plan.steps = [s for s in plan.steps if s.node.id not in absorbed]
         fused = [s for s in fused if s.node.id not in absorbed]
         fused_ids = set(s.node.id for s in fused)
         for s in fused:
-            fl = ops.flavour_for(s.info["prec"])
             for seg in s.info["segments"]:
                 if seg["src_id"] in fused_ids and seg["c_off"] % 8 == 0:
-                    need_g8.add((seg["src_id"], fl))
+                    need_g8.add(seg["src_id"])
                 else:
                     need_f32.add(seg["src_id"])
             if s.info["post_add_id"] is not None:
                 need_f32.add(s.info["post_add_id"])
         for s in fused:
-            s.emit["g8"] = (s.node.id, ops.G8_F16) in need_g8
+            s.emit["g8"] = s.node.id in need_g8
             s.emit["f32"] = s.node.id in need_f32 or not s.emit["g8"]
         # variables, placeholders and the fetch stay alive; everything else dies after its last reader
         last_use = {}
@@ -315,7 +307,7 @@ class Session(object):
                 plan.free_after[idx].append(nid)
         return plan
 
-    # ---- what the three fused launch kinds share ------------------------------------------------------------
+    # ---- the step of a fused convolution --------------------------------------------------------------------
     @staticmethod
     def _dst(env, emit, shape):
         """the buffer run_device was given for this step's fp32 result, viewed as [N] + shape[1:], or None"""
@@ -327,10 +319,83 @@ class Session(object):
         """the env entry of a fused launch from what its ops call returned: fp32 first, then G8, as `emit` asked"""
         res = list(res) if isinstance(res, tuple) else [res]
         f32 = res.pop(0) if emit["f32"] else None
-        return {"f32": f32, "g8": {ops.G8_F16: res.pop(0)} if emit["g8"] else {}}
+        return {"f32": f32, "g8": res.pop(0) if emit["g8"] else None}
+
+    def _fused_step(self, n, terms, segs, cout, out_hw, act=None, leak=0.2, pn=False, pn_eps=1e-8, post_add=None, d2s=False):
+        """The step that computes node `n` as a fused convolution of what the matchers found: `terms` summed over their
+        resolved segments `segs` (cout outputs on out_hw pixels), then act / pixel norm / post-add, stored plainly or, with
+        d2s, through depth_to_space(2).  Returns None where no launch takes it.
+        The outputs run as windows [(first channel, width)], one launch each with its own precision and its own packed
+        weights: one window up to 128 plain outputs (mpg_conv2d_fused, the only entry that reaches the small-channel
+        kernel), ops.wide_chunks above that (ops.conv2d_fused_wide, the pixel norm behind the last window), 128 at a time
+        under a depth-to-space store (ops.conv2d_fused_d2s)."""
+        if d2s:
+            windows = [(co, min(128, cout - co)) for co in range(0, cout, 128)]
+        else:
+            windows = ops.wide_chunks(cout) if cout > 128 else [(0, cout)]
+        single = not d2s and len(windows) == 1
+        if len(segs) > _lib.MAX_SEG:
+            return None
+        if len(windows) > 1 and pn and post_add is not None:      # the post-add follows the norm, which follows the last window
+            return None
+        lead = terms[0].conv.inputs[1].attrs["var"]
+        precs = [self._launch_prec(lead, cw, segs) for _, cw in windows]
+        if d2s and ops.PREC_F16F6 in precs:      # the F16F6 kernel has no depth-to-space store: conv + standalone shuffle
+            return None
+        launch = ops.conv2d_fused_d2s if d2s else ops.conv2d_fused if single else ops.conv2d_fused_wide
+        emit = {"f32": True, "g8": False}
+
+        def run(env):
+            if single:
+                args = dict(segments=self._segments(env, segs, precs[0]))
+            else:
+                args = dict(c_total=cout, chunks=[(self._segments(env, segs, prec, win), win[0])
+                                                  for win, prec in zip(windows, precs)])
+            args.update(out_hw=out_hw, bias=self._bias_for(terms), act=act, leak=leak, want_f32=emit["f32"],
+                        want_g8=emit["g8"])
+            if not d2s:      # the depth-to-space store takes neither (_match_d2s finds none)
+                args.update(pixel_norm=pn, pn_eps=pn_eps,
+                            post_add=self._f32(env, post_add) if post_add is not None else None)
+            # the measurement hook (Session.tap) re-issues ops.conv2d_fused(**tapped): single plain launches only
+            tapped = single and self.tap is not None and self.tap in lead
+            if tapped:
+                self.tapped = args
+            timed = tapped and self.tap_events is not None
+            if timed:
+                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                ev[0].record()
+            res = launch(out=self._dst(env, emit, n.shape), **args)
+            if timed:
+                ev[1].record()
+                self.tap_events.append(ev)
+            return self._boxed(res, emit)
+
+        info = {
+            "kind": "conv2d_fused_d2s" if d2s else "conv2d_fused", "cout": cout // 4 if d2s else cout, "act": act,
+            "pixel_norm": pn, "prec": precs[0], "post_add": post_add.name if post_add is not None else None,
+            "post_add_id": post_add.id if post_add is not None else None, "segments": _segments_info(segs),
+        }
+        if d2s:
+            info["conv_cout"] = cout
+        if not single:
+            info["launches"] = len(windows)
+        parts = dict(segs=segs, terms=terms, act=act, leak=leak, pn=pn, post_add=post_add, prec=precs[0], cout=cout,
+                     out_hw=out_hw) if single else None
+        deps = [sg[0] for sg in segs] + ([post_add] if post_add is not None else [])
+        return _Step(n, deps, run, info, emit, parts)
+
+    def _segments(self, env, segs, prec, window=None):
+        """the ops.Segment objects of one launch at precision `prec`: every resolved segment with its G8 source from `env`
+        and its weights packed for the output channels `window` (all of them when None)"""
+        out = []
+        for (src, c_off, up, term, w_off, cin) in segs:
+            pk = self._packed_for(term, w_off, cin, prec, window)
+            g8, off = self._g8(env, src, c_off, cin)
+            out.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
+        return out
 
     # ---- residual blocks of small-channel convolutions: two launches -> one -------------------------------
-    def _fuse_small_pairs(self, fused, consumers, fetch):
+    def _fuse_small_pairs(self, fused, single_use):
         """relu(convB(relu(convA(x))) + conv1x1(x)) with <= 8 channels everywhere (resBlock 0 and 3 of gen_resnet,
         multipassGAN-4x.py:505-526,560,564) was planned as two conv_small launches with the middle tensor going through
         HBM; here the step of launch B becomes one mpg_conv2d_small_pair call and launch A is dropped: returns the node
@@ -346,7 +411,7 @@ class Session(object):
                 continue
             s1 = by_id[src1.id]
             n1, p1 = s1.node, s1.parts
-            if (p1 is None or n1 is fetch or len(consumers.get(n1.id, [])) != 1 or p1["pn"] or p1["post_add"] is not None
+            if (p1 is None or not single_use(n1) or p1["pn"] or p1["post_add"] is not None
                     or len(p1["segs"]) != 1 or p1["prec"] != p2["prec"] or p1["cout"] != cin_b):
                 continue
             src0, c_off0, up0, term_a, w_off_a, cin_a = p1["segs"][0]
@@ -375,7 +440,7 @@ class Session(object):
             pk_a = self._packed_for(term_a, 0, cin_a, prec)
             pk_b = self._packed_for(term_b, 0, p1["cout"], prec)
             pk_s = self._packed_for(term_s, 0, cin_a, prec) if term_s is not None else None
-            g8, off = self._g8(env, src0, c_off0, cin_a, ops.G8_F16)
+            g8, off = self._g8(env, src0, c_off0, cin_a)
             return self._boxed(ops.conv2d_small_pair(
                 g8, off, up0[0], pk_a, pk_b, pk_s, p2["out_hw"], up_x_only=up0[1], bias_a=self._bias_for(p1["terms"]), act_a=p1["act"],
                 leak_a=p1["leak"], bias_b=self._bias_for(p2["terms"]), act_b=p2["act"], leak_b=p2["leak"],
@@ -442,84 +507,7 @@ class Session(object):
             if s is None:
                 return None
             segs.extend(s)
-        if len(segs) > _lib.MAX_SEG:
-            return None
-        deps = [s[0] for s in segs] + ([post_add] if post_add is not None else [])
-        out_hw = (n.shape[1], n.shape[2])
-
-        lead = terms[0].conv.inputs[1].attrs["var"]
-        if cout > 128:
-            if pn and post_add is not None:      # the post-add follows the pixel norm, which follows the last window
-                return None
-            return self._wide_step(n, deps, terms, segs, lead, cout, out_hw, act, leak, pn, pn_eps, post_add)
-        prec = self._launch_prec(lead, cout, segs)
-
-        emit = {"f32": True, "g8": False}
-
-        def run(env):
-            seg_objs = []
-            for (src, c_off_src, up, term, w_off, cin) in segs:
-                pk = self._packed_for(term, w_off, cin, prec)
-                g8, off = self._g8(env, src, c_off_src, cin, ops.flavour_for(prec))
-                seg_objs.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
-            bias = self._bias_for(terms)
-            pa = self._f32(env, post_add) if post_add is not None else None
-            if self.tap is not None and self.tap in lead:
-                self.tapped = dict(segments=seg_objs, out_hw=out_hw, bias=bias, act=act, leak=leak, pixel_norm=pn,
-                                   pn_eps=pn_eps, post_add=pa, want_f32=emit["f32"], want_g8=emit["g8"])
-            timed = self.tap is not None and self.tap_events is not None and self.tap in lead
-            if timed:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            res = ops.conv2d_fused(seg_objs, out_hw, bias=bias, act=act, leak=leak, pixel_norm=pn, pn_eps=pn_eps,
-                                   post_add=pa, want_f32=emit["f32"], want_g8=emit["g8"], out=self._dst(env, emit, n.shape))
-            if timed:
-                ev[1].record()
-                self.tap_events.append(ev)
-            return self._boxed(res, emit)
-
-        parts = dict(segs=segs, terms=terms, act=act, leak=leak, pn=pn, post_add=post_add, prec=prec, cout=cout, out_hw=out_hw)
-        info = {
-            "kind": "conv2d_fused", "cout": cout, "act": act, "pixel_norm": pn, "prec": prec,
-            "post_add": post_add.name if post_add is not None else None,
-            "post_add_id": post_add.id if post_add is not None else None,
-            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, w_off=w_off, **_up_info(up),
-                              kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
-                         for (src, c_off_src, up, term, w_off, cin) in segs],
-        }
-        return _Step(n, deps, run, info, emit, parts)
-
-    def _wide_step(self, n, deps, terms, segs, lead, cout, out_hw, act, leak, pn, pn_eps, post_add):
-        """the step of a fused convolution of more than 128 outputs: one window launch per entry of ops.wide_chunks, each
-        with its own precision and its own packed weights (output channels [co, co + cw) of every segment, the folded
-        batch-norm scale sliced with them), the pixel norm behind the last one (ops.conv2d_fused_wide)"""
-        chunks = ops.wide_chunks(cout)
-        precs = [self._launch_prec(lead, cw, segs) for _, cw in chunks]
-        emit = {"f32": True, "g8": False}
-
-        def run(env):
-            launches = []
-            for (co, cw), prec in zip(chunks, precs):
-                seg_objs = []
-                for (src, c_off_src, up, term, w_off, cin) in segs:
-                    pk = self._packed_chunk(term, w_off, cin, prec, co, cw)
-                    g8, off = self._g8(env, src, c_off_src, cin, ops.flavour_for(prec))
-                    seg_objs.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
-                launches.append((seg_objs, co))
-            pa = self._f32(env, post_add) if post_add is not None else None
-            return self._boxed(ops.conv2d_fused_wide(
-                launches, out_hw, cout, bias=self._bias_for(terms), act=act, leak=leak, pixel_norm=pn, pn_eps=pn_eps,
-                post_add=pa, want_f32=emit["f32"], want_g8=emit["g8"], out=self._dst(env, emit, n.shape)), emit)
-
-        info = {
-            "kind": "conv2d_fused", "cout": cout, "launches": len(chunks), "act": act, "pixel_norm": pn, "prec": precs[0],
-            "post_add": post_add.name if post_add is not None else None,
-            "post_add_id": post_add.id if post_add is not None else None,
-            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=cin, w_off=w_off, **_up_info(up),
-                              kernel=tuple(term.conv.inputs[1].shape[:2]), weight=term.conv.inputs[1].attrs["var"])
-                         for (src, c_off_src, up, term, w_off, cin) in segs],
-        }
-        return _Step(n, deps, run, info, emit)
+        return self._fused_step(n, terms, segs, cout, (n.shape[1], n.shape[2]), act, leak, pn, pn_eps, post_add)
 
     def _launch_prec(self, lead, cout, segs):
         """the precision of a fused launch of `cout` outputs over segments `segs` whose leading weight is `lead`"""
@@ -541,7 +529,7 @@ class Session(object):
     # ---- pixel shuffle: depth_to_space(2) of a linear 1x1 convolution, the shuffle in the convolution's store -------
     def _match_d2s(self, n, single_use):
         """depth_to_space(bias_add(conv2d 1x1)) with C = 4C' / 4 a multiple of 8 (GAN.pixel_shuffle, GAN.py:554-560):
-        one mpg_conv2d_fused_d2s launch per 128 output channels, whatever the width of the convolution"""
+        one step of mpg_conv2d_fused_d2s launches (_fused_step), whatever the width of the convolution"""
         if n.op != "depth_to_space" or n.attrs["r"] != 2:
             return None
         bias = n.inputs[0]
@@ -555,35 +543,9 @@ class Session(object):
             return None
         term = _Term(conv, bias, None)
         segs = self._segments_of(term)
-        if segs is None or len(segs) > _lib.MAX_SEG:
+        if segs is None:
             return None
-        lead = conv.inputs[1].attrs["var"]
-        chunks = [(co, min(128, c_total - co)) for co in range(0, c_total, 128)]
-        precs = [self._launch_prec(lead, cw, segs) for _, cw in chunks]
-        if ops.PREC_F16F6 in precs:      # the F16F6 kernel has no depth-to-space store: conv + standalone shuffle
-            return None
-        out_hw = (conv.shape[1], conv.shape[2])
-        emit = {"f32": True, "g8": False}
-
-        def run(env):
-            launches = []
-            for (co, cw), prec in zip(chunks, precs):
-                seg_objs = []
-                for (src, c_off_src, up, t, w_off, ci) in segs:
-                    pk = self._packed_chunk(t, w_off, ci, prec, co, cw)
-                    g8, off = self._g8(env, src, c_off_src, ci, ops.flavour_for(prec))
-                    seg_objs.append(ops.Segment(g8, pk, off, up[0], up_x_only=up[1]))
-                launches.append((seg_objs, co))
-            return self._boxed(ops.conv2d_fused_d2s(launches, out_hw, c_total, bias=self._bias_for([term]), want_f32=emit["f32"],
-                                                    want_g8=emit["g8"], out=self._dst(env, emit, n.shape)), emit)
-
-        info = {
-            "kind": "conv2d_fused_d2s", "cout": c_total // 4, "conv_cout": c_total, "launches": len(chunks), "act": None,
-            "pixel_norm": False, "prec": precs[0], "post_add": None, "post_add_id": None,
-            "segments": [dict(src=src.name, src_id=src.id, c_off=c_off_src, cin=ci, w_off=w_off, **_up_info(up), kernel=(1, 1),
-                              weight=lead) for (src, c_off_src, up, t, w_off, ci) in segs],
-        }
-        return _Step(n, [s[0] for s in segs], run, info, emit)
+        return self._fused_step(n, [term], segs, c_total, (conv.shape[1], conv.shape[2]), d2s=True)
 
     def plan_summary(self, fetch):
         """the launch plan of `fetch` as a list of dicts (no GPU needed): one entry per kernel launch"""
@@ -685,28 +647,20 @@ class Session(object):
         self._folded[key] = res
         return res
 
-    def _packed_for(self, term, w_off, cin, prec):
-        key = ("pack", term.conv.id, w_off, cin, prec)
+    def _packed_for(self, term, w_off, cin, prec, window=None):
+        """the packed weights of input channels [w_off, w_off + cin) of `term`, batch-norm scale folded in; with `window`
+        = (co, cw) output channels [co, co + cw) alone, packed as a launch of their own with those channels of the scale"""
+        key = ("pack", term.conv.id, w_off, cin, prec, window)
         pk = self._packed.get(key)
         if pk is None:
             w = self.vars.get(term.conv.inputs[1].attrs["var"])
             scale, _ = self._bn_scale_shift(term)
+            if window is not None:
+                co, cw = window
+                w = w[..., co:co + cw].contiguous()
+                scale = scale[co:co + cw].contiguous() if scale is not None else None
             pk = ops.pack_conv_weights(w, wscale=term.conv.attrs["wscale"], cout_scale=scale, c_off=w_off, cin=cin,
                                        prec=prec)
-            self._packed[key] = pk
-        return pk
-
-    def _packed_chunk(self, term, w_off, cin, prec, co, cw):
-        """output channels [co, co + cw) of a wide convolution, packed as a launch of their own, with those channels of
-        the folded batch-norm scale"""
-        key = ("pack", term.conv.id, w_off, cin, prec, co, cw)
-        pk = self._packed.get(key)
-        if pk is None:
-            w = self.vars.get(term.conv.inputs[1].attrs["var"])[..., co:co + cw].contiguous()
-            scale, _ = self._bn_scale_shift(term)
-            if scale is not None:
-                scale = scale[co:co + cw].contiguous()
-            pk = ops.pack_conv_weights(w, wscale=term.conv.attrs["wscale"], cout_scale=scale, c_off=w_off, cin=cin, prec=prec)
             self._packed[key] = pk
         return pk
 
@@ -798,7 +752,9 @@ class Session(object):
         raise G.GraphError("no HIP lowering for node %r (inputs %r)" % (n, n.inputs))
 
     def _match_direct(self, n, single_use):
-        """[act](bn?(bias_add?(conv2d | matmul))) on the vector-ALU kernel: strided convs, cout > 512, FC."""
+        """[act](bn?(bias_add?(conv2d | matmul | conv2d_transpose))) outside the fused step: strided convolutions, more
+        than ops.WIDE_MAX_COUT = 512 outputs and fully connected layers on the vector-ALU kernels, transposed
+        convolutions through ops.conv2d_transpose."""
         m = G.match_layer(n, single_use, ("conv2d", "matmul", "conv2d_transpose"))
         if m is None:
             return None

@@ -26,8 +26,8 @@ TRAINABLE_KINDS = ("weight", "bias", "gamma", "beta")
 
 
 def _mfma_ok(kh, kw, width, stride):
-    """the fused MFMA kernel takes stride-1 filters up to 7x7 and 128 output channels per launch;
-    wider layers (the 256-wide d_c4, multipassGAN-4x.py:614) run as two launches"""
+    """the fused MFMA kernel takes stride-1 filters up to 7x7; a launch covers up to 128 output channels, and layers of
+    up to 512 (the 256-wide d_c4, multipassGAN-4x.py:614) run as one launch per 128 (_mfma_conv)"""
     return stride == (1, 1) and kh <= 7 and kw <= 7 and width <= 512
 
 
@@ -47,7 +47,7 @@ def _wgrad_prec(prec):
     return prec if prec == ops.PREC_F16X1 else ops.PREC_F16X3
 
 
-def _cached_g8(t, prec, scaled):
+def _cached_g8(t, scaled):
     """(G8 form of t, the abs-max it was scaled by or None), kept on the tensor object.
     scaled False: the plain hi/lo split of an activation -- a block's input feeds two convolutions (first conv and 1x1
     shortcut), the second one finds the form the first one made.  scaled True: t times the power of two of its abs-max -- a
@@ -63,7 +63,7 @@ def _cached_g8(t, prec, scaled):
     if tag is None or tag[2:] != (t._version, t.data_ptr(), tuple(t.shape)):
         tc = t.detach().contiguous()
         am = ops.absmax(tc) if scaled else None
-        tag = (ops.to_g8(tc, 0, tc.shape[3], ops.flavour_for(prec), amax=am), am, t._version, t.data_ptr(), tuple(t.shape))
+        tag = (ops.to_g8(tc, 0, tc.shape[3], amax=am), am, t._version, t.data_ptr(), tuple(t.shape))
         try:
             if tags is None:
                 tags = t._mpg_g8 = {}
@@ -93,10 +93,10 @@ def _mfma_conv(x, w, wscale, prec, bias=None, act=None, leak=0.2, pad_hi=0, resc
     if not rescale:
         amax = None
         if isinstance(x, torch.Tensor):
-            x = _cached_g8(x.contiguous(), prec, False)[0]
+            x = _cached_g8(x.contiguous(), False)[0]
     elif isinstance(x, torch.Tensor):
         amax = ops.absmax(x) if amax is None else amax
-        x = ops.to_g8(x.contiguous(), 0, x.shape[3], ops.flavour_for(prec), amax=amax)
+        x = ops.to_g8(x.contiguous(), 0, x.shape[3], amax=amax)
     for c0 in range(0, cout, 128):
         c1 = min(cout, c0 + 128)
         wc = w if (c0 == 0 and c1 == cout) else w[..., c0:c1].contiguous()
@@ -180,7 +180,7 @@ class ConvLayerFn(torch.autograd.Function):
         d_g8 = None
         if x_g8 is not None and wgrad_mm:
             # one scaled hi/lo conversion of d feeds both gradient kernels; x comes from the forward launch
-            d_g8 = ops.to_g8(d, 0, cout, ops.flavour_for(cfg["prec"]), amax=d_amax)
+            d_g8 = ops.to_g8(d, 0, cout, amax=d_amax)
         if ctx.needs_input_grad[1]:
             if d_g8 is not None:
                 dw = train_ops.conv2d_wgrad_g8(x_g8, d_g8, kh, kw, wscale, _wgrad_prec(cfg["prec"]), None, d_amax)
@@ -218,7 +218,7 @@ def _conv_fwd(x, w, b, cfg):
             xd.shape[0], 1, 1, cout)
     if _mfma_ok(kh, kw, cout, cfg["stride"]):
         if cfg.get("rescale_fwd") and x.dim() == 4:
-            g8, am = _cached_g8(x, cfg["prec"], True)
+            g8, am = _cached_g8(x, True)
             return _mfma_conv(g8, w.contiguous(), cfg["wscale"], cfg["prec"], b, rescale=True, amax=am)
         return _mfma_conv(x.detach().contiguous(), w.contiguous(), cfg["wscale"], cfg["prec"], b)
     return ops.conv2d_direct(x.detach().contiguous(), w.contiguous(), cfg["stride"], cfg["wscale"], None, b)
@@ -227,15 +227,15 @@ def _conv_fwd(x, w, b, cfg):
 def _conv_dgrad(dy, w, cfg, hw):
     kh, kw, cin, cout = w.shape
     if _mfma_ok(kh, kw, cin, cfg["stride"]) and not cfg.get("fc"):
-        g8, am = _cached_g8(dy, cfg["prec"], True)
+        g8, am = _cached_g8(dy, True)
         return _mfma_conv(g8, _dgrad_weights(w), cfg["wscale"], cfg["prec"], pad_hi=1, rescale=True, amax=am)
     return train_ops.conv2d_dgrad(dy.detach(), w, hw, cfg["stride"], cfg["wscale"])
 
 
 def _conv_wgrad(x, dy, cfg, kh, kw):
     if train_ops.wgrad_mfma_ok(kh, kw, cfg["stride"]) and not cfg.get("fc"):
-        xg, xam = _cached_g8(x, cfg["prec"], True)
-        dg, dam = _cached_g8(dy, cfg["prec"], True)
+        xg, xam = _cached_g8(x, True)
+        dg, dam = _cached_g8(dy, True)
         return train_ops.conv2d_wgrad_g8(xg, dg, kh, kw, cfg["wscale"], _wgrad_prec(cfg["prec"]), xam, dam)
     return train_ops.conv2d_wgrad(x.detach(), dy.detach(), kh, kw, cfg["stride"], cfg["wscale"])
 
@@ -634,48 +634,18 @@ class TrainSession(object):
                 self._scalar_feeds[node.node] = float(t)
             else:
                 env[node.id] = torch.as_tensor(t, dtype=torch.float32, device=self.device)
-        users = self._count_users(fetches)
-        self._consumers = self._consumer_map(fetches) if self.eval_mode else {}
+        cons = G.consumers(fetches)
+        users = {nid: len(readers) for nid, readers in cons.items()}      # a fetch counts as a reader
+        self._consumers = cons if self.eval_mode else {}      # evaluation asks whether a layer's only reader takes G8
         # the UPDATE_OPS of tf.contrib.layers.batch_norm (multipassGAN-4x.py:773-776,889-899) run inside
         # mpg_bn_train_fwd_ordered: every evaluated batch-norm layer advances its moving averages once
         return [self._eval(f, env, users) for f in fetches]
 
-    def _count_users(self, fetches):
-        users, seen, stack = {}, set(), list(fetches)
-        for f in fetches:
-            users[f.id] = users.get(f.id, 0) + 1
-        while stack:
-            n = stack.pop()
-            if n.id in seen:
-                continue
-            seen.add(n.id)
-            for i in n.inputs:
-                users[i.id] = users.get(i.id, 0) + 1
-                stack.append(i)
-        return users
-
-    def _consumer_map(self, fetches):
-        """node id -> the nodes that read it (a fetched node also lists None): evaluation asks whether a layer's only reader
-        is a convolution that takes the G8 form"""
-        cons, seen, stack = {}, set(), list(fetches)
-        for f in fetches:
-            cons.setdefault(f.id, []).append(None)
-        while stack:
-            n = stack.pop()
-            if n.id in seen:
-                continue
-            seen.add(n.id)
-            for i in n.inputs:
-                cons.setdefault(i.id, []).append(n)
-                stack.append(i)
-        return cons
-
     def _feeds_one_mfma_conv(self, n):
         """is the only reader of node n a stride-1 convolution of the matrix-core kernel reading it as its input?"""
-        readers = self._consumers.get(n.id, [])
-        if len(readers) != 1 or readers[0] is None or readers[0].op != "conv2d" or readers[0].inputs[0] is not n:
+        r = G.sole_reader(self._consumers, n)
+        if r is None or r.op != "conv2d" or r.inputs[0] is not n:
             return False
-        r = readers[0]
         kh, kw, _, cout = self.graph.variables[r.inputs[1].attrs["var"]].shape
         return _mfma_ok(kh, kw, cout, tuple(r.attrs["stride"]))
 

@@ -3,9 +3,10 @@ the first growing level is 256 channels wide; those layers run as window launche
 narrower network keeps the plan it had."""
 import json
 import os
-import re
 
 import pytest
+
+from plan_cases import norm as _norm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -75,18 +76,6 @@ def test_planner_cap_and_pack_limit(mpg):
         G.reset_default_graph()
     assert kinds[512] == [("conv2d_fused", 4)] and kinds[520] == [("act", None)]
     assert _lib.load().mpg_conv_pack_size(3, 3, 16, 136, 3) == 0
-
-
-def _norm(plan):
-    out = []
-    for e in plan:
-        d = {k: v for k, v in e.items() if k not in ("node", "post_add", "post_add_id", "segments")}
-        d["op"] = re.sub(r"_\d+$", "", e["node"])
-        d["has_post_add"] = e.get("post_add") is not None
-        d["segments"] = [{k: (list(v) if isinstance(v, tuple) else v) for k, v in s.items() if k not in ("src", "src_id")}
-                         for s in e.get("segments", [])]
-        out.append(d)
-    return out
 
 
 @pytest.mark.parametrize("prec", [2, 3])
