@@ -62,7 +62,7 @@ for name, default in [
         ("simLowHeight", 64), ("overlappedpixel", 3), ("startIndex", 0), ("useAvgDepool", False), ("avgMode", 0),
         ("velScale", 1.0), ("upsamplingMode", 2), ("upsampledData", False), ("sliceMode", 0), ("interpMode", 1),
         ("genUni", False), ("setVelZero", False), ("upsampleFirst", True), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("deviceTiles", 1)]:
+        ("deviceTiles", 1), ("uniCodec", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -367,6 +367,7 @@ for layerno in range(frame_min, frame_max):
         head, _ = uniio.readUni(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, layerno))
         head['dimX'] = head['dimY'] = simSizeHigh
         head['dimZ'] = slices                                                # 2x2x1: the slices the file holds (see above)
-        uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/' % fromSim + name % layerno, head, vol)
+        uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/' % fromSim + name % layerno, head, vol,
+                                 codec="device" if int(P["uniCodec"]) else "host")
     print('')
 print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))

@@ -58,7 +58,8 @@ for name, default in [
         ("startingIter", 0), ("loadEmas", False), ("useVelInTDisc", False), ("upsampleMode", 1), ("lossScaling", False),
         ("stageIter", 25000), ("decayIter", 25000), ("maxFms", 256), ("use_wgan_gp", False), ("use_res_net", False),
         ("use_mb_stddev", False), ("deviceTiles", 1), ("use_LSGAN", False), ("startFms", 512), ("filterSize", 3), ("outNNTestNo", 17),
-        ("firstNNArch", False), ("gDrop", False), ("add_adj_idcs", False), ("gpu", 2), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3")]:
+        ("firstNNArch", False), ("gDrop", False), ("add_adj_idcs", False), ("gpu", 2), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
+        ("uniCodec", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -139,7 +140,8 @@ def output_main():
         if gen_uni:
             head = dict(head_0)
             head['dimX'] = head['dimY'] = head['dimZ'] = s
-            uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol)
+            uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol,
+                                     codec="device" if int(P["uniCodec"]) else "host")
     print('Test finished, %d volumes written to %s.' % (f1 - f0, sims))
 
 

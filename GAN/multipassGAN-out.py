@@ -56,6 +56,7 @@ transposeAxis = int(ph.getParam("transposeAxis", 0))
 gpu = ph.getParam("gpu", "0")
 synthWeights = int(ph.getParam("synthWeights", 0))          # extension: seeded random weights if no checkpoint
 prec = ph.getParam("prec", "2")                             # extension: 2 = f16f6 (default), 3 = f16x3 (fp32-grade)
+uniCodec = int(ph.getParam("uniCodec", 0))                  # extension: .uni deflate on 0 = the host (zlib), 1 = the GPU
 nets = []
 for k in (1, 2, 3):
     nets.append(dict(
@@ -133,6 +134,7 @@ for layerno in range(frame_min, frame_max):
     if generateUni:
         head = dict(head_0)
         head['dimX'] = head['dimY'] = head['dimZ'] = simSizeHigh
-        uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/source_%04d.uni' % (fromSim, layerno), head, vol)
+        uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/source_%04d.uni' % (fromSim, layerno), head, vol,
+                                 codec="device" if uniCodec else "host")
         print('stored .uni file')
 print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))

@@ -304,6 +304,30 @@ int mpg_depth_to_space(mpg_stream_t stream, const float* x, int n, int h, int w,
 int mpg_space_to_depth(mpg_stream_t stream, const float* x, int n, int h, int w, int c, int r, float* y);
 
 /* ------------------------------------------------------------------------
+ * Device-side DEFLATE of a .uni payload: replaces the gzip.open(...).write(content.tobytes()) of the reference writer
+ * (tools_wscale/uniio.py:91-123), whose zlib pass over the whole volume is the longest step of a 4x frame.
+ * The payload is cut into units of MPG_DEFLATE_UNIT bytes.  Every unit becomes a byte-aligned, NON-final raw DEFLATE
+ * stream (RFC 1951): one fixed-Huffman block of word-granular tokens (a word equal to its predecessor extends a run,
+ * runs become matches of distance 4 and length 4 * min(r, 64), every other word is four literals) closed by an empty
+ * stored block, or, where that would be longer, one stored block.  Unit streams concatenate into one deflate body;
+ * the caller ends a body with an empty final block (bytes 03 00).
+ * ------------------------------------------------------------------------ */
+#define MPG_DEFLATE_UNIT 32768                       /* payload bytes per unit */
+#define MPG_DEFLATE_SLOT (MPG_DEFLATE_UNIT + 16)     /* workspace bytes per unit: the stored form (5 + unit), 16-byte slots */
+#define MPG_DEFLATE_SLAB (64 << 20)                  /* most payload bytes per encode call */
+/* bytes of slot workspace for n_bytes of payload (uniio.py:91-123) */
+size_t mpg_deflate_ws_bytes(size_t n_bytes);
+/* encode n_bytes (a positive multiple of 4, at most MPG_DEFLATE_SLAB; src 16-byte aligned) of payload (uniio.py:91-123):
+ * unit u's stream goes to slots + u * MPG_DEFLATE_SLOT (slots: mpg_deflate_ws_bytes(n_bytes), 16-byte aligned),
+ * its length to sizes[u], and the CRC-32 (zlib.crc32) of its input bytes to crcs[u]; ceil(n_bytes / unit) units. */
+int mpg_deflate_encode(mpg_stream_t stream, const void* src, size_t n_bytes, void* slots, uint32_t* sizes,
+                       uint32_t* crcs);
+/* compaction (uniio.py:91-123): out[sum(sizes[0..u)) ...] = the sizes[u] bytes of slot u, for u < n_units; nothing is
+ * written at or beyond out + out_bytes. */
+int mpg_deflate_compact(mpg_stream_t stream, const void* slots, const uint32_t* sizes, size_t n_units, void* out,
+                        size_t out_bytes);
+
+/* ------------------------------------------------------------------------
  * Training step: what tf.gradients produces for
  * the layers of GAN.py, and the optimiser update.  fp32 NHWC device tensors;
  * geometry is tf.nn.conv2d SAME of an [n,h,w,cin] input (GAN.py:686-691).

@@ -17,6 +17,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PREC_F16X1, PREC_F16F6, PREC_F16X3 = 1, 2, 3
 G8_F16 = 0
 MAX_SEG = 4
+DEFLATE_UNIT, DEFLATE_SLOT, DEFLATE_SLAB = 32768, 32768 + 16, 64 << 20    # MPG_DEFLATE_* of include/mpgan.h
 
 _ACT_IDS = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH}
 
@@ -134,6 +135,10 @@ PROTOTYPES = {
     "mpg_conv2d_transpose": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _I, _F, _P]),
     "mpg_depth_to_space": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "mpg_space_to_depth": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    # device codec of the .uni writer
+    "mpg_deflate_ws_bytes": (_Z, [_Z]),
+    "mpg_deflate_encode": (_I, [_P, _P, _Z, _P, _P, _P]),
+    "mpg_deflate_compact": (_I, [_P, _P, _P, _Z, _P, _Z]),
     # training step
     "mpg_conv2d_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "mpg_conv2d_wgrad_mfma_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),

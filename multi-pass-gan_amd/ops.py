@@ -698,3 +698,47 @@ def cutoff(v, thr=0.0005, out=None):
     out = torch.empty_like(v) if out is None else out
     _lib.check(lib.mpg_cutoff(_stream(), _ptr(v), v.numel(), thr, _ptr(out)), "mpg_cutoff")
     return out
+
+
+# ---------------------------------------------------------------- device codec of the .uni writer (tools_wscale/uniio.py:91-123)
+DEFLATE_UNIT, DEFLATE_SLOT, DEFLATE_SLAB = _lib.DEFLATE_UNIT, _lib.DEFLATE_SLOT, _lib.DEFLATE_SLAB
+
+
+def deflate_ws_bytes(n_bytes):
+    """bytes of slot workspace that deflate_encode needs for n_bytes of payload"""
+    return int(_lib.load().mpg_deflate_ws_bytes(int(n_bytes)))
+
+
+def deflate_encode(src, slots=None, sizes=None, crcs=None):
+    """Deflate the bytes of `src` (contiguous float32 GPU tensor, at most DEFLATE_SLAB bytes, 16-byte aligned) in units
+    of DEFLATE_UNIT bytes -> (slots uint8 [units * DEFLATE_SLOT], sizes int32 [units], crcs int32 [units]): unit u's
+    raw DEFLATE stream is slots[u * DEFLATE_SLOT:][:sizes[u]], crcs[u] (read as uint32) the CRC-32 of its input."""
+    lib = _lib.load()
+    src = _dev(src, "src")
+    n_bytes = src.numel() * 4
+    units = (n_bytes + DEFLATE_UNIT - 1) // DEFLATE_UNIT
+    if slots is None:
+        slots = torch.empty(units * DEFLATE_SLOT, dtype=torch.uint8, device=src.device)
+    if sizes is None:
+        sizes = torch.empty(units, dtype=torch.int32, device=src.device)
+    if crcs is None:
+        crcs = torch.empty(units, dtype=torch.int32, device=src.device)
+    _dev(slots, "slots", torch.uint8), _dev(sizes, "sizes", torch.int32), _dev(crcs, "crcs", torch.int32)
+    if slots.numel() < units * DEFLATE_SLOT or sizes.numel() < units or crcs.numel() < units:
+        raise _lib.MpgError("deflate_encode: workspace too small for %d units" % units)
+    _lib.check(lib.mpg_deflate_encode(_stream(), _ptr(src), n_bytes, _ptr(slots), _ptr(sizes), _ptr(crcs)), "mpg_deflate_encode")
+    return slots, sizes, crcs
+
+
+def deflate_compact(slots, sizes, units, out=None):
+    """the unit streams of deflate_encode, back to back: out[sum(sizes[:u]):][:sizes[u]] = slot u"""
+    lib = _lib.load()
+    _dev(slots, "slots", torch.uint8), _dev(sizes, "sizes", torch.int32)
+    units = int(units)
+    if slots.numel() < units * DEFLATE_SLOT or sizes.numel() < units:
+        raise _lib.MpgError("deflate_compact: %d units exceed the workspace" % units)
+    if out is None:
+        out = torch.empty(units * DEFLATE_SLOT, dtype=torch.uint8, device=slots.device)
+    _dev(out, "out", torch.uint8)
+    _lib.check(lib.mpg_deflate_compact(_stream(), _ptr(slots), _ptr(sizes), units, _ptr(out), out.numel()), "mpg_deflate_compact")
+    return out

@@ -5,7 +5,8 @@ File = gzip stream of: 4-byte magic (b"MNT2" or b"MNT3"), a 288-byte header,
 then the raw C-order payload [dimZ, dimY, dimX, channels] of float32 (scalar:
 elementType 1, 4 bytes/element; vec3: elementType 2, 12 bytes/element) or int32
 (elementType 0).  Files are always written as MNT3.  Large grids stream through a chunked, multi-threaded codec
-(below) whose output every gzip reader, the reference's included, decodes to the same bytes.
+(below) whose output every gzip reader, the reference's included, decodes to the same bytes.  writeUniFromDevice can
+instead deflate the payload on the GPU (codec "device", further below): same bytes after inflation, larger files.
 """
 import concurrent.futures
 import gzip
@@ -159,13 +160,20 @@ def writeUni(filename, header, content, level=None, threads=None, chunk_bytes=CH
                 out.write(member(i))
 
 
-def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk_bytes=CHUNK_BYTES):
+def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk_bytes=CHUNK_BYTES, codec=None):
     """writeUni for a float32 CUDA tensor: the volume is copied to pinned host memory chunk by chunk on a side stream
     while the previous chunks are being deflated, so neither the 537 MB device-to-host copy of a 512^3 volume nor its
-    compression waits for the other."""
+    compression waits for the other.  codec: "host" (zlib on the thread pool, the default) or "device" (deflated by
+    HIP kernels, only compressed bytes cross to the host; larger files, see _write_device); None = MPG_UNI_CODEC."""
     import torch
     if level is None:
         level = int(os.environ.get("MPG_UNI_LEVEL", "6"))
+    if codec is None:
+        codec = os.environ.get("MPG_UNI_CODEC", "") or "host"
+    if codec not in ("host", "device"):
+        raise UniError("unknown codec %r: expected \"host\" or \"device\"" % (codec,))
+    if codec == "device":
+        return _write_device(filename, header, volume, level)
     flat = volume.contiguous().reshape(-1)
     if flat.dtype != torch.float32:
         flat = flat.float()
@@ -200,6 +208,160 @@ def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk
     with open(filename, "wb") as out, concurrent.futures.ThreadPoolExecutor(nthreads) as pool:
         for blob in pool.map(member, range(len(cuts))):
             out.write(blob)
+
+
+# ----------------------------------------------------------------------------------------------
+# device codec.  ops.deflate_encode turns every UNIT bytes of the payload into a byte-aligned, non-final raw DEFLATE
+# stream (fixed Huffman code over word-granular runs, or a stored block) and the CRC-32 of those bytes; the streams of
+# consecutive units concatenate into a valid deflate body, which an empty final block closes.  The host only frames
+# members around bodies it never inflates: MEMBER_UNITS units each, the CRCs of their units combined.
+# ----------------------------------------------------------------------------------------------
+UNIT = 32768                      # payload bytes per device-encoded unit (MPG_DEFLATE_UNIT)
+SLOT = UNIT + 16                  # workspace bytes per unit (MPG_DEFLATE_SLOT)
+SLAB_BYTES = 64 << 20             # payload bytes per encode call (MPG_DEFLATE_SLAB): bounds the workspace
+MEMBER_UNITS = CHUNK_BYTES // UNIT    # units per gzip member: members as large as the host codec's, so readUni's
+#                                       thread pool gets the same work items either way
+_FINAL_BLOCK = b"\x03\x00"        # BFINAL 1, BTYPE 01, end-of-block: an empty last block
+_CRC_POLY = 0xEDB88320
+
+
+def _gf_mul(a, b):
+    """a * b mod the CRC-32 polynomial, bit-reflected (bit 31 is x^0), as zlib's multmodp"""
+    p = 0
+    for i in range(32):
+        if a & (0x80000000 >> i):
+            p ^= b
+        b = (b >> 1) ^ (_CRC_POLY if b & 1 else 0)
+    return p
+
+
+_SHIFT_TABLES = {}
+
+
+def _crc_shift_tables(nbytes):
+    """four 256-entry tables: the CRC register `c` moved past nbytes zero bytes is T0[c & 255] ^ T1[c >> 8 & 255] ^ ..."""
+    tabs = _SHIFT_TABLES.get(nbytes)
+    if tabs is None:
+        xp, sq, n = 0x80000000, 0x00800000, nbytes          # x^0; x^8
+        while n:
+            if n & 1:
+                xp = _gf_mul(xp, sq)
+            sq = _gf_mul(sq, sq)
+            n >>= 1
+        basis = [_gf_mul(1 << k, xp) for k in range(32)]
+        tabs = []
+        for byte in range(4):
+            t = [0] * 256
+            for v in range(1, 256):
+                low = v & -v
+                t[v] = t[v ^ low] ^ basis[8 * byte + low.bit_length() - 1]
+            tabs.append(t)
+        if len(_SHIFT_TABLES) < 64:
+            _SHIFT_TABLES[nbytes] = tabs
+    return tabs
+
+
+def crc32_combine(crcs, lengths):
+    """zlib.crc32 of the concatenation of pieces, from the pieces' own CRC-32s and byte lengths"""
+    crc = 0
+    for c, n in zip(crcs, lengths):
+        if n:
+            t0, t1, t2, t3 = _crc_shift_tables(int(n))
+            crc = t0[crc & 255] ^ t1[(crc >> 8) & 255] ^ t2[(crc >> 16) & 255] ^ t3[crc >> 24]
+        crc ^= int(c) & 0xffffffff
+    return crc
+
+
+def _frame_member(body_len, crc, isize):
+    """(head, tail) of a gzip member around a deflate body of body_len bytes that lacks its final block"""
+    total = _MEMBER_HEAD + body_len + len(_FINAL_BLOCK) + 8
+    head = struct.pack("<BBBBIBBH", 0x1f, 0x8b, 8, 4, 0, 0, 255, 8) + _SUBFIELD + struct.pack("<HI", 4, total)
+    return head, _FINAL_BLOCK + struct.pack("<II", crc & 0xffffffff, isize & 0xffffffff)
+
+
+def write_unit_members(out, bodies, sizes, crcs, lengths, member_units=MEMBER_UNITS):
+    """Write gzip members for device-encoded units to the file object `out`.  bodies: the unit streams back to back
+    (bytes-like), sizes[u] the stream length of unit u, crcs[u] / lengths[u] the CRC-32 and byte count of its input.
+    Every member holds up to member_units units and carries the MP size subfield and a CRC-32 / ISIZE trailer."""
+    bodies = memoryview(bodies).cast("B")
+    sizes = [int(x) for x in sizes]
+    lengths = [int(x) for x in lengths]
+    at = 0
+    for a in range(0, len(sizes), member_units):
+        b = min(a + member_units, len(sizes))
+        body_len = sum(sizes[a:b])
+        head, tail = _frame_member(body_len, crc32_combine(crcs[a:b], lengths[a:b]), sum(lengths[a:b]))
+        out.write(head)
+        out.write(bodies[at:at + body_len])
+        out.write(tail)
+        at += body_len
+    if at != len(bodies):
+        raise UniError("unit sizes describe %d bytes, %d were given" % (at, len(bodies)))
+
+
+def _write_device(filename, header, volume, level):
+    """The device codec of writeUniFromDevice.  The payload is encoded in slabs of SLAB_BYTES on the caller's current
+    stream (one slot workspace, reused in stream order); each slab's compacted streams go to pinned memory on a side
+    stream while the next slab is being encoded, so only compressed bytes cross to the host."""
+    import torch
+    if not (isinstance(volume, torch.Tensor) and volume.is_cuda):
+        raise UniError("codec \"device\" needs a GPU tensor")
+    from . import ops
+    flat = volume.contiguous().reshape(-1)
+    if flat.dtype != torch.float32:
+        flat = flat.float()
+    n = header["dimX"] * header["dimY"] * header["dimZ"] * (3 if header["elementType"] == 2 else 1)
+    if flat.numel() != n:
+        raise UniError("volume has %d elements, header describes %d" % (flat.numel(), n))
+    if flat.data_ptr() % 16:
+        flat = flat.clone()
+    dev = flat.device
+    per = SLAB_BYTES // 4
+    cuts = list(range(0, n, per))
+    first = b"MNT3" + struct.pack(_V4_FORMAT, *[header[k] for k in _V4_FIELDS])
+    with open(filename, "wb") as out, torch.cuda.device(dev):
+        out.write(_deflate_member(first, level))
+        if not cuts:
+            return
+        main = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(device=dev)
+        cap_units = (min(n, per) * 4 + UNIT - 1) // UNIT
+        slots = torch.empty(cap_units * SLOT, dtype=torch.uint8, device=dev)
+        bufs = []
+        for _ in range(min(2, len(cuts))):
+            bufs.append(dict(
+                packed=torch.empty(cap_units * SLOT, dtype=torch.uint8, device=dev),
+                meta=torch.empty(2, cap_units, dtype=torch.int32, device=dev),
+                host_meta=torch.empty(2, cap_units, dtype=torch.int32, pin_memory=True),
+                host=torch.empty(cap_units * SLOT, dtype=torch.uint8, pin_memory=True),
+                done=torch.cuda.Event()))
+
+        def launch(k):
+            buf = bufs[k % 2]
+            piece = flat[cuts[k]:cuts[k] + per]
+            units = (piece.numel() * 4 + UNIT - 1) // UNIT
+            ops.deflate_encode(piece, slots, buf["meta"][0], buf["meta"][1])
+            ops.deflate_compact(slots, buf["meta"][0], units, buf["packed"])
+            buf["done"].record(main)
+            return units
+
+        pending = launch(0)
+        for k in range(len(cuts)):
+            units, buf = pending, bufs[k % 2]
+            if k + 1 < len(cuts):
+                pending = launch(k + 1)         # the other buffer: its previous slab has been written out below
+            with torch.cuda.stream(side):
+                side.wait_event(buf["done"])
+                buf["host_meta"].copy_(buf["meta"], non_blocking=True)
+                side.synchronize()
+                meta = buf["host_meta"][:, :units].numpy().view(np.uint32)
+                total = int(meta[0].sum(dtype=np.int64))
+                buf["host"][:total].copy_(buf["packed"][:total], non_blocking=True)
+                side.synchronize()
+            nbytes = min(per, n - cuts[k]) * 4
+            lengths = [UNIT] * (units - 1) + [nbytes - UNIT * (units - 1)]
+            write_unit_members(out, buf["host"][:total].numpy(), meta[0], meta[1], lengths)
+        # `flat`, the workspace and the pinned buffers are released only now: every copy has completed
 
 
 def make_header(dim_x, dim_y, dim_z, vec3=False, info=b"", timestamp=0, grid_type=1):
