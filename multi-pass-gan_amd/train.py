@@ -254,11 +254,27 @@ class ConvFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dx = ConvDgradFn.apply(dy, w, ctx.cfg, (x.shape[1], x.shape[2])) if ctx.needs_input_grad[0] else None
         dw = ConvWgradFn.apply(x, dy, ctx.cfg, w.shape[0], w.shape[1]) if ctx.needs_input_grad[1] else None
-        db = train_ops.channel_sum(dy.detach()) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        db = ChannelSumFn.apply(dy) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         return dx, dw, db, None
 
 
+class ChannelSumFn(torch.autograd.Function):
+    """the bias gradient: sum of dy [..., C] over everything but the channels.  Linear: its gradient is the upstream vector
+    broadcast over the pixels, a view that autograd differentiates again by itself"""
+
+    @staticmethod
+    def forward(ctx, dy):
+        ctx.shape = tuple(dy.shape)
+        return train_ops.channel_sum(dy.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.expand(ctx.shape)
+
+
 class ConvDgradFn(torch.autograd.Function):
+    """dx = the data gradient of conv2d_SAME(x, w * wscale) for an upstream dy, on an input of spatial size hw"""
+
     @staticmethod
     def forward(ctx, dy, w, cfg, hw):
         ctx.save_for_backward(dy, w)
@@ -275,6 +291,12 @@ class ConvDgradFn(torch.autograd.Function):
 
 
 class ConvWgradFn(torch.autograd.Function):
+    """dw = the weight gradient of conv2d_SAME(x, w * wscale) for an upstream dy.
+    Known limit: backward hands its upstream gradient gw to ConvDgradFn / ConvFn as their weight, and weights are packed
+    (ops.pack_conv_weights) into fp16 hi/lo without an abs-max scale: a gw of gradient magnitude (1e-6 and below) would land
+    in fp16 subnormals and lose precision.  Fine for an O(1) gw, which is all the tests feed it; WGAN-GP never calls this
+    rule, which takes a third derivative (the penalty differentiates dD/dx, a ConvDgradFn output, once)."""
+
     @staticmethod
     def forward(ctx, x, dy, cfg, kh, kw):
         ctx.save_for_backward(x, dy)
