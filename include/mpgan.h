@@ -447,8 +447,10 @@ int mpg_adam_step_staged(mpg_stream_t stream, float* p, const float* grad, float
  *   mpg_maccormack (one channel): the MacCormack correction forward + strength/2 (source - backward) where
  *     flags < 0.2, clamped back to `forward` where it leaves the [min, max] of the fluid cells around the truncated
  *     look-up position (:206-343, index clipping as written there: for three of the four corners the batch index is
- *     clipped to w-1 too).  keep (may be NULL) receives 1 where the correction term survived: the only place where
- *     d out / d source differs from the semi-Lagrangian one (TensorFlow differentiates tf.where by its branches). */
+ *     clipped to w-1 too -- and so is the row index, which for h < w would leave the batch entry: h != w is
+ *     MPG_ERR_ARG, decided on the host before anything is launched).  keep (may be NULL) receives 1 where the
+ *     correction term survived: the only place where d out / d source differs from the semi-Lagrangian one
+ *     (TensorFlow differentiates tf.where by its branches). */
 int mpg_advect_velocity(mpg_stream_t stream, const float* vel, int n, int hv, int wv, int cv, int h, int w, float dt,
                         float* out);
 int mpg_semi_lagrange(mpg_stream_t stream, const float* source, const float* vel, int n, int h, int w, int c,

@@ -264,6 +264,9 @@ extern "C" int mpg_maccormack(mpg_stream_t stream, const float* source, const fl
                               float* keep) {
     MPG_REQUIRE(source && forward && backward && flags && vel && out, "mpg_maccormack: null pointer");
     MPG_REQUIRE(n >= 1 && h >= 1 && w >= 1, "mpg_maccormack: bad shape");
+    // three of the four clamp corners clip their row index to w-1: for h < w that is a row of the next batch entry
+    MPG_REQUIRE(h == w, "mpg_maccormack: h (%d) != w (%d): the reference's position grid and clamp indices are those of a "
+                        "square grid (GAN.py:270-272,362-374)", h, w);
     const size_t total = (size_t)n * h * w;
     hipLaunchKernelGGL(maccormack_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, source, forward, backward,
                        flags, vel, n, h, w, strength, out, keep);
