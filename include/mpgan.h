@@ -209,7 +209,9 @@ int mpg_conv2d_direct(mpg_stream_t stream, const float* x, int n, int h, int w, 
                       int act, float leak, float* y);
 
 /* ------------------------------------------------------------------------
- * Resampling (legacy TF1 coordinates: src = dst * in/out, no half-pixel centres)
+ * Resampling (legacy TF1 coordinates: src = dst * in/out, no half-pixel centres).
+ * src is the float32 product float32(dst) * (float32(in) / float32(out)), rounded to float32 before its floor and its
+ * fraction are taken (never the fraction of the unrounded product), as the TF1 kernels do.
  * ------------------------------------------------------------------------ */
 /* tf.image.resize_images(method=1) / kb.resize_images (GAN.py:517,541; multipassGAN-out.py:357) */
 int mpg_resize_nearest(mpg_stream_t stream, const float* x, int n, int h, int w, int c,

@@ -42,6 +42,14 @@ __global__ void conv_direct_kernel(const float* __restrict__ x, int n, int h, in
 }
 
 // ---------------------------------------------------------------- resize (legacy TF1 coordinates)
+// The source coordinate float32(o) * scale, rounded to float32 before its floor and fraction are taken, as TF1 does.  With
+// contraction allowed the compiler folds the product into the later `s - floor(s)` as an FMA, which takes the fraction of
+// the UNROUNDED product: a bilinear weight a float32 ulp off, and a bicubic table offset one off where frac * 1024 is a tie.
+__device__ __forceinline__ float resize_src_coord(int o, float scale) {
+#pragma clang fp contract(off)
+    return (float)o * scale;
+}
+
 __global__ void resize_nearest_kernel(const float* __restrict__ x, int n, int h, int w, int c,
                                       float* __restrict__ y, int oh, int ow, float sy, float sx) {
     const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
@@ -67,7 +75,7 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ x, int n, int h
     const int ox = p % ow; p /= ow;
     const int oy = p % oh;
     const int b = p / oh;
-    const float fy = oy * sy, fx = ox * sx;
+    const float fy = resize_src_coord(oy, sy), fx = resize_src_coord(ox, sx);
     const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
     const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
     const float ly = fy - y0, lx = fx - x0;
@@ -82,7 +90,7 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ x, int n, int h
 // TF 1.x ResizeBicubic: Keys A = -0.75, fraction quantised to 1/1024, taps clamped.
 __device__ __forceinline__ void bicubic_taps(int o, float scale, int in_size, int idx[4], float wt[4]) {
     const float A = -0.75f;
-    const float s = o * scale;
+    const float s = resize_src_coord(o, scale);
     const int i = (int)floorf(s);
     const float delta = s - (float)i;
     const int off = (int)lrintf(delta * 1024.f);
