@@ -155,8 +155,12 @@ if (upsampling_mode, upsampled_data) not in ((2, 0), (1, 1), (3, 1)) or int(P["d
 later_net = upsampling_mode != 2
 if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["premadeTiles"]):
     fail("vorticity / flag / k-eps inputs and premade tiles are not supported")
-if int(P["gDrop"]) or int(P["useVelInTDisc"]):
-    fail("gDrop / useVelInTDisc are 0 in the reference runs and not built")
+use_gdrop, useVelInTDisc = int(P["gDrop"]) > 0, int(P["useVelInTDisc"]) > 0
+if use_gdrop and not int(P["use_LSGAN"]):
+    fail("gDrop 1 needs use_LSGAN 1: the reference feeds the noise strengths only under use_LSGAN (:1993-2014)")
+if useVelInTDisc and not (int(P["adv_flag"]) and int(P["useVelocities"]) and not int(P["add_adj_idcs"])):
+    fail("useVelInTDisc 1 appends the velocity channels 1..3 of a 4-channel low-res tile to the advected frames "
+         "(:1185,1204-1208): adv_flag 1, useVelocities 1, add_adj_idcs 0")
 upRes = int(P["upRes"])
 if upRes != 8:
     fail("the growing networks are built for upRes 8")
@@ -256,14 +260,15 @@ ph.writeParams(test_path + "params.json")
 
 from mpgan_amd import heldout, ops  # noqa: E402
 from mpgan_amd.arch import Cfg8x  # noqa: E402
-from mpgan_amd.train import Trainer8x  # noqa: E402
+from mpgan_amd.train import Trainer8x, gdrop_schedule  # noqa: E402
 
 cfg = Cfg8x(tileSizeLow=tileSizeLow, upRes=upRes, n_inputChannels=n_inputChannels, upsampling_mode=upsampling_mode,
             upsampleMode=int(P["upsampleMode"]), filterSize=int(P["filterSize"]), start_fms=int(P["startFms"]),
             max_fms=int(P["maxFms"]), first_nn_arch=int(P["firstNNArch"]) > 0, use_res_net=int(P["use_res_net"]) > 0,
             pixel_norm=int(P["pixelNorm"]) > 0, addBicubicUpsample=int(P["addBicubicUpsample"]) > 0,
             use_mb_stddev=int(P["use_mb_stddev"]) > 0, bn_decay=float(P["bnDecay"]),
-            usePixelShuffle=int(P["usePixelShuffle"]) > 0)        # read by the first network only (growBlockGen)
+            usePixelShuffle=int(P["usePixelShuffle"]) > 0,        # read by the first network only (growBlockGen)
+            useVelInTDisc=useVelInTDisc and useTempoD, gDrop=use_gdrop)
 learning_rate = float(P["learningRate"])
 trainer = Trainer8x(cfg, device=device, learning_rate=learning_rate, beta1=float(P["adam_beta1"]),
                     beta2=float(P["adam_beta2"]), lambda_l1=float(P["lambda"]), lambda2=float(P["lambda2"]),
@@ -363,6 +368,9 @@ def test_split(tiles):
 
 have_test = test_split(tiCr)
 log, image_no = heldout.HeldOutLog(), 0
+# gDrop (:1878-1882): noise strengths of the two critics and the running scores they follow, all 0 at the start
+gdrop_strength_d = gdrop_strength_t = 0.0
+d_fakeScores_train = t_fakeScores_train = 0.0
 t0 = time.time()
 print('\n*****TRAINING STARTED***** (stop with ctrl-c)\n')
 for it in range(startingIter, trainingIterations):
@@ -390,22 +398,29 @@ for it in range(startingIter, trainingIterations):
     index = int(round(math.log(currentUpres, 2)) - 1)               # the growing stage's optimisers (:1978)
     for _ in range(discRuns):
         bx, by = getinput()
-        log.add_train("avgCost_disc", trainer.disc_step(bx, by, currBlendPer, stage=index)["disc_loss"].detach())
+        log.add_train("avgCost_disc", trainer.disc_step(bx, by, currBlendPer, stage=index,
+                                                         gdrop_str_d=gdrop_strength_d)["disc_loss"].detach())
     tempo = None
     if useTempoD:
         for _ in range(discRuns):
             tempo = getTempoinput()
-            Lt = trainer.tempo_disc_step(tempo[0], tempo[1], tempo[2], currBlendPer, stage=index)
+            Lt = trainer.tempo_disc_step(tempo[0], tempo[1], tempo[2], currBlendPer, stage=index, gdrop_str_t=gdrop_strength_t)
             log.add_train("avgTemCost_disc", Lt["t_disc_loss"].detach())
+    gdrop_strength_d = gdrop_strength_t = 0.0                        # :2013-2014: the generator step is fed 0
     for _ in range(genRuns):
         bx, by = getinput()
         if useTempoD:
             tempo = getTempoinput()
-        L = trainer.gen_step(bx, by, currBlendPer, tempo, stage=index)
+        L = trainer.gen_step(bx, by, currBlendPer, tempo, stage=index, gdrop_str_d=gdrop_strength_d,
+                             gdrop_str_t=gdrop_strength_t)
         log.add_train("avgCost_gen", L["g_loss_d"].detach())
         log.add_train("avgL1Cost_gen", L["l1_loss"].detach())
         if useTempoD:
             log.add_train("avgTemCost_gen", L["g_loss_t"].detach())
+    if use_gdrop:                                                    # :2086-2092 (check_gdrop_interval 1; LSGAN only)
+        d_fakeScores_train, gdrop_strength_d = gdrop_schedule(d_fakeScores_train, float(L["d_sig_g"]))
+        if useTempoD:
+            t_fakeScores_train, gdrop_strength_t = gdrop_schedule(t_fakeScores_train, float(L["t_sig_g"]))
     test_now, print_now, image_now = heldout.schedule(it, testInterval, outputInterval, genTestImg, have_test)
     if test_now:                                                     # draw order of :2099-2137
         train_b, test_b = getinput(numTests, True, False), getinput(numTests, False, False)
@@ -413,11 +428,14 @@ for it in range(startingIter, trainingIterations):
         if useTempoD:
             tempo_b, tempo_test_b = getTempoinput(numTests, True, False), getTempoinput(numTests, False, False)
         log.add_test(trainer.evaluate(train_b[0], train_b[1], test_b[0], test_b[1], tempo=tempo_b, tempo_test=tempo_test_b,
-                                      percentage=currBlendPer, stage=index))
+                                      percentage=currBlendPer, stage=index, gdrop_str_d=gdrop_strength_d,
+                                      gdrop_str_t=gdrop_strength_t))
     if print_now:
         print(log.report(it, trainingIterations, outputInterval, discRuns, genRuns, k=trainer.k, kt=kt, kt_l=kt_l,
                          blend=currBlendPer))
         print('\t{} iterations took {:.2f} seconds.'.format(outputInterval, time.time() - t0))
+        if use_gdrop:
+            print('\tgdrop_strength_d: {:.6f}, gdrop_strength_t: {:.6f}'.format(gdrop_strength_d, gdrop_strength_t))
         if image_now:
             trainer.sample_frame_image(tiCr, heldout.frame_index(fromSim, fromSim, frame_max), test_path + 'test_img/',
                                        image_no, simSizeLow * upRes, percentage=currBlendPer)

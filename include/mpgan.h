@@ -425,6 +425,15 @@ int mpg_tensor_resample(mpg_stream_t stream, const float* value, const float* po
                         int clamp, float* out);
 int mpg_tensor_resample_bwd(mpg_stream_t stream, const float* dy, const float* pos, int n, int h, int w, int c,
                             int clamp, float* dvalue);
+/* The temporal critic's input with useVelInTDisc (multipassGAN-8x.py:1204-1208, read as [-1,th,th,12] at :878): frames
+ * [3B,th,th,1] (advected, at tile size th) and x_t [3B,tl,tl,4] (velocity in channels 1..3) -> out [B, 12 th th], the
+ * reference's reshape [-1,3,P] / transpose (0,2,1) of concat(frames, scale * legacy-bilinear resize of the velocity to
+ * [th,th]) in one pass; the velocity values have the bits of scale * mpg_resize_bilinear.  th % tl == 0. */
+int mpg_tempo_vel_pack(mpg_stream_t stream, const float* frames, const float* x_t, int B, int tl, int th, float scale,
+                       float* out);
+/* gradient of mpg_tempo_vel_pack with respect to the frames (multipassGAN-8x.py:1204-1208 read backwards): dframes
+ * [3B,th,th,1] gathers its element of dout [B, 12 th th]; the velocity slots of dout reach nothing. */
+int mpg_tempo_vel_pack_bwd(mpg_stream_t stream, const float* dout, int B, int th, float* dframes);
 /* One optimiser call of the 8x training loop (multipassGAN-8x.py:1305-1362 with the dynamic loss scaling of :490-541):
  * Adam on the elements of the flat buffer whose `mask` entry is non-zero (the variables of the current growing
  * stage; NULL = all), on the gradient times coef = exp(-ls_var ln 2) / total_grads (use_loss_scaling; the gradient

@@ -158,6 +158,8 @@ PROTOTYPES = {
     "mpg_lerp": (_I, [_P, _P, _P, _Z, _F, _P]),
     "mpg_tensor_resample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mpg_tensor_resample_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "mpg_tempo_vel_pack": (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
+    "mpg_tempo_vel_pack_bwd": (_I, [_P, _P, _I, _I, _P]),
     "mpg_advect_velocity": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "mpg_semi_lagrange": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "mpg_semi_lagrange_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),

@@ -192,7 +192,8 @@ class Cfg8x(object):
 
     def __init__(self, tileSizeLow=16, upRes=8, n_inputChannels=4, upsampling_mode=2, upsampleMode=1, filterSize=3,
                  start_fms=256, max_fms=256, first_nn_arch=True, use_res_net=True, pixel_norm=True,
-                 addBicubicUpsample=True, use_mb_stddev=False, useVelInTDisc=False, bn_decay=0.999, usePixelShuffle=False):
+                 addBicubicUpsample=True, use_mb_stddev=False, useVelInTDisc=False, bn_decay=0.999, usePixelShuffle=False,
+                 gDrop=False):
         self.tileSizeLow, self.upRes = tileSizeLow, upRes
         self.tileSizeHigh = tileSizeLow * upRes
         self.n_inputChannels = n_inputChannels
@@ -202,6 +203,7 @@ class Cfg8x(object):
         self.addBicubicUpsample, self.use_mb_stddev, self.useVelInTDisc = addBicubicUpsample, use_mb_stddev, useVelInTDisc
         self.bn_decay = bn_decay
         self.usePixelShuffle = bool(usePixelShuffle)     # only the first network reads it (growBlockGen, -out.py:239-247)
+        self.gDrop = bool(gDrop)                         # use_gdrop: Gaussian noise on the critics' conv inputs (-8x.py:155,601-603)
         if upsampling_mode not in (1, 2, 3):
             raise NotImplementedError("upsampling_mode %d (only 1, 2, 3 are used by the example runs)" % upsampling_mode)
         self.n_input = tileSizeLow ** 2 * n_inputChannels            # -8x.py:402-416 (modes 1, 2, 3)
@@ -285,9 +287,14 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
         return tf.reshape(old, shape=[-1, size * size])
 
 
-def _critic(x_in, p, percentage, cfg, reuse, use_batch_norm, train, levels, mb_group):
-    """shared body of growing_disc / growing_disc_tempo (-8x.py:814-863, 887-923): returns (score, features)"""
+def _critic(x_in, p, percentage, cfg, reuse, use_batch_norm, train, levels, mb_group, gstr=None):
+    """shared body of growing_disc / growing_disc_tempo (-8x.py:814-863, 887-923): returns (score, features).
+    gstr: the ``Scalar`` strength of the gDrop noise; None stands for the reference's default 0.0 (no noise node)"""
     c = cfg
+
+    def gn(t):                                                                                 # :746-750
+        return tf.gaussian_noise(t, gstr) if c.gDrop and gstr is not None else t
+
     first_w, rows = growing_disc_table(c.start_fms, c.max_fms, c.upRes, levels, c.first_nn_arch, c.filterSize,
                                        tall_filter=(p == "t" and c.useVelInTDisc))
     gan = GAN(x_in, bn_decay=c.bn_decay)
@@ -301,9 +308,9 @@ def _critic(x_in, p, percentage, cfg, reuse, use_batch_norm, train, levels, mb_g
             raw = GAN(raw).avg_pool()
         with tf.variable_scope("%sBlock%d" % (p, up), reuse=reuse):                            # growBlockDisc, :752-780
             kw = {} if c.first_nn_arch else {"in_channels": f}
-            x1, _ = gan.convolutional_layer(a, list(k), lrelu, stride=[1], name="%s_cA%d" % (p, up), in_layer=x,
+            x1, _ = gan.convolutional_layer(a, list(k), lrelu, stride=[1], name="%s_cA%d" % (p, up), in_layer=gn(x),
                                             reuse=reuse, batch_norm=False, train=train, in_channels=f)
-            x2, _ = gan.convolutional_layer(b, list(k), lrelu, stride=[1], name="%s_cB%d" % (p, up), in_layer=x1,
+            x2, _ = gan.convolutional_layer(b, list(k), lrelu, stride=[1], name="%s_cB%d" % (p, up), in_layer=gn(x1),
                                             reuse=reuse, batch_norm=False, train=train, **kw)
             x = gan.avg_pool() if c.first_gen else x2
         skip, _ = skip_gan.convolutional_layer(b, [1, 1], None, stride=[1], name="%s_cfromDensity%d" % (p, up // 2),
@@ -316,9 +323,9 @@ def _critic(x_in, p, percentage, cfg, reuse, use_batch_norm, train, levels, mb_g
         x = gan.minibatch_stddev_layer(x, mb_group) if mb_group else gan.minibatch_stddev_layer(x)
     if not c.first_nn_arch:                                                                    # :852-854
         k = [c.filterSize, c.filterSize]
-        x1, _ = gan.convolutional_layer(32, k, lrelu, stride=[1], name="%s_cA1" % p, in_layer=x, reuse=reuse,
+        x1, _ = gan.convolutional_layer(32, k, lrelu, stride=[1], name="%s_cA1" % p, in_layer=gn(x), reuse=reuse,
                                         batch_norm=use_batch_norm, train=train)
-        gan.convolutional_layer(4, k, None, stride=[1], name="%s_cB1" % p, in_layer=x1, reuse=reuse,
+        gan.convolutional_layer(4, k, None, stride=[1], name="%s_cB1" % p, in_layer=gn(x1), reuse=reuse,
                                 batch_norm=use_batch_norm, train=train)
     else:
         x1 = x
@@ -330,8 +337,9 @@ def _critic(x_in, p, percentage, cfg, reuse, use_batch_norm, train, levels, mb_g
     return gan.y(), feats
 
 
-def growing_disc(in_high_, in_low_, percentage, cfg, reuse=False, use_batch_norm=False, train=None, currentUpres=3):
-    """-8x.py:783-863.  Returns (score [N,1], feature_layers)."""
+def growing_disc(in_high_, in_low_, percentage, cfg, reuse=False, use_batch_norm=False, train=None, currentUpres=3,
+                 gstr=None):
+    """-8x.py:783-863.  Returns (score [N,1], feature_layers).  gstr: gDrop noise strength (``Scalar``; None = 0.0)"""
     c = cfg
     with tf.variable_scope("spatial-disc", reuse=reuse):
         high = tf.reshape(in_high_, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, 1])
@@ -339,13 +347,16 @@ def growing_disc(in_high_, in_low_, percentage, cfg, reuse=False, use_batch_norm
         low = tf.slice_channels(tf.reshape(in_low_, shape=[-1, c.tileSizeLow, c.tileSizeLow, c.n_inputChannels]), 0, 1)
         low = GAN(tf.reshape(low, shape=[-1, c.tileSizeLow, c.tileSizeLow, 1])).avg_depool(scale=[c.upRes],
                                                                                            mode=c.upsampleMode)
-        return _critic(tf.concat([low, high], axis=3), "d", percentage, c, reuse, use_batch_norm, train, currentUpres, 0)
+        return _critic(tf.concat([low, high], axis=3), "d", percentage, c, reuse, use_batch_norm, train, currentUpres, 0,
+                       gstr)
 
 
 def growing_disc_tempo(in_high_, percentage, cfg, n_t_channels=3, reuse=True, use_batch_norm=False, train=None,
-                       currentUpres=3):
-    """-8x.py:866-923 (useVelInTDisc 0): [N, H, W, 3] frame triples -> score"""
+                       currentUpres=3, gstr=None):
+    """-8x.py:866-923: [N, H, W, 3] frame triples -> score.  With cfg.useVelInTDisc the rows are the 12 H W values
+    mpg_tempo_vel_pack writes (frames and scaled velocity in the reference's order, :1204-1208), read as [N, H, W, 12]
+    (:878), and the growing blocks use [filterSize + 2, filterSize] filters (:754-755).  gstr: gDrop noise strength"""
     c = cfg
     with tf.variable_scope("tempo-disc", reuse=reuse):
         x = tf.reshape(in_high_, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, 12 if c.useVelInTDisc else 3])
-        return _critic(x, "t", percentage, c, reuse, use_batch_norm, train, currentUpres, 1)[0]
+        return _critic(x, "t", percentage, c, reuse, use_batch_norm, train, currentUpres, 1, gstr)[0]

@@ -3,6 +3,7 @@
 // plain fp32 direct convolution on the vector ALUs (strided / odd shapes and an
 // independent check of the MFMA kernel).  One thread per output element with
 // the channel (or x) index fastest, so wave accesses are contiguous.
+#include "mpgan_resize.h"
 #include "mpgan_valu.h"
 
 using namespace mpg::valu;
@@ -42,14 +43,7 @@ __global__ void conv_direct_kernel(const float* __restrict__ x, int n, int h, in
 }
 
 // ---------------------------------------------------------------- resize (legacy TF1 coordinates)
-// The source coordinate float32(o) * scale, rounded to float32 before its floor and fraction are taken, as TF1 does.  With
-// contraction allowed the compiler folds the product into the later `s - floor(s)` as an FMA, which takes the fraction of
-// the UNROUNDED product: a bilinear weight a float32 ulp off, and a bicubic table offset one off where frac * 1024 is a tie.
-__device__ __forceinline__ float resize_src_coord(int o, float scale) {
-#pragma clang fp contract(off)
-    return (float)o * scale;
-}
-
+// (source coordinate and the bilinear look-up: mpgan_resize.h, shared with mpg_tempo_vel_pack)
 __global__ void resize_nearest_kernel(const float* __restrict__ x, int n, int h, int w, int c,
                                       float* __restrict__ y, int oh, int ow, float sy, float sx) {
     const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
@@ -75,16 +69,7 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ x, int n, int h
     const int ox = p % ow; p /= ow;
     const int oy = p % oh;
     const int b = p / oh;
-    const float fy = resize_src_coord(oy, sy), fx = resize_src_coord(ox, sx);
-    const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-    const float ly = fy - y0, lx = fx - x0;
-    const float* base = x + (size_t)b * h * w * c + ch;
-    const float tl = base[((size_t)y0 * w + x0) * c], tr = base[((size_t)y0 * w + x1) * c];
-    const float bl = base[((size_t)y1 * w + x0) * c], br = base[((size_t)y1 * w + x1) * c];
-    const float top = tl + (tr - tl) * lx;
-    const float bot = bl + (br - bl) * lx;
-    y[idx] = top + (bot - top) * ly;
+    y[idx] = resize_bilinear_at(x + (size_t)b * h * w * c + ch, h, w, c, oy, ox, sy, sx);
 }
 
 // TF 1.x ResizeBicubic: Keys A = -0.75, fraction quantised to 1/1024, taps clamped.

@@ -163,6 +163,14 @@ def random_normal_like(x, channels, stddev, seed=0):
     return Node("random_normal", [x], shape=shape, stddev=float(stddev), seed=None if seed is None else int(seed))
 
 
+def gaussian_noise(x, strength):
+    """gaussian_noise_layer of multipassGAN-8x.py:601-603 (`gDrop`): x + N(0, 1) * (strength * sqrt(C)), C the channel
+    count of x; `strength` is a ``Scalar`` read from the feed at run time (0 leaves x as it is), the draw is fresh every run"""
+    if not isinstance(strength, Scalar):
+        raise GraphError("gaussian_noise: the strength must be a Scalar")
+    return Node("gaussian_noise", [x], shape=x.shape, strength=strength, stddev=1.0, seed=None)
+
+
 def slice_channels(x, begin, size):
     """tf.slice(x, [0,0,0,begin], [-1,h,w,size]) (multipassGAN-out.py:330)."""
     shape = list(x.shape)

@@ -589,6 +589,22 @@ class ResampleFn(torch.autograd.Function):
         return train_ops.tensor_resample_bwd(dy, pos, ctx.clamp), None, None
 
 
+class TempoVelPackFn(torch.autograd.Function):
+    """the useVelInTDisc input of the temporal critic (multipassGAN-8x.py:1204-1208): frames [3B,th,th,1] next to the
+    scaled, bilinearly upsampled velocity of x_t, in the reference's [B, 12 th th] order; x_t is data, the gradient goes
+    to the frames (the gradient penalty differentiates with respect to the packed tensor, never through the pack)"""
+
+    @staticmethod
+    def forward(ctx, frames, x_t, scale):
+        ctx.th = frames.shape[1]
+        return train_ops.tempo_vel_pack(frames, x_t, scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        return train_ops.tempo_vel_pack_bwd(dout, ctx.th), None, None
+
+
 class TrainSession(object):
     """Eager, differentiable evaluation of ``graph`` nodes; parameters are leaf tensors keyed by
     the TF variable path.  ``run(fetches, feeds)`` returns torch tensors that carry the tape."""
@@ -671,6 +687,11 @@ class TrainSession(object):
         kh, kw, _, cout = self.graph.variables[r.inputs[1].attrs["var"]].shape
         return _mfma_ok(kh, kw, cout, tuple(r.attrs["stride"]))
 
+    @staticmethod
+    def _noise_seed(n):
+        """one stream per noise node (the reference draws from TensorFlow's global generator), as session.Session does"""
+        return n.attrs["seed"] if n.attrs["seed"] is not None else n.id
+
     def _higher(self, n):
         """does this node sit in a variable scope that needs differentiable backward passes?"""
         return any(n.scope.startswith(p) for p in self.higher_order_scopes)
@@ -723,7 +744,15 @@ class TrainSession(object):
             y = ev(n.inputs[-1])
             return LerpFn.apply(x, y, t)
         if op == "random_normal":
-            return seeded_normal(self._noise_gen, n, ev(n.inputs[0]), n.attrs["seed"])
+            return seeded_normal(self._noise_gen, n, ev(n.inputs[0]), self._noise_seed(n))
+        if op == "gaussian_noise":
+            # x + N(0, 1) * (s * sqrt(C)) (multipassGAN-8x.py:601-603): linear in x, so it differentiates to any order
+            x = ev(n.inputs[0])
+            s = n.attrs["strength"].value(self._scalar_feeds)
+            if s == 0.0:
+                return x
+            noise = seeded_normal(self._noise_gen, n, x, self._noise_seed(n)) * (s * math.sqrt(x.shape[-1]))
+            return ActFn.apply(x, noise, None, 0.2)
         if op == "max_pool":
             if self._higher(n):
                 raise NotImplementedError("second-order gradient through max_pool (no reference network uses it)")
@@ -1341,6 +1370,17 @@ class Trainer4x(_SlotStateMixin, _HeldOutMixin):
         return Ld["disc_loss"].detach(), Lg["gen_loss_complete"].detach()
 
 
+GDROP_BETA, GDROP_LIM, GDROP_COEF, GDROP_EXP = 0.9, 0.5, 0.2, 2.0        # multipassGAN-8x.py:168-171 (gdrop_* constants)
+
+
+def gdrop_schedule(score, curr_fake):
+    """the end-of-iteration gDrop update (multipassGAN-8x.py:2086-2092, check_gdrop_interval 1, LSGAN only): `score` is the
+    running value, `curr_fake` the mean critic output on generated data of the generator step
+    -> (new score, new noise strength)"""
+    score = score * GDROP_BETA + (1.0 - curr_fake) * (1.0 - GDROP_BETA)
+    return score, GDROP_COEF * max(score - GDROP_LIM, 0.0) ** GDROP_EXP
+
+
 class Trainer8x(_SlotStateMixin, _HeldOutMixin):
     """One stage of the progressive-growing training of multipassGAN-8x.py (graph :1023-1144, optimisers
     :1305-1362): WGAN-GP (lambda 10, target 1, epsilon penalty 1e-3) or LSGAN or sigmoid-CE losses, L1 and
@@ -1364,9 +1404,21 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         if use_wgan_gp:
             self.wgan_lambda, self.wgan_target, self.wgan_epsilon = (150.0, 30.0, 1e-3) if use_LSGAN else (10.0, 1.0, 1e-3)
         self.currentUpres = int(round(math.log(cfg.upRes, 2)))
+        # `gDrop 1` (use_gdrop, multipassGAN-8x.py:155): the strengths are fed only under use_LSGAN (:1993-2014); without it
+        # the reference's discriminator step leaves the placeholder unfed and TensorFlow raises
+        self.gdrop = bool(getattr(cfg, "gDrop", False))
+        if self.gdrop and not use_LSGAN:
+            raise _lib.MpgError("gDrop 1 needs use_LSGAN 1: the reference feeds the noise strengths only under use_LSGAN "
+                                "(multipassGAN-8x.py:1993-2014)")
+        if cfg.useVelInTDisc and not (use_tempo and adv_flag and cfg.n_inputChannels == 4):
+            raise _lib.MpgError("useVelInTDisc 1 needs the temporal critic, adv_flag 1 and a 4-channel low-res tile whose "
+                                "channels 1..3 are the velocity (multipassGAN-8x.py:1185,1204-1208); got use_tempo %r, "
+                                "adv_flag %r, %d channels" % (use_tempo, adv_flag, cfg.n_inputChannels))
         g = G.reset_default_graph()
         self.graph = g
         self.percentage = G.scalar_placeholder("percentage")
+        self.gdrop_str_d = G.scalar_placeholder("gdrop_str_d") if self.gdrop else None
+        self.gdrop_str_t = G.scalar_placeholder("gdrop_str_t") if self.gdrop else None
         self.x = G.placeholder([None, cfg.n_input], name="x")
         self.x_disc = G.placeholder([None, cfg.n_input], name="x_disc")
         self.y_gp = G.placeholder([None, cfg.n_output], name="y_gp")
@@ -1380,8 +1432,10 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         self.gen_y = arch.growing_gen(x_in, cfg, self.percentage, use_batch_norm=self.batch_norm, train=True,
                                       currentUpres=self.currentUpres)
         dk = dict(cfg=cfg, use_batch_norm=self.batch_norm, train=True, currentUpres=self.currentUpres)
-        self.disc, self.f_y = arch.growing_disc(self.y_in, self.x_disc, self.percentage, reuse=False, **dk)
-        self.gen, self.f_g = arch.growing_disc(self.gen_y, self.x_disc, self.percentage, reuse=True, **dk)
+        gd = dict(gstr=self.gdrop_str_d)
+        self.disc, self.f_y = arch.growing_disc(self.y_in, self.x_disc, self.percentage, reuse=False, **dk, **gd)
+        self.gen, self.f_g = arch.growing_disc(self.gen_y, self.x_disc, self.percentage, reuse=True, **dk, **gd)
+        # the penalty critics pass no gstr: strength 0 (:1249,1283)
         self.d_out, _ = arch.growing_disc(self.y_gp, self.x_disc, self.percentage, reuse=True, **dk)
         self.k2_ls = list(k2_ls) if k2_ls is not None else [1.0] * len(self.f_y)
         # temporal discriminator (multipassGAN-8x.py:1158-1300; final growing stage, tensorResample advection)
@@ -1402,11 +1456,13 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
             self.gen_ts = arch.growing_gen(x_t_in, cfg, self.percentage, reuse=True, use_batch_norm=self.batch_norm, train=True,
                                              currentUpres=self.currentUpres)
             tk = dict(cfg=cfg, n_t_channels=self.n_t, use_batch_norm=self.batch_norm, train=True, currentUpres=self.currentUpres)
-            self.t_fake = G.placeholder([None, cfg.n_output * self.n_t], name="t_fake")
-            self.t_real = G.placeholder([None, cfg.n_output * self.n_t], name="t_real")
-            self.t_gp = G.placeholder([None, cfg.n_output * self.n_t], name="t_gp")
-            self.gen_s = arch.growing_disc_tempo(self.t_fake, self.percentage, reuse=False, **tk)
-            self.disc_s = arch.growing_disc_tempo(self.t_real, self.percentage, reuse=True, **tk)
+            # useVelInTDisc: every frame carries its three scaled velocity channels (:1204-1208), 12 values per pixel
+            tw = cfg.n_output * (12 if cfg.useVelInTDisc else self.n_t)
+            self.t_fake = G.placeholder([None, tw], name="t_fake")
+            self.t_real = G.placeholder([None, tw], name="t_real")
+            self.t_gp = G.placeholder([None, tw], name="t_gp")
+            self.gen_s = arch.growing_disc_tempo(self.t_fake, self.percentage, reuse=False, gstr=self.gdrop_str_t, **tk)
+            self.disc_s = arch.growing_disc_tempo(self.t_real, self.percentage, reuse=True, gstr=self.gdrop_str_t, **tk)
             self.t_out = arch.growing_disc_tempo(self.t_gp, self.percentage, reuse=True, **tk)
         self.sess = TrainSession(variables or VariableStore(device, seed=seed), graph=g, prec=prec, device=device)
         if use_wgan_gp:
@@ -1434,7 +1490,16 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
             return (-logits).mean() if real else logits.mean()
         return sigmoid_ce(logits, torch.ones_like(logits) if real else torch.zeros_like(logits))
 
-    def losses(self, batch_xs, batch_ys, percentage=3.0, lerp_factor=None, need_gp=True):
+    def _gdrop_feeds(self, feeds, gdrop_str_d=None, gdrop_str_t=None):
+        """adds the gDrop noise strengths a run of the spatial (gdrop_str_d) / temporal (gdrop_str_t) critic reads"""
+        if self.gdrop:
+            if gdrop_str_d is not None:
+                feeds[self.gdrop_str_d] = float(gdrop_str_d)
+            if gdrop_str_t is not None:
+                feeds[self.gdrop_str_t] = float(gdrop_str_t)
+        return feeds
+
+    def losses(self, batch_xs, batch_ys, percentage=3.0, lerp_factor=None, need_gp=True, gdrop_str_d=0.0):
         """-> dict of loss tensors (multipassGAN-8x.py:1082-1142); batch_ys at full tileSizeHigh resolution"""
         dev = self.sess.device
         xs = torch.as_tensor(batch_xs, dtype=torch.float32, device=dev)
@@ -1445,6 +1510,7 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         else:
             feeds = {self.x: xs, self.x_disc: xs, self.y2: ys, self.percentage: percentage}
             ys = ys.reshape(-1, self.cfg.n_output, 2)[:, :, 0].contiguous()        # the target channel
+        self._gdrop_feeds(feeds, gdrop_str_d=gdrop_str_d)
         out = self.sess.run([self.gen_y, self.disc, self.gen] + list(self.f_y) + list(self.f_g), feeds)
         nf = len(self.f_y)
         gen_y, disc, gen = out[0], out[1], out[2]
@@ -1459,6 +1525,8 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         L["gen_l2_loss"] = 0.5 * PairLossFn.apply(ys, gen_y, 1)
         L["l1_loss"] = PairLossFn.apply(ys, gen_y, 0) / float(gen_y.numel())
         L["g_loss_d"] = self._adv(gen, True)
+        if self.gdrop:
+            L["d_sig_g"] = gen.detach().mean()                                   # what the gDrop schedule reads (:2088)
         if self.use_wgan_gp and need_gp:
             if lerp_factor is None:
                 lerp_factor = torch.rand((xs.shape[0], 1), generator=self.rng)
@@ -1487,9 +1555,10 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         return ops.resize_nearest(ys.reshape(-1, cur, cur, 1).contiguous(), th, th).reshape(-1, th * th)
 
     # ------------------------------------------------------------------ temporal branch
-    def _frames_as_channels(self, frames, y_pos, xts=None, cur_size=None):
+    def _frames_as_channels(self, frames, y_pos, xts=None, cur_size=None, percentage=None):
         """advection look-up at the CURRENT stage's resolution (the positions come at tileSizeLow * 2^stage):
-        generated frames are nearest-downsampled to it, resampled, and resized back (:1178-1200)"""
+        generated frames are nearest-downsampled to it, resampled, and resized back (:1178-1200).  With useVelInTDisc
+        the frames leave next to upresFac * the bilinearly upsampled velocity of x_t (:1204-1208, TempoVelPackFn)"""
         th = self.cfg.tileSizeHigh
         frames = frames.reshape(frames.shape[0], -1)
         cur = int(round(math.sqrt(frames.shape[1])))
@@ -1515,9 +1584,13 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
                 v = ResizeNearestFn.apply(v, th, th)
         else:
             v = self._to_full_res(frames).reshape(-1, th, th, 1)
+        if self.cfg.useVelInTDisc:
+            tl = self.cfg.tileSizeLow
+            scale = float(2 ** int(math.ceil(percentage)))                      # upresFac (:1178)
+            return TempoVelPackFn.apply(v.contiguous(), xts.detach().reshape(-1, tl, tl, 4), scale)
         return v.reshape(-1, self.n_t, self.cfg.n_output).permute(0, 2, 1).reshape(-1, self.cfg.n_output * self.n_t)
 
-    def _tempo_forward(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0):
+    def _tempo_forward(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, gdrop_str_t=0.0):
         """the forward passes tempo_losses and evaluate share, for [3B, .] coherent frame rows
         -> (fake, real frames as channels, T(fake) logits, T(real) logits)"""
         dev = self.sess.device
@@ -1532,26 +1605,31 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
             yts = yts.reshape(-1, self.cfg.n_output, 2)[:, :, 0].contiguous()
         # resolution of the current growing stage = that of the fed targets (tileSizeLow * 2^ceil(percentage), :1180-1181)
         cur_size = int(round(math.sqrt(yts.shape[1]))) if self.cfg.upsampling_mode == 2 else self.cfg.tileSizeHigh
-        fake = self._frames_as_channels(gen_ts, batch_y_pos, xts, cur_size)
-        real = self._frames_as_channels(yts, batch_y_pos, xts, cur_size)
-        gen_s, disc_s = self.sess.run([self.gen_s, self.disc_s], {self.t_fake: fake, self.t_real: real,
-                                                                   self.percentage: percentage})
+        fake = self._frames_as_channels(gen_ts, batch_y_pos, xts, cur_size, percentage)
+        real = self._frames_as_channels(yts, batch_y_pos, xts, cur_size, percentage)
+        feeds = self._gdrop_feeds({self.t_fake: fake, self.t_real: real, self.percentage: percentage}, gdrop_str_t=gdrop_str_t)
+        gen_s, disc_s = self.sess.run([self.gen_s, self.disc_s], feeds)
         return fake, real, gen_s, disc_s
 
-    def tempo_losses(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, lerp_factor=None, need_gp=True):
+    def tempo_losses(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, lerp_factor=None, need_gp=True,
+                     gdrop_str_t=0.0):
         """t_disc_loss / g_loss_t of multipassGAN-8x.py:1216-1300 for [3B, .] coherent frame rows (final stage)"""
         dev = self.sess.device
-        fake, real, gen_s, disc_s = self._tempo_forward(batch_xts, batch_yts, batch_y_pos, percentage)
+        fake, real, gen_s, disc_s = self._tempo_forward(batch_xts, batch_yts, batch_y_pos, percentage, gdrop_str_t)
         L = {"t_loss_y": self._adv(disc_s, True), "t_loss_g": self._adv(gen_s, False)}
         t_disc_loss = L["t_loss_y"] * self.weight_dld + L["t_loss_g"]
         if self.use_wgan_gp and need_gp:
+            # useVelInTDisc: t_lerp_factor is [4B, 1, 1] on the [4B, P, 3] tensor (:1281-1283), one factor per third of a row
+            rows = fake.shape[0] * (4 if self.cfg.useVelInTDisc else 1)
             if lerp_factor is None:
-                lerp_factor = torch.rand((fake.shape[0], 1), generator=self.rng)
-            lf = torch.as_tensor(lerp_factor, dtype=torch.float32, device=dev).reshape(-1, 1)
-            y_gp = (lf * real + (1.0 - lf) * fake.detach()).requires_grad_(True)
+                lerp_factor = torch.rand((rows, 1), generator=self.rng)
+            lf = torch.as_tensor(lerp_factor, dtype=torch.float32, device=dev).reshape(rows, 1)
+            y_gp = (lf * real.reshape(rows, -1) + (1.0 - lf) * fake.detach().reshape(rows, -1)).reshape(fake.shape)
+            y_gp = y_gp.requires_grad_(True)
             t_out = self.sess.run([self.t_out], {self.t_gp: y_gp, self.percentage: percentage})[0]
             (grads_t,) = torch.autograd.grad(t_out.mean(), y_gp, create_graph=True)
-            # [B, n_output, n_t]: the norm runs over the pixels of each frame (reduce_sum(axis=1), :1287)
+            # [B, n_output, n_t] ([4B, n_output, n_t] with useVelInTDisc): the norm runs over the pixels of each frame
+            # (reduce_sum(axis=1), :1287)
             gt = grads_t.reshape(-1, self.cfg.n_output, self.n_t)
             norm = torch.sqrt(((gt + 1e-4) ** 2).sum(dim=1))
             L["grad_penalty_t"] = (self.wgan_lambda * (norm - self.wgan_target) ** 2).mean()
@@ -1559,6 +1637,8 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
             t_disc_loss = t_disc_loss + L["epsilon_penalty_t"] * self.wgan_epsilon + L["grad_penalty_t"]
         L["t_disc_loss"] = t_disc_loss
         L["g_loss_t"] = self._adv(gen_s, True)
+        if self.gdrop:
+            L["t_sig_g"] = gen_s.detach().mean()                                 # (:2091)
         return L
 
     @property
@@ -1570,6 +1650,18 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
     @property
     def tileSizeHigh(self):
         return self.cfg.tileSizeHigh
+
+    _eval_gdrop = (0.0, 0.0)
+
+    def evaluate(self, x, y, x_test, y_test, tempo=None, tempo_test=None, percentage=None, stage=None, gdrop_str_d=0.0,
+                 gdrop_str_t=0.0):
+        """_HeldOutMixin.evaluate; gdrop_str_d / gdrop_str_t: the gDrop noise strengths the test section feeds where it
+        feeds them (multipassGAN-8x.py:2086-2092), the end-of-iteration values"""
+        self._eval_gdrop = (gdrop_str_d, gdrop_str_t)
+        try:
+            return _HeldOutMixin.evaluate(self, x, y, x_test, y_test, tempo, tempo_test, percentage, stage)
+        finally:
+            self._eval_gdrop = (0.0, 0.0)
 
     def _adv_stat(self, st, real):
         """_adv out of the mpg_logit_stats vector: LSGAN 0.5 (l - target)^2, WGAN -l / +l, else sigmoid cross entropy"""
@@ -1588,13 +1680,14 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
             feeds = {self.x: xs, self.x_disc: xs, self.y_in: self._to_full_res(ys), self.percentage: percentage}
         else:
             feeds = {self.x: xs, self.x_disc: xs, self.y2: ys, self.percentage: percentage}
-        disc, gen = self.sess.run([self.disc, self.gen], feeds)
+        disc, gen = self.sess.run([self.disc, self.gen], self._gdrop_feeds(feeds, gdrop_str_d=self._eval_gdrop[0]))
         return train_ops.logit_stats(disc), train_ops.logit_stats(gen)
 
     def _eval_tempo(self, tempo, percentage=None):
         """-> (stats of T(real), stats of T(fake), None) for [3B, .] coherent rows"""
         percentage = float(self.currentUpres) if percentage is None else percentage
-        _, _, gen_s, disc_s = self._tempo_forward(tempo[0], tempo[1], tempo[2] if len(tempo) > 2 else None, percentage)
+        _, _, gen_s, disc_s = self._tempo_forward(tempo[0], tempo[1], tempo[2] if len(tempo) > 2 else None, percentage,
+                                                  self._eval_gdrop[1])
         return train_ops.logit_stats(disc_s), train_ops.logit_stats(gen_s), None
 
     def _sample(self, low, high, percentage=None):
@@ -1612,32 +1705,36 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         grads = torch.autograd.grad(loss if scale is None else loss * scale, opt.params, allow_unused=True)
         opt.step(grads, stage=stage)
 
-    def tempo_disc_step(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, lerp_factor=None, stage=None):
-        L = self.tempo_losses(batch_xts, batch_yts, batch_y_pos, percentage, lerp_factor)
+    def tempo_disc_step(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, lerp_factor=None, stage=None,
+                        gdrop_str_t=0.0):
+        L = self.tempo_losses(batch_xts, batch_yts, batch_y_pos, percentage, lerp_factor, gdrop_str_t=gdrop_str_t)
         self._update(self.opt_t, L["t_disc_loss"], stage)
         return L
 
-    def disc_step(self, batch_xs, batch_ys, percentage=3.0, lerp_factor=None, stage=None):
-        L = self.losses(batch_xs, batch_ys, percentage, lerp_factor)
+    def disc_step(self, batch_xs, batch_ys, percentage=3.0, lerp_factor=None, stage=None, gdrop_str_d=0.0):
+        L = self.losses(batch_xs, batch_ys, percentage, lerp_factor, gdrop_str_d=gdrop_str_d)
         self._update(self.opt_d, L["disc_loss"], stage)
         return L
 
-    def gen_step(self, batch_xs, batch_ys, percentage=3.0, tempo=None, stage=None):
-        L = self.losses(batch_xs, batch_ys, percentage, need_gp=False)
+    def gen_step(self, batch_xs, batch_ys, percentage=3.0, tempo=None, stage=None, gdrop_str_d=0.0, gdrop_str_t=0.0):
+        """the reference feeds the generator step the strengths it has just set to 0 (:2013-2014,2022-2023)"""
+        L = self.losses(batch_xs, batch_ys, percentage, need_gp=False, gdrop_str_d=gdrop_str_d)
         if tempo is not None:
-            Lt = self.tempo_losses(tempo[0], tempo[1], tempo[2], percentage, need_gp=False)
+            Lt = self.tempo_losses(tempo[0], tempo[1], tempo[2], percentage, need_gp=False, gdrop_str_t=gdrop_str_t)
             L.update(Lt)
             L["gen_loss_complete"] = L["gen_loss_complete"] + self.kt * Lt["g_loss_t"]        # :1302
         self._update(self.opt_g, L["gen_loss_complete"], stage)     # the moving averages move inside the optimiser call
         return L
 
-    def train_step(self, batch_xs, batch_ys, percentage=3.0, discRuns=1, genRuns=1, tempo=None, stage=None):
-        """stage: index of the growing stage's optimisers, log2(currentUpres) - 1 (:1978); None = the last one"""
+    def train_step(self, batch_xs, batch_ys, percentage=3.0, discRuns=1, genRuns=1, tempo=None, stage=None,
+                   gdrop_str_d=0.0, gdrop_str_t=0.0):
+        """stage: index of the growing stage's optimisers, log2(currentUpres) - 1 (:1978); None = the last one.
+        gdrop_str_d / gdrop_str_t: the gDrop noise strengths of the critic steps; the generator step runs at 0 (:2013-2014)"""
         for _ in range(discRuns):
-            Ld = self.disc_step(batch_xs, batch_ys, percentage, stage=stage)
+            Ld = self.disc_step(batch_xs, batch_ys, percentage, stage=stage, gdrop_str_d=gdrop_str_d)
         if tempo is not None:
             for _ in range(discRuns):
-                self.tempo_disc_step(tempo[0], tempo[1], tempo[2], percentage, stage=stage)
+                self.tempo_disc_step(tempo[0], tempo[1], tempo[2], percentage, stage=stage, gdrop_str_t=gdrop_str_t)
         for _ in range(genRuns):
             Lg = self.gen_step(batch_xs, batch_ys, percentage, tempo, stage=stage)
         return Ld["disc_loss"].detach(), Lg["gen_loss_complete"].detach()

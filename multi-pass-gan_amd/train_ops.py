@@ -252,6 +252,43 @@ def tensor_resample_bwd(dy, pos, clamp=True):
     return dv
 
 
+def tempo_vel_pack(frames, x_t, scale, out=None):
+    """the temporal critic's input with useVelInTDisc (multipassGAN-8x.py:1204-1208, :878): frames [3B,th,th,1] and x_t
+    [3B,tl,tl,4] (velocity in channels 1..3) -> [B, 12 th th]; `out` (optional) is overwritten"""
+    lib = _lib.load()
+    frames, x_t = _cont(frames, "frames"), _cont(x_t, "x_t")
+    if frames.dim() != 4 or frames.shape[1] != frames.shape[2] or frames.shape[3] != 1:
+        raise _lib.MpgError("tempo_vel_pack: frames %s are not [3B, th, th, 1]" % (tuple(frames.shape),))
+    n, th = frames.shape[0], frames.shape[1]
+    if n < 3 or n % 3:
+        raise _lib.MpgError("tempo_vel_pack: %d frame rows are no multiple of 3" % n)
+    if x_t.dim() != 4 or x_t.shape[0] != n or x_t.shape[1] != x_t.shape[2] or x_t.shape[3] != 4:
+        raise _lib.MpgError("tempo_vel_pack: x_t %s is not [%d, tl, tl, 4]" % (tuple(x_t.shape), n))
+    tl = x_t.shape[1]
+    if out is None:
+        out = torch.empty((n // 3, 12 * th * th), dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != (n // 3, 12 * th * th) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise _lib.MpgError("tempo_vel_pack: out %s is not a contiguous fp32 [%d, %d]" % (tuple(out.shape), n // 3, 12 * th * th))
+    _lib.check(lib.mpg_tempo_vel_pack(_stream(), _ptr(frames), _ptr(x_t), n // 3, tl, th, float(scale), _ptr(_dev(out, "out"))),
+               "mpg_tempo_vel_pack")
+    return out
+
+
+def tempo_vel_pack_bwd(dout, th, out=None):
+    """gradient of tempo_vel_pack with respect to the frames: dout [B, 12 th th] -> [3B, th, th, 1]"""
+    lib = _lib.load()
+    dout = _cont(dout, "dout")
+    if dout.dim() != 2 or dout.shape[1] != 12 * th * th:
+        raise _lib.MpgError("tempo_vel_pack_bwd: dout %s is not [B, %d]" % (tuple(dout.shape), 12 * th * th))
+    b = dout.shape[0]
+    if out is None:
+        out = torch.empty((3 * b, th, th, 1), dtype=torch.float32, device=dout.device)
+    elif tuple(out.shape) != (3 * b, th, th, 1) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise _lib.MpgError("tempo_vel_pack_bwd: out %s is not a contiguous fp32 [%d, %d, %d, 1]" % (tuple(out.shape), 3 * b, th, th))
+    _lib.check(lib.mpg_tempo_vel_pack_bwd(_stream(), _ptr(dout), b, th, _ptr(_dev(out, "out"))), "mpg_tempo_vel_pack_bwd")
+    return out
+
+
 def adam_step_staged(p, grad, m, v, mask, state, lr, total_grads, use_loss_scaling, beta1, beta2, eps=1e-8, ls_inc=0.0005,
                      ls_dec=1.0, ema_shadow=None, ema_decay=0.999):
     """one optimiser call of multipassGAN-8x.py:1305-1362 / 490-541 on flat fp32 buffers (mpg_adam_step_staged)"""
