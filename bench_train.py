@@ -131,6 +131,8 @@ def main():
     ap.add_argument("--prec", type=int, default=3, choices=(2, 3),
                     help="3: fp32-grade convolutions (default, what the parity tests hold the step to); 2: forward and "
                          "data-gradient convolutions at MPG_PREC_F16F6 where the kernels cover the shape (weight gradients stay at 3)")
+    ap.add_argument("--upsample-mode", type=int, default=1, choices=(0, 1, 2),
+                    help="c5: the resize inside the generator (upsampleMode: 0 bilinear, 1 nearest, 2 bicubic)")
     ap.add_argument("--eager", action="store_true", help="launch kernel by kernel instead of replaying the captured hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--launch-timeout", type=float, default=3000.0)
@@ -219,7 +221,7 @@ def timed(step, batch, args, comm, dev):
 def bench_c5(args, comm, dev, rank, world, rng):
     from mpgan_amd.arch import Cfg8x
     from mpgan_amd.train import Trainer8x
-    cfg = Cfg8x(tileSizeLow=args.tile, upRes=8, n_inputChannels=6, start_fms=256, max_fms=256)
+    cfg = Cfg8x(tileSizeLow=args.tile, upRes=8, n_inputChannels=6, start_fms=256, max_fms=256, upsampleMode=args.upsample_mode)
     tr = Trainer8x(cfg, device=str(dev), comm=comm, prec=args.prec)
     xs = torch.as_tensor(rng.random((args.batch, cfg.n_input)).astype(np.float32), device=dev)
     ys = torch.as_tensor(rng.random((args.batch, cfg.n_output)).astype(np.float32), device=dev)
@@ -232,7 +234,8 @@ def bench_c5(args, comm, dev, rank, world, rng):
         "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": DTYPES[args.prec], "data": "synthetic",
         "config": {"workload": "BASELINE configs[4] per GPU: multipassGAN-8x.py final stage (percentage 3.0), tileSize %d -> %d^2, "
-                               "batch %d, firstNNArch, startFms 256, 6 input channels, WGAN-GP" % (args.tile, th, args.batch),
+                               "batch %d, firstNNArch, startFms 256, 6 input channels, WGAN-GP, upsampleMode %d" % (
+                                   args.tile, th, args.batch, args.upsample_mode),
                    "parallelism": "dp%d" % world, "tiles_per_s": round(world * args.batch / dt, 1),
                    "disc_loss": float(d), "gen_loss_complete": float(g)},
         "roofline": wgrad_roofline(dev, th // 2, args.batch, k=3, c=64) if rank == 0 else None,

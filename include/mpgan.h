@@ -413,6 +413,16 @@ int mpg_pixel_norm_bwd(mpg_stream_t stream, const float* dy, const float* x, siz
 /* gradient of the nearest upsample by integer factors (GAN.py:517; dy is [n,oh,ow,c]) */
 int mpg_resize_nearest_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx,
                            int h, int w);
+/* gradients of mpg_resize_bilinear / mpg_resize_bicubic (tf.image.resize_images method 0 / 2, GAN.py:541; the upsampling
+ * inside the first 8x generator with upsampleMode 0 / 2, multipassGAN-8x.py:629).  dy is [n,oh,ow,c]; dx [n,h,w,c] is
+ * overwritten, every element, those that no output reads with 0.  Any h, w, oh, ow >= 1, as in the forward.  The resize is
+ * Y = R_h X R_w^T, the gradient R_h^T dY R_w in two gather passes (along H into tmp, n*h*ow*c floats provided by the caller,
+ * then along W) with the forward's coordinates, indices and clamping; the bicubic weights carry the bits of the TF1
+ * coefficient table.  The order of every sum is fixed: the same dy gives the same bits. */
+int mpg_resize_bilinear_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx,
+                            int h, int w, float* tmp);
+int mpg_resize_bicubic_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx,
+                           int h, int w, float* tmp);
 /* gradient of mpg_avg_pool2 (dx is [n,h,w,c], dy [n,h/2,w/2,c]) */
 int mpg_avg_pool2_bwd(mpg_stream_t stream, const float* dy, int n, int h, int w, int c, float* dx);
 /* lerp(x, y, t) = x + (y - x) * t with t already clipped to [0,1] (multipassGAN-8x.py:598-599); x NULL = zeros */

@@ -154,6 +154,8 @@ PROTOTYPES = {
     "mpg_act_bwd": (_I, [_P, _P, _P, _Z, _I, _F, _P, _P]),
     "mpg_pixel_norm_bwd": (_I, [_P, _P, _P, _Z, _I, _F, _P]),
     "mpg_resize_nearest_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
+    "mpg_resize_bilinear_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "mpg_resize_bicubic_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "mpg_avg_pool2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "mpg_lerp": (_I, [_P, _P, _P, _Z, _F, _P]),
     "mpg_tensor_resample": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),

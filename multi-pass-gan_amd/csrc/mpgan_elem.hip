@@ -43,7 +43,7 @@ __global__ void conv_direct_kernel(const float* __restrict__ x, int n, int h, in
 }
 
 // ---------------------------------------------------------------- resize (legacy TF1 coordinates)
-// (source coordinate and the bilinear look-up: mpgan_resize.h, shared with mpg_tempo_vel_pack)
+// (source coordinate, taps and the bilinear look-up: mpgan_resize.h, shared with mpg_tempo_vel_pack and the adjoints)
 __global__ void resize_nearest_kernel(const float* __restrict__ x, int n, int h, int w, int c,
                                       float* __restrict__ y, int oh, int ow, float sy, float sx) {
     const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
@@ -72,24 +72,7 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ x, int n, int h
     y[idx] = resize_bilinear_at(x + (size_t)b * h * w * c + ch, h, w, c, oy, ox, sy, sx);
 }
 
-// TF 1.x ResizeBicubic: Keys A = -0.75, fraction quantised to 1/1024, taps clamped.
-__device__ __forceinline__ void bicubic_taps(int o, float scale, int in_size, int idx[4], float wt[4]) {
-    const float A = -0.75f;
-    const float s = resize_src_coord(o, scale);
-    const int i = (int)floorf(s);
-    const float delta = s - (float)i;
-    const int off = (int)lrintf(delta * 1024.f);
-    const float x0 = (float)off / 1024.f;
-    const float x1 = (float)(1024 - off) / 1024.f;
-    const float xa = x0 + 1.f, xb = x1 + 1.f;
-    wt[0] = ((A * xa - 5.f * A) * xa + 8.f * A) * xa - 4.f * A;
-    wt[1] = ((A + 2.f) * x0 - (A + 3.f)) * x0 * x0 + 1.f;
-    wt[2] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-    wt[3] = ((A * xb - 5.f * A) * xb + 8.f * A) * xb - 4.f * A;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) idx[t] = min(max(i - 1 + t, 0), in_size - 1);
-}
-
+// TF 1.x ResizeBicubic (taps: mpgan_resize.h, shared with mpg_resize_bicubic_bwd)
 __global__ void resize_bicubic_kernel(const float* __restrict__ x, int n, int h, int w, int c,
                                       float* __restrict__ y, int oh, int ow, float sy, float sx) {
     const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;

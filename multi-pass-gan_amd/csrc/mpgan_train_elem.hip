@@ -1,9 +1,10 @@
 // Elementwise and reducing companions of the training step on the vector ALUs, fp32 NHWC: the backward passes of the
-// activations, pixel norm, nearest resize and 2x2 average pool, lerp, the |a - b| / (a - b)^2 loss sums, the backward
-// of the backward pass of the minibatch-stddev layer (WGAN-GP), and what held-out evaluation adds: the six means of a
-// critic's logits and the 8-bit grey mosaics of test tiles.  Entries: mpg_act_bwd, mpg_pixel_norm_bwd,
-// mpg_resize_nearest_bwd, mpg_avg_pool2_bwd, mpg_lerp, mpg_pair_reduce, mpg_minibatch_stddev_bwd2, mpg_logit_stats,
-// mpg_tiles_to_gray8.
+// activations, pixel norm, nearest / bilinear / bicubic resize and 2x2 average pool, lerp, the |a - b| / (a - b)^2 loss
+// sums, the backward of the backward pass of the minibatch-stddev layer (WGAN-GP), and what held-out evaluation adds: the
+// six means of a critic's logits and the 8-bit grey mosaics of test tiles.  Entries: mpg_act_bwd, mpg_pixel_norm_bwd,
+// mpg_resize_nearest_bwd, mpg_resize_bilinear_bwd, mpg_resize_bicubic_bwd, mpg_avg_pool2_bwd, mpg_lerp, mpg_pair_reduce,
+// mpg_minibatch_stddev_bwd2, mpg_logit_stats, mpg_tiles_to_gray8.
+#include "mpgan_resize.h"
 #include "mpgan_valu.h"
 
 using namespace mpg::valu;
@@ -72,6 +73,44 @@ __global__ void resize_nearest_bwd_kernel(const float* __restrict__ dy, int n, i
         for (int dxx = 0; dxx < fx; ++dxx)
             s += dy[(((size_t)b * oh + iy * fy + dyy) * ow + ix * fx + dxx) * c + ch];
     dx[idx] = s * scale;
+}
+
+// One axis of the adjoint of the bilinear (METHOD 0) / bicubic (METHOD 2) resize: Y = R_h X R_w^T, so dX = R_h^T dY R_w, one
+// launch per axis.  src is [outer, out, inner], dst [outer, in, inner]; a thread owns one dst element, source index i of the
+// axis, and GATHERS: it walks the outputs o that can have a tap on i in ascending order, forms the forward's taps of o
+// (mpgan_resize.h) and adds weight * src[o] for every tap whose clamped index is i -- at the borders two taps of one o can be.
+// No scatter, no atomics, a fixed order: the same input gives the same bits.  An i that no output reads is written 0.
+// The window [first, last] is integer arithmetic.  With e = floor(o * in / out) taken exactly, a tap i0 + t (t in LO .. HI) of o can
+// be i only if i - HI <= i0 <= i - LO; clamping widens that only at i = 0 and i = in - 1, where the window is cut at 0 and
+// out - 1 anyway.  The forward's i0 = floor(float32(o) * float32(in / out)) is within 1 of e, so e is in
+// [i - HI - 1, i - LO + 1]: (i - HI - 1) * out / in <= o < (i - LO + 2) * out / in.  Only o in [0, out) is ever read.
+template <int METHOD>
+__global__ void resize_axis_bwd_kernel(const float* __restrict__ src, size_t outer, int out, int in, size_t inner,
+                                       float scale, float* __restrict__ dst) {
+    constexpr int T = METHOD == 0 ? 2 : 4, LO = METHOD == 0 ? 0 : -1, HI = METHOD == 0 ? 1 : 2;
+    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+    if (idx >= outer * in * inner) return;
+    const size_t k = idx % inner;
+    const size_t p = idx / inner;
+    const int i = (int)(p % in);
+    const size_t b = p / in;
+    const long long lo_num = (long long)(i - HI - 1) * out, hi_num = (long long)(i - LO + 2) * out;     // hi_num > 0
+    const int first = lo_num > 0 ? (int)((lo_num + in - 1) / in) : 0;
+    const long long past = (hi_num + in - 1) / in;
+    const int last = past < out ? (int)past - 1 : out - 1;
+    const float* col = src + b * out * inner + k;
+    float s = 0.f;
+    for (int o = first; o <= last; ++o) {
+        int ti[T];
+        float tw[T];
+        if constexpr (METHOD == 0) bilinear_taps(o, scale, in, ti, tw);
+        else bicubic_taps<true>(o, scale, in, ti, tw);
+        const float v = col[(size_t)o * inner];
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+            if (ti[t] == i) s += tw[t] * v;
+    }
+    dst[idx] = s;
 }
 
 // 2x2 average pool backward: every input pixel receives a quarter of its output pixel
@@ -304,6 +343,32 @@ extern "C" int mpg_resize_nearest_bwd(mpg_stream_t stream, const float* dy, int 
     hipLaunchKernelGGL(resize_nearest_bwd_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, dy, n, oh,
                        ow, c, dx, h, w, 1.f);
     MPG_LAUNCH_CHECK("resize_nearest_bwd_kernel");
+}
+
+// dy [n,oh,ow,c] -> tmp [n,h,ow,c] along H -> dx [n,h,w,c] along W; the scales are the forward's (float)in / (float)out
+template <int METHOD>
+static int resize_bwd(const char* name, mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx, int h,
+                      int w, float* tmp) {
+    MPG_REQUIRE(dy && dx && tmp, "%s: null pointer", name);
+    MPG_REQUIRE(n >= 1 && h >= 1 && w >= 1 && c >= 1 && oh >= 1 && ow >= 1, "%s: bad shape", name);
+    const float sy = (float)h / (float)oh, sx = (float)w / (float)ow;
+    const size_t rows = (size_t)n * h, inner_h = (size_t)ow * c;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((resize_axis_bwd_kernel<METHOD>), dim3(grid_for(rows * inner_h)), dim3(BLK), 0, s, dy, (size_t)n, oh, h,
+                       inner_h, sy, tmp);
+    hipLaunchKernelGGL((resize_axis_bwd_kernel<METHOD>), dim3(grid_for(rows * w * c)), dim3(BLK), 0, s, (const float*)tmp, rows,
+                       ow, w, (size_t)c, sx, dx);
+    MPG_LAUNCH_CHECK(name);
+}
+
+extern "C" int mpg_resize_bilinear_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx, int h,
+                                       int w, float* tmp) {
+    return resize_bwd<0>("mpg_resize_bilinear_bwd", stream, dy, n, oh, ow, c, dx, h, w, tmp);
+}
+
+extern "C" int mpg_resize_bicubic_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx, int h,
+                                      int w, float* tmp) {
+    return resize_bwd<2>("mpg_resize_bicubic_bwd", stream, dy, n, oh, ow, c, dx, h, w, tmp);
 }
 
 extern "C" int mpg_avg_pool2_bwd(mpg_stream_t stream, const float* dy, int n, int h, int w, int c, float* dx) {

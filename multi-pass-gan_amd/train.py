@@ -393,6 +393,31 @@ class ResizeNearestBwdFn(torch.autograd.Function):
         return ResizeNearestFn.apply(g, *ctx.ohw), None
 
 
+class ResizeFn(torch.autograd.Function):
+    """tf.image.resize_images(x, [oh, ow], method) with method 0 (bilinear) or 2 (bicubic): the upsampling inside the first
+    8x generator with upsampleMode 0 / 2 (multipassGAN-8x.py:629).  Linear in x: only the shapes and the method are kept,
+    and ResizeBwdFn's backward is this forward again, so the pair differentiates to any order"""
+    @staticmethod
+    def forward(ctx, x, oh, ow, method):
+        ctx.hw, ctx.method = (x.shape[1], x.shape[2]), method
+        return ops.resize_images(x.detach().contiguous(), oh, ow, method)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ResizeBwdFn.apply(dy, ctx.hw, ctx.method), None, None, None
+
+
+class ResizeBwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dy, hw, method):
+        ctx.ohw, ctx.method = (dy.shape[1], dy.shape[2]), method
+        return train_ops.resize_bwd(dy.detach(), hw[0], hw[1], method)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ResizeFn.apply(g, ctx.ohw[0], ctx.ohw[1], ctx.method), None, None
+
+
 class LerpFn(torch.autograd.Function):
     """lerp(x, y, t) (multipassGAN-8x.py:598-599); x may be None (tf.zeros_like).  Linear in both operands: the backward is
     made of lerps.  train_ops.lerp clamps t to [0, 1], and 1 - clamp(t) = clamp(1 - t), so t is kept as given"""
@@ -772,8 +797,9 @@ class TrainSession(object):
             x = ev(n.inputs[0])
             if n.attrs["method"] == 1:
                 return ResizeNearestFn.apply(x, n.attrs["oh"], n.attrs["ow"])
-            if x.requires_grad:
-                raise NotImplementedError("gradient of bilinear / bicubic resize (only applied to network inputs)")
+            if x.requires_grad:                         # the generator's feature maps with upsampleMode 0 / 2
+                return ResizeFn.apply(x, n.attrs["oh"], n.attrs["ow"], n.attrs["method"])
+            # network inputs, eval_mode, the critic's low-res condition: nothing to differentiate, no graph node
             return ops.resize_images(x.contiguous(), n.attrs["oh"], n.attrs["ow"], n.attrs["method"])
         raise G.GraphError("training: no lowering for %r" % (n,))
 

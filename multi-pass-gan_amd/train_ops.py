@@ -200,6 +200,28 @@ def resize_nearest_bwd(dy, h, w):
     return dx
 
 
+_RESIZE_BWD = {0: "mpg_resize_bilinear_bwd", 1: "mpg_resize_nearest_bwd", 2: "mpg_resize_bicubic_bwd"}
+
+
+def resize_bwd(dy, h, w, method):
+    """gradient of ops.resize_images(x [n,h,w,c], oh, ow, method) for dy [n,oh,ow,c] (method ids of GAN.py:541).  Bilinear
+    and bicubic: any sizes, two gather passes through a [n,h,ow,c] buffer; nearest: integer factors (resize_nearest_bwd)"""
+    if method not in _RESIZE_BWD:
+        raise _lib.MpgError("resize method %r not supported" % (method,))
+    if method == 1:
+        return resize_nearest_bwd(dy, h, w)
+    lib = _lib.load()
+    dy = _cont(dy, "dy")
+    n, oh, ow, c = dy.shape
+    if min(n, h, w, c, oh, ow) < 1:             # before the buffers: torch.empty refuses a negative size in its own words
+        raise _lib.MpgError("%s: bad shape %s -> [%d, %d]" % (_RESIZE_BWD[method], tuple(dy.shape), h, w))
+    dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dy.device)
+    tmp = torch.empty((n, h, ow, c), dtype=torch.float32, device=dy.device)
+    _lib.check(getattr(lib, _RESIZE_BWD[method])(_stream(), _ptr(dy), n, oh, ow, c, _ptr(dx), h, w, _ptr(tmp)),
+               _RESIZE_BWD[method])
+    return dx
+
+
 def max_pool_bwd(dy, arg, h, w, k, s):
     lib = _lib.load()
     dy = _cont(dy, "dy")
