@@ -357,6 +357,38 @@ int mpg_conv2d_wgrad_mfma(mpg_stream_t stream, const float* x, int n, int h, int
  * This is what tf.gradients' Conv2DBackpropFilter does for the layers of GAN.py:686-691 under multipassGAN-4x.py:880-902. */
 int mpg_conv2d_wgrad_g8(mpg_stream_t stream, const void* x_g8, int n, int h, int w, int cin, const void* dy_g8, int cout,
                         int kh, int kw, float wscale, int prec, const float* x_amax, const float* dy_amax, float* dw);
+/* The launches the two entries above make for a shape, in launch order: a query like mpg_conv_pack_size, host arithmetic
+ * only (no device is touched).  Returns the number of launches, 0 for a shape or filter the entries refuse, and fills
+ * records[i * MPG_WGRAD_PLAN_INTS + field] for the first max_records of them (records may be NULL to count only).
+ * Fields of a record (a field of the other form is 0):
+ *    0 form            MPG_WGRAD_FORM_ROW: one filter row per block; MPG_WGRAD_FORM_RING: all rows of a square 3x3 / 4x4 / 5x5
+ *                      filter per block, x rows in an LDS ring
+ *    1 k               kernel instantiation: filter width (row form), filter size (ring form)
+ *    2 cotw            ... cout tiles of 32 per wave (row form) / per window (ring form)
+ *    3 prec            ... products: 3 (MPG_PREC_F16X3) or 1 (MPG_PREC_F16X1)
+ *    4 blocks          grid size, padding blocks included
+ *    5 lds_bytes       dynamic LDS of a block
+ *   row form: a launch covers input channels [ci0, ci0 + cin) and `windows` windows of `cout` output channels from co0
+ *    6 ci0   7 co0   8 cin   9 cout
+ *   10 cit             ci tiles of 32, one per wave
+ *   11 cog             groups of cotw cout tiles, one per wave
+ *   12 ks              waves that share the 16-pixel k-steps of a chunk (cit * cog * ks <= 8 waves)
+ *   13 chunk           pixels of a row staged at a time
+ *   14 windows         equal cout windows merged into this launch (>= 1)
+ *   15 nsplit          blocks per filter row and window: ranges of the n * h image rows
+ *   16 rows_per_split  image rows of a range
+ *   ring form: one launch covers all channels
+ *   17 chunks          column chunks of 64 pixels per row
+ *   18 n_ci            ci tiles of 32
+ *   19 n_cow           cout windows of 32 * cotw
+ *   20 ranges          row ranges per image
+ *   21 rows_per_range  output rows of a range
+ *   22 n_outer         n * ranges * chunks; each runs n_ci * n_cow blocks
+ *   23 reserved        0 */
+#define MPG_WGRAD_PLAN_INTS 24
+#define MPG_WGRAD_FORM_ROW 0
+#define MPG_WGRAD_FORM_RING 1
+int mpg_conv2d_wgrad_plan(int n, int h, int w, int cin, int cout, int kh, int kw, int prec, int32_t* records, int max_records);
 /* dy_amax: NULL, or a device float holding max |dy| already computed with mpg_absmax */
 /* d loss / d x of the same convolution, any stride / filter size (the strided 4x4 discriminator
  * convs, multipassGAN-4x.py:607-614).  The filter is passed with its channel axes swapped,

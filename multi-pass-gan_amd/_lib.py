@@ -17,6 +17,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 PREC_F16X1, PREC_F16F6, PREC_F16X3 = 1, 2, 3
 G8_F16 = 0
 MAX_SEG = 4
+WGRAD_PLAN_INTS, WGRAD_FORM_ROW, WGRAD_FORM_RING = 24, 0, 1                # MPG_WGRAD_* of include/mpgan.h
 DEFLATE_UNIT, DEFLATE_SLOT, DEFLATE_SLAB = 32768, 32768 + 16, 64 << 20    # MPG_DEFLATE_* of include/mpgan.h
 
 _ACT_IDS = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH}
@@ -144,6 +145,7 @@ PROTOTYPES = {
     "mpg_conv2d_wgrad_mfma_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "mpg_conv2d_wgrad_mfma": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _F, _I, _P, _Z, _P, _P, _P]),
     "mpg_conv2d_wgrad_g8": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "mpg_conv2d_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I]),
     "mpg_conv2d_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "mpg_fc_forward": (_I, [_P, _P, _I, _I, _P, _I, _F, _P, _I, _F, _P]),
     "mpg_channel_sum_ordered": (_I, [_P, _P, _Z, _I, _P, _P, _Z]),

@@ -782,9 +782,99 @@ hipError_t launch_ring(hipStream_t s, const WrArgs& a, int blocks) {
 }
 
 template <int KW, int COTW, int PREC>
-hipError_t launch(hipStream_t s, const WgArgs& a, int blocks, size_t lds_bytes, int windows) {
-    const hipError_t e = mpg::launch_dyn_lds<wgrad_mfma_kernel<KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks * windows), dim3(WG_THREADS), lds_bytes, s, a);
+hipError_t launch(hipStream_t s, const WgArgs& a, int blocks, size_t lds_bytes) {
+    const hipError_t e = mpg::launch_dyn_lds<wgrad_mfma_kernel<KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks), dim3(WG_THREADS), lds_bytes, s, a);
     return e != hipSuccess ? e : hipGetLastError();
+}
+
+// One launch of a weight gradient, as the planner below decides it: everything about it that does not depend on the
+// tensors' addresses.  The record of mpg_conv2d_wgrad_plan (include/mpgan.h) is this struct, field by field.
+struct WgLaunch {
+    int form;                // MPG_WGRAD_FORM_ROW (wgrad_mfma_kernel) or MPG_WGRAD_FORM_RING (wgrad_ring_kernel)
+    int k, cotw, prec;       // the instantiation: <k, COTW, PREC> of the row form (k = KW), <k, k, COTW, PREC> of the ring form
+    int blocks;              // grid size
+    int lds;                 // dynamic LDS bytes
+    int ci0, co0, cin, cout, cit, cog, ks, chunk, windows, nsplit, rows_per_split;      // row form (WgArgs)
+    int chunks, n_ci, n_cow, ranges, rows_per_range, n_outer;                           // ring form (WrArgs)
+};
+
+// The launches of one weight gradient, in launch order: pure host arithmetic on the shape.  `emit` gets each WgLaunch
+// and returns MPG_OK to go on; the first other value ends the plan and is returned.
+template <class Emit>
+int wgrad_plan(int n, int h, int w, int cin, int cout, int kh, int kw, int prec, Emit&& emit) {
+    // all filter rows of a tile in one block, x rows in an LDS ring (wgrad_ring_kernel): 1.02 .. 3x faster than the
+    // one-filter-row kernel on every 3x3 / 4x4 / 5x5 shape of the training steps (tools/probe_wgrad_shapes.py,
+    // profiles/r03/wgrad_variants.md); other filter shapes stay on that kernel
+    if (MPG_WG_RING && kh == kw && (kh == 3 || kh == 4 || kh == 5)) {
+        const int nco = (cout + 31) / 32;
+        // cout tiles per window: as many as the registers of a wave take beside its windows (5x5 with a 64-wide window is 7
+        // tiles on two of the waves and compiled to 28 spilled registers: 32-wide windows there, 4 tiles on one wave, 3 on
+        // the others; 3x3 with a 128-wide window at three products: 7 spilled registers, 64-wide there)
+        const int cotw = kh == 3 ? (nco >= 3 && prec != MPG_PREC_F16X3 ? 4 : (nco >= 2 ? 2 : 1)) : (kh == 4 && nco >= 2 ? 2 : 1);
+        WgLaunch l = {};
+        l.form = MPG_WGRAD_FORM_RING;
+        l.k = kh; l.cotw = cotw; l.prec = prec == MPG_PREC_F16X3 ? 3 : 1;
+        l.chunks = (w + WR_PX - 1) / WR_PX;
+        l.n_ci = (cin + 31) / 32;
+        l.n_cow = (cout + 32 * cotw - 1) / (32 * cotw);
+        // row ranges: a block pays for KH rows before its first output row, so ranges are as long as still leaves ~1024
+        // blocks (4 per CU) to balance the chip
+        const int per_range = n * l.chunks * l.n_ci * l.n_cow;
+        int rs = (1024 + per_range - 1) / per_range;
+        const int max_rs = h / 8 > 1 ? h / 8 : 1;
+        if (rs > max_rs) rs = max_rs;
+        if (rs < 1) rs = 1;
+        l.rows_per_range = (h + rs - 1) / rs;
+        l.ranges = (h + l.rows_per_range - 1) / l.rows_per_range;
+        l.n_outer = n * l.ranges * l.chunks;
+        l.blocks = ((l.n_outer + 7) / 8) * 8 * l.n_ci * l.n_cow;
+        l.lds = (kh + 1) * WR_XSLOT + 2 * (2 * cotw * 4 * WR_DP * 16);
+        return emit(l);
+    }
+    // a wave keeps KW * COTW accumulator tiles of 16 registers, 6 at most beside its fragments (256 registers per wave at two
+    // waves per SIMD; 8 tiles compiled to 3 spilled registers), so a 4- or 5-wide filter row takes 64 output channels per
+    // window (x is then staged twice, from L2)
+    const int co_step = kw >= 4 ? 64 : 128;
+    const bool merged = cout > co_step && cout % co_step == 0;     // equal windows: one launch, windows on grid.y
+    for (int ci0 = 0; ci0 < cin; ci0 += 128)
+        for (int co0 = 0; co0 < (merged ? 1 : cout); co0 += co_step) {
+            WgLaunch l = {};
+            l.form = MPG_WGRAD_FORM_ROW;
+            l.k = kw; l.prec = prec == MPG_PREC_F16X3 ? 3 : 1;
+            l.ci0 = ci0; l.co0 = co0;
+            l.cin = cin - ci0 < 128 ? cin - ci0 : 128;
+            l.cout = cout - co0 < co_step ? cout - co0 : co_step;
+            const int nci = (l.cin + 31) / 32, nco = (l.cout + 31) / 32;
+            l.cit = nci > 2 ? 4 : nci;                           // 1, 2, 4 ci tiles, one per wave
+            const int avail = WG_WAVES / l.cit;                   // waves left for output-channel groups
+            int cog = nco >= 3 ? 4 : nco;                         // 1, 2, 4
+            if (cog > avail) cog = avail;
+            l.cog = cog;
+            l.cotw = (nco + cog - 1) / cog;                       // co tiles per wave: 1, 2
+            const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
+            l.ks = WG_WAVES / (l.cit * l.cog);                    // waves left over split the 16-pixel k-steps of a chunk
+            l.chunk = 32 * l.ks < 64 ? 64 : 32 * l.ks;            // fewer barriers per pixel with 64-pixel chunks
+            const int xu = X_UNITS_DMA;
+            const int gx = l.cit * 4, gd = l.cog * l.cotw * 4;    // channel groups of the LDS images
+            // short rows, and at most xu (x) / D_UNITS_DMA (dy) LDS-DMA instructions per wave in the copy plan
+            auto x_units = [&](int chunk) { return gx * npl * (chunk + 16 + LDS_ROW_PAD); };
+            auto d_units = [&](int chunk) { return gd * npl * (chunk + LDS_ROW_PAD); };
+            while (l.chunk > 32 && (l.chunk / 2 >= w || x_units(l.chunk) > xu * WG_THREADS || d_units(l.chunk) > D_UNITS_DMA * WG_THREADS))
+                l.chunk /= 2;
+            if (l.chunk / 16 < l.ks) l.ks = l.chunk / 16;         // the other waves idle (tiny layers)
+            l.lds = 2 * (x_units(l.chunk) + d_units(l.chunk)) * 16;
+            const int rows = n * h;
+            int want = 1024 / kh;
+            if (want < 1) want = 1;
+            int nsplit = want < rows ? want : rows;
+            l.rows_per_split = (rows + nsplit - 1) / nsplit;
+            l.nsplit = (rows + l.rows_per_split - 1) / l.rows_per_split;
+            l.windows = merged ? cout / co_step : 1;
+            l.blocks = ((l.nsplit + 7) / 8) * 8 * kh * l.windows;
+            const int rc = emit(l);
+            if (rc != MPG_OK) return rc;
+        }
+    return MPG_OK;
 }
 
 // all launches of one weight gradient; dw is zeroed first (the row ranges are combined with atomics)
@@ -795,102 +885,52 @@ int wgrad_launches(hipStream_t s, const char* xg, const char* dg, const float* x
     MPG_REQUIRE((size_t)((cin > cout ? cin : cout) + 7) / 8 * 2 * h * w < (1u << 30), "mpg_conv2d_wgrad: image too large");
     hipError_t e = mpg::zero_async(dw, (size_t)kh * kw * cin * cout * sizeof(float), s);
     if (e != hipSuccess) return mpg::hip_check(e, "mpg_conv2d_wgrad: memset");
-    // all filter rows of a tile in one block, x rows in an LDS ring (wgrad_ring_kernel): 1.02 .. 3x faster than the
-    // one-filter-row kernel on every 3x3 / 4x4 / 5x5 shape of the training steps (tools/probe_wgrad_shapes.py,
-    // profiles/r03/wgrad_variants.md); other filter shapes stay on that kernel
-    if (MPG_WG_RING && kh == kw && (kh == 3 || kh == 4 || kh == 5)) {
-        const int nco = (cout + 31) / 32;
-        // cout tiles per window: as many as the registers of a wave take beside its windows (5x5 with a 64-wide window is 7
-        // tiles on two of the waves and compiled to 28 spilled registers: 32-wide windows there, 4 tiles on one wave, 3 on
-        // the others; 3x3 with a 128-wide window at three products: 7 spilled registers, 64-wide there)
-        const int cotw = kh == 3 ? (nco >= 3 && prec != MPG_PREC_F16X3 ? 4 : (nco >= 2 ? 2 : 1)) : (kh == 4 && nco >= 2 ? 2 : 1);
-        WrArgs a;
-        a.xg = xg; a.dg = dg; a.x_amax = x_amax; a.d_amax = d_amax; a.zeros = zeros; a.dw = dw;
-        a.n = n; a.h = h; a.w = w;
-        a.x_cg = (cin + 7) / 8; a.d_cg = (cout + 7) / 8;
-        a.cin_total = cin; a.cout_total = cout;
-        a.pt = (kh - 1) / 2;
-        a.wscale = wscale;
-        a.chunks = (w + WR_PX - 1) / WR_PX;
-        a.n_ci = (cin + 31) / 32;
-        a.n_cow = (cout + 32 * cotw - 1) / (32 * cotw);
-        // row ranges: a block pays for KH rows before its first output row, so ranges are as long as still leaves ~1024
-        // blocks (4 per CU) to balance the chip
-        const int per_range = n * a.chunks * a.n_ci * a.n_cow;
-        int rs = (1024 + per_range - 1) / per_range;
-        const int max_rs = h / 8 > 1 ? h / 8 : 1;
-        if (rs > max_rs) rs = max_rs;
-        if (rs < 1) rs = 1;
-        a.rows_per_range = (h + rs - 1) / rs;
-        a.ranges = (h + a.rows_per_range - 1) / a.rows_per_range;
-        a.n_outer = n * a.ranges * a.chunks;
-        const int blocks = ((a.n_outer + 7) / 8) * 8 * a.n_ci * a.n_cow;
+    const int rc = wgrad_plan(n, h, w, cin, cout, kh, kw, prec, [&](const WgLaunch& l) -> int {
         hipError_t le = hipErrorInvalidValue;
-#define MPG_WR(K, C)                                                                      \
-    if (kh == K && cotw == C)                                                             \
-        le = prec == MPG_PREC_F16X3 ? launch_ring<K, K, C, 3>(s, a, blocks) : launch_ring<K, K, C, 1>(s, a, blocks)
-        MPG_WR(3, 1); MPG_WR(3, 2); MPG_WR(4, 1); MPG_WR(4, 2); MPG_WR(5, 1);
-        if (kh == 3 && cotw == 4) le = launch_ring<3, 3, 4, 1>(s, a, blocks);
-#undef MPG_WR
-        if (le != hipSuccess) return mpg::hip_check(le, "wgrad_ring_kernel");
-        MPG_LAUNCH_CHECK("mpg_conv2d_wgrad (ring)");
-    }
-    // a wave keeps KW * COTW accumulator tiles of 16 registers, 6 at most beside its fragments (256 registers per wave at two
-    // waves per SIMD; 8 tiles compiled to 3 spilled registers), so a 4- or 5-wide filter row takes 64 output channels per
-    // window (x is then staged twice, from L2)
-    const int co_step = kw >= 4 ? 64 : 128;
-    const bool merged = cout > co_step && cout % co_step == 0;     // equal windows: one launch, windows on grid.y
-    for (int ci0 = 0; ci0 < cin; ci0 += 128)
-        for (int co0 = 0; co0 < (merged ? 1 : cout); co0 += co_step) {
-            WgArgs a;
-            a.xg = xg; a.dg = dg; a.x_amax = x_amax; a.d_amax = d_amax; a.dw = dw; a.zeros = zeros;
+        if (l.form == MPG_WGRAD_FORM_RING) {
+            WrArgs a;
+            a.xg = xg; a.dg = dg; a.x_amax = x_amax; a.d_amax = d_amax; a.zeros = zeros; a.dw = dw;
             a.n = n; a.h = h; a.w = w;
             a.x_cg = (cin + 7) / 8; a.d_cg = (cout + 7) / 8;
-            a.cin_total = cin; a.cout_total = cout; a.ci0 = ci0; a.co0 = co0;
-            a.cin = cin - ci0 < 128 ? cin - ci0 : 128;
-            a.cout = cout - co0 < co_step ? cout - co0 : co_step;
-            a.kh = kh; a.pt = (kh - 1) / 2; a.pl = (kw - 1) / 2;
+            a.cin_total = cin; a.cout_total = cout;
+            a.pt = (kh - 1) / 2;
             a.wscale = wscale;
-            const int nci = (a.cin + 31) / 32, nco = (a.cout + 31) / 32;
-            a.cit = nci > 2 ? 4 : nci;                           // 1, 2, 4 ci tiles, one per wave
-            const int avail = WG_WAVES / a.cit;                   // waves left for output-channel groups
-            int cog = nco >= 3 ? 4 : nco;                         // 1, 2, 4
-            if (cog > avail) cog = avail;
-            a.cog = cog;
-            const int cotw = (nco + cog - 1) / cog;               // co tiles per wave: 1, 2
-            const int npl = prec == MPG_PREC_F16X3 ? 2 : 1;
-            a.ks = WG_WAVES / (a.cit * a.cog);                    // waves left over split the 16-pixel k-steps of a chunk
-            a.chunk = 32 * a.ks < 64 ? 64 : 32 * a.ks;            // fewer barriers per pixel with 64-pixel chunks
-            const int xu = X_UNITS_DMA;
-            const int gx = a.cit * 4, gd = a.cog * cotw * 4;      // channel groups of the LDS images
-            // short rows, and at most xu (x) / D_UNITS_DMA (dy) LDS-DMA instructions per wave in the copy plan
-            auto x_units = [&](int chunk) { return gx * npl * (chunk + 16 + LDS_ROW_PAD); };
-            auto d_units = [&](int chunk) { return gd * npl * (chunk + LDS_ROW_PAD); };
-            while (a.chunk > 32 && (a.chunk / 2 >= w || x_units(a.chunk) > xu * WG_THREADS || d_units(a.chunk) > D_UNITS_DMA * WG_THREADS))
-                a.chunk /= 2;
-            if (a.chunk / 16 < a.ks) a.ks = a.chunk / 16;         // the other waves idle (tiny layers)
-            a.xp = a.chunk + 16 + LDS_ROW_PAD;
-            a.dp = a.chunk + LDS_ROW_PAD;
-            const size_t lds = 2 * ((size_t)x_units(a.chunk) + d_units(a.chunk)) * 16;
-            MPG_REQUIRE(lds <= WG_LDS_MAX, "mpg_conv2d_wgrad: LDS plan %zu bytes", lds);
-            MPG_REQUIRE(x_units(a.chunk) <= xu * WG_THREADS && d_units(a.chunk) <= D_UNITS_DMA * WG_THREADS, "mpg_conv2d_wgrad: copy plan");
-            const int rows = n * h;
-            int want = 1024 / kh;
-            if (want < 1) want = 1;
-            int nsplit = want < rows ? want : rows;
-            a.rows_per_split = (rows + nsplit - 1) / nsplit;
-            a.nsplit = (rows + a.rows_per_split - 1) / a.rows_per_split;
-            const int blocks = ((a.nsplit + 7) / 8) * 8 * kh;
-            const int windows = merged ? cout / co_step : 1;
-            a.windows = windows;
-            hipError_t le = hipErrorInvalidValue;
-#define MPG_WGM(K, C)                                                                        \
-    if (kw == K && cotw == C)                                                                \
-        le = prec == MPG_PREC_F16X3 ? launch<K, C, 3>(s, a, blocks, lds, windows) : launch<K, C, 1>(s, a, blocks, lds, windows)
-            MPG_WGM(1, 1); MPG_WGM(1, 2); MPG_WGM(3, 1); MPG_WGM(3, 2); MPG_WGM(4, 1); MPG_WGM(5, 1);
-#undef MPG_WGM
-            if (le != hipSuccess) return mpg::hip_check(le, "wgrad_mfma_kernel");
+            a.chunks = l.chunks; a.n_ci = l.n_ci; a.n_cow = l.n_cow;
+            a.ranges = l.ranges; a.rows_per_range = l.rows_per_range; a.n_outer = l.n_outer;
+#define MPG_WR(K, C)                                                                      \
+    if (l.k == K && l.cotw == C)                                                          \
+        le = l.prec == 3 ? launch_ring<K, K, C, 3>(s, a, l.blocks) : launch_ring<K, K, C, 1>(s, a, l.blocks)
+            MPG_WR(3, 1); MPG_WR(3, 2); MPG_WR(4, 1); MPG_WR(4, 2); MPG_WR(5, 1);
+            if (l.k == 3 && l.cotw == 4) le = launch_ring<3, 3, 4, 1>(s, a, l.blocks);
+#undef MPG_WR
+            return le != hipSuccess ? mpg::hip_check(le, "wgrad_ring_kernel") : MPG_OK;
         }
+        WgArgs a;
+        a.xg = xg; a.dg = dg; a.x_amax = x_amax; a.d_amax = d_amax; a.dw = dw; a.zeros = zeros;
+        a.n = n; a.h = h; a.w = w;
+        a.x_cg = (cin + 7) / 8; a.d_cg = (cout + 7) / 8;
+        a.cin_total = cin; a.cout_total = cout; a.ci0 = l.ci0; a.co0 = l.co0;
+        a.cin = l.cin; a.cout = l.cout;
+        a.windows = l.windows;
+        a.kh = kh; a.pt = (kh - 1) / 2; a.pl = (kw - 1) / 2;
+        a.cit = l.cit; a.cog = l.cog; a.ks = l.ks;
+        a.chunk = l.chunk;
+        a.xp = l.chunk + 16 + LDS_ROW_PAD;
+        a.dp = l.chunk + LDS_ROW_PAD;
+        a.nsplit = l.nsplit; a.rows_per_split = l.rows_per_split;
+        a.wscale = wscale;
+        const int npl = l.prec == 3 ? 2 : 1;
+        const int xunits = l.cit * 4 * npl * a.xp, dunits = l.cog * l.cotw * 4 * npl * a.dp;
+        MPG_REQUIRE((size_t)l.lds <= WG_LDS_MAX, "mpg_conv2d_wgrad: LDS plan %d bytes", l.lds);
+        MPG_REQUIRE(xunits <= X_UNITS_DMA * WG_THREADS && dunits <= D_UNITS_DMA * WG_THREADS, "mpg_conv2d_wgrad: copy plan");
+#define MPG_WGM(K, C)                                                                        \
+    if (l.k == K && l.cotw == C)                                                             \
+        le = l.prec == 3 ? launch<K, C, 3>(s, a, l.blocks, (size_t)l.lds) : launch<K, C, 1>(s, a, l.blocks, (size_t)l.lds)
+        MPG_WGM(1, 1); MPG_WGM(1, 2); MPG_WGM(3, 1); MPG_WGM(3, 2); MPG_WGM(4, 1); MPG_WGM(5, 1);
+#undef MPG_WGM
+        return le != hipSuccess ? mpg::hip_check(le, "wgrad_mfma_kernel") : MPG_OK;
+    });
+    if (rc != MPG_OK) return rc;
     MPG_LAUNCH_CHECK("mpg_conv2d_wgrad");
 }
 
@@ -926,6 +966,25 @@ static int wgrad_check(int n, int h, int w, int cin, int cout, int kh, int kw, i
     MPG_REQUIRE(kh >= 1 && kh <= 7 && (kw == 1 || kw == 3 || kw == 4 || kw == 5), "mpg_conv2d_wgrad: filter %dx%d not built", kh, kw);
     MPG_REQUIRE(prec == MPG_PREC_F16X1 || prec == MPG_PREC_F16X3, "mpg_conv2d_wgrad: prec %d", prec);
     return MPG_OK;
+}
+
+// the launch plan as numbers: host arithmetic only, no device is touched
+extern "C" int mpg_conv2d_wgrad_plan(int n, int h, int w, int cin, int cout, int kh, int kw, int prec, int32_t* records,
+                                     int max_records) {
+    if (wgrad_check(n, h, w, cin, cout, kh, kw, prec) != MPG_OK) return 0;
+    int count = 0;
+    wgrad_plan(n, h, w, cin, cout, kh, kw, prec, [&](const WgLaunch& l) -> int {
+        if (records != nullptr && count < max_records) {
+            int32_t* r = records + (size_t)count * MPG_WGRAD_PLAN_INTS;
+            const int32_t v[MPG_WGRAD_PLAN_INTS] = {l.form, l.k, l.cotw, l.prec, l.blocks, l.lds, l.ci0, l.co0, l.cin, l.cout, l.cit,
+                                                    l.cog, l.ks, l.chunk, l.windows, l.nsplit, l.rows_per_split, l.chunks, l.n_ci,
+                                                    l.n_cow, l.ranges, l.rows_per_range, l.n_outer, 0};
+            for (int i = 0; i < MPG_WGRAD_PLAN_INTS; ++i) r[i] = v[i];
+        }
+        ++count;
+        return MPG_OK;
+    });
+    return count;
 }
 
 // both operands already in G8 (the layer's forward input as the convolution kernel read it, and the scaled dy of the

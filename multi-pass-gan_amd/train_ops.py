@@ -30,6 +30,27 @@ def wgrad_mfma_ok(kh, kw, stride):
     return tuple(stride) == (1, 1) and 1 <= kh <= 7 and kw in (1, 3, 4, 5)
 
 
+WGRAD_PLAN_FIELDS = ("form", "k", "cotw", "prec", "blocks", "lds_bytes", "ci0", "co0", "cin", "cout", "cit", "cog", "ks", "chunk",
+                     "windows", "nsplit", "rows_per_split", "chunks", "n_ci", "n_cow", "ranges", "rows_per_range", "n_outer")
+
+
+def conv2d_wgrad_plan(n, h, w, cin, cout, kh, kw, prec=_lib.PREC_F16X3):
+    """the launches conv2d_wgrad_mfma / conv2d_wgrad_g8 make for a shape, in launch order: one dict per launch with the
+    fields of mpg_conv2d_wgrad_plan (form as "row" / "ring"); [] for a filter they refuse.  Needs no GPU."""
+    import ctypes
+    lib = _lib.load()
+    count = lib.mpg_conv2d_wgrad_plan(n, h, w, cin, cout, kh, kw, prec, None, 0)
+    buf = (ctypes.c_int32 * (max(count, 1) * _lib.WGRAD_PLAN_INTS))()
+    got = lib.mpg_conv2d_wgrad_plan(n, h, w, cin, cout, kh, kw, prec, buf, count)
+    assert got == count
+    plan = []
+    for i in range(count):
+        rec = dict(zip(WGRAD_PLAN_FIELDS, buf[i * _lib.WGRAD_PLAN_INTS:(i + 1) * _lib.WGRAD_PLAN_INTS]))
+        rec["form"] = "ring" if rec["form"] == _lib.WGRAD_FORM_RING else "row"
+        plan.append(rec)
+    return plan
+
+
 _UNIT = {}
 
 
