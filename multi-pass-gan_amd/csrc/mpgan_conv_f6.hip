@@ -49,25 +49,18 @@ namespace {
 #define MPG_W0 1
 #endif
 //   MPG_PIECES_AFTER 0   the LDS-DMA pieces of an fp16 group are issued in front of the group's operand wait (rounds 2-3)
-//   MPG_IMG_LATE 1  the image pieces of a stage may land during the next stage (measured slower: off)
-#ifndef MPG_IMG_LATE
-#define MPG_IMG_LATE 0
-#endif
 #ifndef MPG_PIECES_AFTER
 #define MPG_PIECES_AFTER 1
 #endif
-//   MPG_ALT 1       experiment, off: the second half of the waves of an 8-wave block runs a stage's correction steps BEFORE its
-//                   fp16 groups (complementary phases on a SIMD).  As compiled the corrections-first order keeps 265 spilled
-//                   registers at four cout tiles (profiles/r03/kloop_variants.md): not measured on the hardware
-#ifndef MPG_ALT
-#define MPG_ALT 0
-#endif
 // (measured and dropped: the NT steps `w_lo6 x a_hi6` riding in the last NT fp16 groups of the stage, operands prefetched like
-// the fp16 ones, only `w_hi6 x a_lo6` left as a separate phase: b1.B 650 us against 639, profiles/r03/kloop_variants.md)
-//   MPG_STAMPS 1    diagnostic build only: every wave accumulates, over the stages of its K loop, the s_memtime cycles from
-//                   the barrier release to (0) its first MFMA wait satisfied, (1) the end of the fp16 groups, (2) the end
-//                   of the correction steps, (3) the release of the next barrier, and writes the four sums to
-//                   y[(block * WAVES + wave) * 4 ..] when desc.reserved has bit 3 set (tools/probe_stamps.py)
+// the fp16 ones, only `w_hi6 x a_lo6` left as a separate phase: b1.B 650 us against 639, profiles/r03/kloop_variants.md;
+// the second half of the waves running a stage's corrections BEFORE its fp16 groups: 265 spilled registers at four cout
+// tiles, same file)
+//   MPG_STAMPS 1    diagnostic build only: every wave accumulates, over the barrier intervals of its K loop, the s_memtime
+//                   cycles (0) from the barrier release to its first MFMA wait satisfied, (1) in the fp16 groups, (2) in the
+//                   correction steps, (3) waiting for the next barrier, and writes the four sums to
+//                   y[(block * WAVES + wave) * 4 ..] when desc.reserved has bit 3 set (tools/probe_stamps.py).  With the
+//                   barrier in mid-stage an interval is [head, corr(st), fp16(st + 1), wait], else [head, fp16, corr, wait]
 #ifndef MPG_STAMPS
 #define MPG_STAMPS 0
 #endif
@@ -182,8 +175,6 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int r = lane & 31;
-    const int hh = lane >> 5;
 
     int bid = blockIdx.x;
     const int nblk = gridDim.x;
@@ -210,6 +201,12 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
     for (int s0 = 0; s0 < ((a.dbg & 1) ? 0 : a.nseg); ++s0) {
         const int s = seg_flip ? a.nseg - 1 - s0 : s0;
         const auto& sg = ap->seg[s];
+        // The lane's indices are derived again in every segment from an id the compiler cannot see through: lane-only
+        // terms of the addresses below would else be hoisted out of the segment loop and held in registers across both
+        // stage loops (the 128-register kernel has none to spare: they went to scratch).
+        int tid_seg = threadIdx.x;
+        asm volatile("" : "+v"(tid_seg));
+        const int tid = tid_seg, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
         if (NT <= 2 && sg.direct) {
             // 1x1 segment over cg_seg >= 2 channel groups: no halo, so no LDS image.  The G8 rows are already
             // fragment-shaped (16 B per pixel and group): lane (pixel r, half hh) loads its B operands from
@@ -437,35 +434,80 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
         half8 bh[PT][4];
         v4i o16n = {0, 0, 0, 0};
         const unsigned i_base = lds_off(img_lds);
+        constexpr int AH = MPG_AH, G16 = 4 * NT;
+        half8 aq[AH + 1];
+        // MID: the reads of the first NPG fp16 groups of `stage` (tap offsets `o`), issued under the last correction step of
+        // the stage before: no barrier stands between the two phases, the registers are free (the a_lo codes are made by
+        // step NT - 1) and what they read landed in front of the barrier behind which they are issued
+        constexpr int NAH = AH < G16 ? AH : G16;     // groups whose reads stand in front of the first group's MFMAs
+        // (the 128-register kernel, which keeps the barrier at the stage boundary, would also spill 3 registers for it)
+        constexpr int NPG = NT == 1 ? 0 : NAH;
+        constexpr int NPRE = kx_cum(NPG, NT, PT);
+        auto prefetch_head = [&](int stage, const v4i& o) {
+            const unsigned ab = lds_off(w_lds + (stage % R) * WSTAGE) + (unsigned)lane * 16u;
+            const int t[4] = {o.x, o.y, o.z, o.w};
+            static_for<0, NPG>([&](auto gc) {
+                constexpr int g = decltype(gc)::value, j = g / NT;
+                if constexpr (g % NT == 0)
+                    static_for<0, PT>([&](auto pc) {
+                        constexpr int pt = decltype(pc)::value;
+                        ds_read16<0>(bh[pt][j], i_base + (unsigned)(pixb[pt] + t[j]));
+                    });
+                ds_read16<g * 1024>(aq[g % (AH + 1)], ab);
+            });
+        };
 #if MPG_STAMPS
         unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts3_prev = 0;
         unsigned sum_head = 0, sum_f16 = 0, sum_f6 = 0, sum_bar = 0;
 #endif
 
-        auto run_stages = [&](auto oc) {
-        constexpr bool CORR_FIRST = decltype(oc)::value != 0;
-        int img_in_flight = 0;      // image pieces of the previous stage that may still be in flight behind this barrier
+        // The stage loop.  MID (two to four cout tiles, segments with sg.pref: every image has two stages between its issue
+        // and its first slot):
+        // the ONE barrier of a stage stands between its fp16 groups and its correction steps,
+        //     [first barrier] fp16(0) | corr(0) fp16(1) | corr(1) fp16(2) | ... | corr(NS-1) [drain]
+        // so an interval between two barriers pairs the latency- and VALU-bound corrections of one wave of a SIMD with
+        // the matrix-dense fp16 groups of its partner, and no operand wait stands directly behind a barrier but the
+        // first correction step's, whose operands are in registers by then.  Barrier `|` of stage st:
+        //   - every wave has left fp16(st) and corr(st-1): ring slot (st-1) % R and the image buffers that no slot of stage
+        //     st or later reads are free.  The weight pieces of stage st + 2 are issued behind it, in corr(st), the image
+        //     pieces (if a group is due) behind them in the first fp16 groups of stage st + 1: `vmcnt` issue order of an
+        //     interval is [weights][image].
+        //   - the wave's own wait in front of it covers what corr(st) and fp16(st+1) read: the weights of stage st + 1
+        //     (issued in the interval before) and an image whose first slot lies in stage st + 1; an image first read
+        //     later may stay in flight (run-time count), the next barrier's wait covers it with the weights behind it.
+        // !MID (tp 8 / 12: an image is first read in the stage after its issue, so it would have to be issued while
+        // corr(st-1) of a partner may still read the buffer it replaces): the barrier stands at the stage boundary.
+        auto run_stages = [&](auto mc) {
+        constexpr bool MID = decltype(mc)::value != 0;
+        if constexpr (MID) {
+            wait_dma_and_barrier<(D - 1) * NI>();     // image 0, stage 0 and the tap table
+            ds_read16<0>(o16n, lds_off(tap16 + hh * 4));
+            lgkm_wait<0>();
+            tie(o16n);
+            prefetch_head(0, o16n);
+        }
         for (int st = 0; st < NS; ++st) {
-            // stage st (and everything older, incl. the images issued before it) has landed; all waves are done
-            // with stage st-1.  (MPG_IMG_LATE: the image pieces of stage st-1 -- in front of its weight pieces in issue
-            // order, so `vmcnt` can count them with the weights -- may stay in flight when their group is first read two
-            // or more stages later.  Measured: b1.B 652 against 636 us, b2.A 229 against 231: off.)
-            if constexpr (MPG_IMG_LATE) wait_dma_rt((D - 1) * NI, img_in_flight);
-            else wait_dma_and_barrier<(D - 1) * NI>();
+            // !MID: stage st (and everything older, incl. the images issued before it) has landed; all waves are done
+            // with stage st-1
+            if constexpr (!MID) wait_dma_and_barrier<(D - 1) * NI>();
 #if MPG_STAMPS
-            if (st > 0) {       // the barrier's lgkmcnt(0) completed every stamp of the previous stage
-                sum_head += (unsigned)(ts1 - ts0);
-                sum_f16 += (unsigned)(ts2 - ts1);
-                sum_f6 += (unsigned)(ts3 - ts2);
-                if (st > 1) sum_bar += (unsigned)(ts0 - ts3_prev);
-                ts3_prev = ts3;
+            if constexpr (!MID) {
+                if (st > 0) {       // the barrier's lgkmcnt(0) completed every stamp of the previous stage
+                    sum_head += (unsigned)(ts1 - ts0);
+                    sum_f16 += (unsigned)(ts2 - ts1);
+                    sum_f6 += (unsigned)(ts3 - ts2);
+                    if (st > 1) sum_bar += (unsigned)(ts0 - ts3_prev);
+                    ts3_prev = ts3;
+                }
+                MPG_STAMP(ts0);
             }
-            MPG_STAMP(ts0);
 #endif
             // the tap table is constant over the segment: stage st + 1's entry is read at the head of stage st
-            if (st == 0) {
-                ds_read16<0>(o16n, lds_off(tap16 + hh * 4));
-                lgkm_wait<0>();
+            if constexpr (!MID) {
+                if (st == 0) {
+                    ds_read16<0>(o16n, lds_off(tap16 + hh * 4));
+                    lgkm_wait<0>();
+                }
             }
             tie(o16n);
             const v4i o16 = o16n;
@@ -481,15 +523,17 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
             // wave issues an MFMA (profiles/r02/kloop_analysis.md).  Order within the stage: the image pieces in the
             // first half of the groups, then the NI weight pieces of stage st + D, so `vmcnt((D-1) NI)` at the next
             // barrier still covers them.
-            const bool do_img = g_next < G && st * 8 >= (g_next - 1) * sg.tp;
+            // MID: the fp16 groups of stage st run in the interval behind the barrier of stage st - 1, which is the one
+            // that frees the buffer; the weight pieces go behind the correction MFMAs.
+            const int st_free = MID ? st - 1 : st;
+            const bool do_img = st_free >= 0 && g_next < G && st_free * 8 >= (g_next - 1) * sg.tp;
             const int img_chunk = g_next;
-            // first stage that reads group g_next: the one holding slot g_next * tp
-            img_in_flight = (MPG_IMG_LATE && do_img && (g_next * sg.tp) / 8 >= st + 2) ? sg.ni_img : 0;
+            // MID: the image stays in flight across this stage's barrier unless the next fp16 groups read it: its first
+            // slot g_next * tp lies in stage st + 1 (sg.pref: never earlier)
+            const int img_late = (MID && !(MPG_DIAG6 & 4) && do_img && (g_next * sg.tp) / 8 > st + 1) ? sg.ni_img : 0;
             if (do_img) ++g_next;
             const char* wb = w_lds + (st % R) * WSTAGE;
             const unsigned a_base = lds_off(wb) + (unsigned)lane * 16u;
-            constexpr int AH = MPG_AH, G16 = 4 * NT;
-            half8 aq[AH + 1];
             v8i hi6[PT], lo6[PT];
             int sb[PT], e16[PT];
             // fp16 group g = (k-step g / NT, cout tile g % NT): its reads are [the PT B fragments of the k-step when
@@ -523,6 +567,7 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
             // bf6 weight planes of the correction steps: step k < NT reads w_lo6[k], step k >= NT w_hi6[k - NT]
             constexpr int KS6 = 2 * NT;                            // correction steps
             constexpr int WD = MPG_WD < KS6 - 1 ? MPG_WD : KS6 - 1;
+            constexpr int WPC = (NI + NT - 1) / NT;          // MID: weight pieces per a_lo correction step
             v4i wq[WD + 1][2];
             auto read_w6 = [&](auto kc) {
                 constexpr int k = decltype(kc)::value;
@@ -531,13 +576,11 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
                 ds_read16<off + 1024>(wq[k % (WD + 1)][1], a_base);
             };
             // ---- the fp16 product: G16 groups of PT MFMAs ----
-            auto fp16_phase = [&](auto mk) {
-                constexpr bool MAKE_HI6 = decltype(mk)::value != 0;
-                // fp16 groups first, corrections behind them: the weight planes of correction step 0 are read in front of
-                // the last group (the correction phase then starts on operands that are there: its head was ~200 cycles of
-                // LDS latency, and the younger wave of a SIMD runs that phase alone)
-                constexpr bool W0_AHEAD = MAKE_HI6 && MPG_W0;
-                static_for<0, (AH < G16 ? AH : G16)>([&](auto gc) { read_group(gc); });
+            auto fp16_phase = [&]() {
+                // the weight planes of correction step 0 are read in front of the last group: the correction phase starts on
+                // operands that are there (MID: the first correction MFMA issues as soon as the barrier releases)
+                constexpr bool W0_AHEAD = MPG_W0 != 0;
+                static_for<(MID ? NPG : 0), NAH>([&](auto gc) { read_group(gc); });      // MID: the first NPG in prefetch_head
                 static_for<0, G16>([&](auto gc) {
                     constexpr int g = decltype(gc)::value, j = g / NT, nt = g % NT;
                     // the LDS-DMA pieces of the group: a wave waits 60-185 cycles per piece for the CU's address unit.  Behind
@@ -550,7 +593,7 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
                                     constexpr int i = g * IPG + decltype(kc)::value;
                                     if constexpr (i < MAXI) img_piece(img_chunk, std::integral_constant<int, i>{});
                                 });
-                        } else {
+                        } else if constexpr (!MID) {
                             static_for<0, WPG>([&](auto kc) {
                                 constexpr int i = (g - HALF) * WPG + decltype(kc)::value;
                                 if constexpr (i < NI) w_piece(st + D, std::integral_constant<int, i>{});
@@ -560,8 +603,9 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
                     if constexpr (!MPG_PIECES_AFTER) pieces();
                     if constexpr (g + AH < G16) read_group(std::integral_constant<int, g + AH>{});
                     if constexpr (W0_AHEAD && g == G16 - 1) read_w6(std::integral_constant<int, 0>{});
-                    lgkm_wait<kx_allowed(g, NT, PT, AH) + (W0_AHEAD && g == G16 - 1 ? 2 : 0)>();   // reads issued behind group g's own
-                    if constexpr (g == 0 && MAKE_HI6) { MPG_STAMP(ts1); }
+                    // reads issued behind group g's own (MID: the tap-table read stands behind the NPG groups read ahead)
+                    lgkm_wait<kx_allowed(g, NT, PT, AH) + (W0_AHEAD && g == G16 - 1 ? 2 : 0) + (MID && g < NPG ? 1 : 0)>();
+                    if constexpr (g == 0 && !MID) { MPG_STAMP(ts1); }
                     tie(aq[g % (AH + 1)]);
                     if constexpr (nt == 0)
                         static_for<0, PT>([&](auto pc) { tie(bh[decltype(pc)::value][j]); });
@@ -572,10 +616,8 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
                     if constexpr (MPG_PIECES_AFTER) pieces();
                     // the a_hi block scales and codes (VALU work under the matrix pipe): tile row g - 3 NT behind each group
                     // of the last k-step, whatever is left behind the last group
-                    if constexpr (MAKE_HI6) {
-                        if constexpr (g >= 3 * NT && g - 3 * NT < PT) make_hi6(std::integral_constant<int, g - 3 * NT>{});
-                        if constexpr (g == G16 - 1 && NT < PT) static_for<NT, PT>([&](auto pc) { make_hi6(pc); });
-                    }
+                    if constexpr (g >= 3 * NT && g - 3 * NT < PT) make_hi6(std::integral_constant<int, g - 3 * NT>{});
+                    if constexpr (g == G16 - 1 && NT < PT) static_for<NT, PT>([&](auto pc) { make_hi6(pc); });
                 });
             };
             // ---- the two bf6 corrections: step k < NT is w_lo6[k] x a_hi6, step k >= NT is w_hi6[k - NT] x a_lo6 ----
@@ -610,7 +652,14 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
                 if constexpr (k >= 1 && k + WD < KS6) read_w6(std::integral_constant<int, k + WD>{});
                 // reads issued behind W(k): at k = 0 the a_lo fragments and W(1 .. WD), later W(k + 1 .. k + WD)
                 constexpr int ahead = (k + WD < KS6 ? k + WD : KS6 - 1) - k;
-                lgkm_wait<(k == 0 ? 4 * PB : 0) + 2 * ahead>();
+                // MID: behind the last W read, in front of the last step's wait, the head of the next stage's fp16 groups
+                constexpr int pre = (MID && k == KS6 - 1) ? NPRE : 0;
+                if constexpr (pre != 0) {
+                    tie(o16n);
+                    prefetch_head(st + 1, o16n);
+                }
+                lgkm_wait<(k == 0 ? 4 * PB : 0) + 2 * ahead + pre>();
+                if constexpr (k == 0 && MID) { MPG_STAMP(ts1); }
                 tie(wq[k % (WD + 1)][0]);
                 tie(wq[k % (WD + 1)][1]);
                 const v8i w6 = __builtin_shufflevector(wq[k % (WD + 1)][0], wq[k % (WD + 1)][1], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -629,52 +678,61 @@ __global__ __launch_bounds__(Pipe6<NT>::WAVES * 64, Pipe6<NT>::OCC) void conv_mf
                     static_for<0, PT>([&](auto pc) {
                         if constexpr (lo_step(decltype(pc)::value, NT, PT) == k) make_lo6(pc);
                     });
+                } else if constexpr (MID) {
+                    // the weight pieces of stage st + D, one at a time behind the MFMAs of the a_lo steps, whose gaps carry
+                    // no conversion work: the slot they overwrite was last read in corr(st - 1), which every wave left
+                    // before this stage's barrier
+                    static_for<0, WPC>([&](auto ic) {
+                        constexpr int i = (k - NT) * WPC + decltype(ic)::value;
+                        if constexpr (i < NI) w_piece(st + D, std::integral_constant<int, i>{});
+                    });
                 }
             });
 #else
+            if constexpr (MID) static_for<0, NI>([&](auto ic) { w_piece(st + D, ic); });
             // (named first: an asm operand alone does not capture a variable of the enclosing lambda)
             const v8i& h0 = hi6[0];
             const int &s0 = sb[0], &e0 = e16[0];
             asm volatile("" ::"v"(h0), "v"(s0), "v"(e0));
 #endif
             };
-            // The two waves of a SIMD (wave w and w + WAVES / 2 of an 8-wave block) walk the stage in OPPOSITE orders: the
-            // first half runs the matrix-dense fp16 groups first and the latency- and VALU-bound correction steps last,
-            // the second half the other way round (all operands of a stage are there at its barrier).  Run in the same
-            // order the older wave of a SIMD wins every arbitration, finishes after ~3300 cycles and idles, and the
-            // younger one ends the stage alone in its correction steps at < 50 % matrix duty (profiles/r03/kloop_stamps.txt).
-            if constexpr (CORR_FIRST) {
-                static_for<0, PT>([&](auto pc) {
-                    constexpr int pt = decltype(pc)::value;
-                    static_for<0, 4>([&](auto jc) {
-                        constexpr int j = decltype(jc)::value;
-                        ds_read16<0>(bh[pt][j], i_base + (unsigned)(pixb[pt] + to16[j]));
-                    });
-                });
-                lgkm_wait<0>();
-                static_for<0, PT>([&](auto pc) {
-                    static_for<0, 4>([&](auto jc) { tie(bh[decltype(pc)::value][decltype(jc)::value]); });
-                    make_hi6(pc);
-                });
-                MPG_STAMP(ts1);
-                bf6_phase(std::integral_constant<int, 0>{});
-                MPG_STAMP(ts2);
-                fp16_phase(std::integral_constant<int, 0>{});
-            } else {
-                fp16_phase(std::integral_constant<int, 1>{});
-                MPG_STAMP(ts2);
-                bf6_phase(std::integral_constant<int, MPG_W0>{});
+            fp16_phase();
+            MPG_STAMP(ts2);
+            if constexpr (MID) {
+                // the weights of stage st + 1 (the newest pieces but for an image issued in the groups above) have landed
+                wait_dma_late_and_barrier(img_late);
+#if MPG_STAMPS
+                // (the barrier's lgkmcnt(0) completed every stamp in front of it) the interval behind the barrier of stage
+                // st - 1: head ts0 .. ts1, correction steps .. ts3, fp16 groups .. ts2, wait for this barrier .. new ts0
+                if (st > 0) {
+                    sum_head += (unsigned)(ts1 - ts0);
+                    sum_f6 += (unsigned)(ts3 - ts1);
+                    sum_f16 += (unsigned)(ts2 - ts3);
+                    if (st > 1) sum_bar += (unsigned)(ts0 - ts3_prev);
+                    ts3_prev = ts2;
+                }
+                MPG_STAMP(ts0);
+#endif
             }
+            bf6_phase(std::integral_constant<int, MPG_W0>{});
             MPG_STAMP(ts3);
         }
         };
-        // one loop per order, chosen once per segment (a branch inside the stage body would merge the two register
-        // allocations at every stage: 390 spilled registers when tried)
-#if MPG_ALT
-        if (WAVES == 8 && wave_u >= WAVES / 2) run_stages(std::integral_constant<int, 1>{});
-        else
-#endif
+        // one loop per barrier position, chosen once per segment (a branch inside the stage body would merge the two
+        // register allocations at every stage: 390 spilled registers when tried)
+        // (two `if`s in a row, the second on a value the compiler cannot tell from the first, like the direct path above: as
+        // the two arms of ONE branch the loops spill 130 to 830 registers)
+        // The one-cout-tile kernel keeps the barrier at the stage boundary for every segment: with four waves per SIMD its
+        // phases already run beside three other waves', and measured with the barrier in mid-stage b2.A took 217.9 us
+        // against 213.9 and b2.B 92.5 against 89.6 (profiles/r14/bench_c2_per_layer.txt, kloop_stamps_barrier.txt).
+        if constexpr (NT == 1) {
             run_stages(std::integral_constant<int, 0>{});
+        } else {
+            int mid = __builtin_amdgcn_readfirstlane(sg.pref);
+            if (mid) run_stages(std::integral_constant<int, 1>{});
+            asm volatile("" : "+s"(mid));
+            if (!mid) run_stages(std::integral_constant<int, 0>{});
+        }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __syncthreads();
 #if MPG_STAMPS

@@ -19,15 +19,36 @@ template <int N>
 __device__ __forceinline__ void wait_dma_and_barrier() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
-// ... with `extra` (0..7, wave-uniform) more of the newest operations allowed in flight
-__device__ __forceinline__ void wait_dma_rt(int base, int extra) {
-    switch (base + extra) {
-#define MPG_W(n) case n: wait_dma_and_barrier<n>(); break;
-        MPG_W(0) MPG_W(1) MPG_W(2) MPG_W(3) MPG_W(4) MPG_W(5) MPG_W(6) MPG_W(7) MPG_W(8) MPG_W(9) MPG_W(10) MPG_W(11)
-        MPG_W(12) MPG_W(13) MPG_W(14) MPG_W(15)
-#undef MPG_W
-        default: wait_dma_and_barrier<0>(); break;
-    }
+// at most `late` (0..4, wave-uniform) of the newest LDS-DMA operations still in flight, every LDS read done, then the
+// barrier -- as ONE asm statement: the compiler sees no branch, so a K loop with several hundred live registers keeps
+// one register allocation around it (a `switch` in a stage body splits the allocation at every stage and spills)
+__device__ __forceinline__ void wait_dma_late_and_barrier(int late) {
+    asm volatile(
+        "s_cmp_lt_u32 %0, 1\n\t"
+        "s_cbranch_scc1 .Lmpg_w0_%=\n\t"
+        "s_cmp_lt_u32 %0, 2\n\t"
+        "s_cbranch_scc1 .Lmpg_w1_%=\n\t"
+        "s_cmp_lt_u32 %0, 3\n\t"
+        "s_cbranch_scc1 .Lmpg_w2_%=\n\t"
+        "s_cmp_lt_u32 %0, 4\n\t"
+        "s_cbranch_scc1 .Lmpg_w3_%=\n\t"
+        "s_waitcnt vmcnt(4)\n\t"
+        "s_branch .Lmpg_wb_%=\n"
+        ".Lmpg_w3_%=:\n\t"
+        "s_waitcnt vmcnt(3)\n\t"
+        "s_branch .Lmpg_wb_%=\n"
+        ".Lmpg_w2_%=:\n\t"
+        "s_waitcnt vmcnt(2)\n\t"
+        "s_branch .Lmpg_wb_%=\n"
+        ".Lmpg_w1_%=:\n\t"
+        "s_waitcnt vmcnt(1)\n\t"
+        "s_branch .Lmpg_wb_%=\n"
+        ".Lmpg_w0_%=:\n\t"
+        "s_waitcnt vmcnt(0)\n"
+        ".Lmpg_wb_%=:\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "s_barrier" ::"s"(late)
+        : "memory", "scc");
 }
 
 __device__ __forceinline__ void dma16(const char* src, char* lds_wave_base) {

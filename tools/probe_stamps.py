@@ -1,6 +1,8 @@
 """diagnostic: per-phase cycle sums of the F16F6 K loop (library built with -DMPG_STAMPS=1, MPGAN_LIB_OVERRIDE), b1.B and
-b2.A, one launch each: per wave and stage, s_memtime cycles from the barrier release to the first satisfied fragment wait,
-through the fp16 groups, through the correction steps, and waiting at the next barrier.  argv[1]: waves per block of the
+b2.A, one launch each: per wave and barrier interval, s_memtime cycles from the barrier release to the first satisfied
+fragment wait, in the fp16 groups, in the correction steps, and waiting at the next barrier.  (With the barrier in
+mid-stage -- the 5x5 layers -- an interval is head, corrections of stage st, fp16 groups of stage st + 1, wait; with the
+barrier at the stage boundary -- the 3x3 case -- head, fp16 groups, corrections, wait.)  argv[1]: waves per block of the
 one-cout-tile kernel of the library under test (8; 4 before round 5)"""
 import os
 import sys
