@@ -5,22 +5,28 @@
 // is, per filter tap, a GEMM whose contraction runs over PIXELS.  v_mfma_f32_32x32x16_f16 wants the
 // 8 contraction elements of a lane in one register quad, while the tensors of the convolution kernels (G8:
 // [N][C/8][2 planes hi,lo][H][W][8 fp16], scaled by a power of two taken from the tensor's absolute maximum where it
-// is a gradient) keep 8 CHANNELS of a pixel together.  The kernel reads G8 as it is: the pixel rows of a channel
+// is a gradient) keep 8 CHANNELS of a pixel together.  The kernels read G8 as it is: the pixel rows of a channel
 // group are copied to LDS unchanged and the fragments come out of ds_read_b64_tr_b16, the transposing LDS read of
-// gfx950 (a first version rewrote both operands channel-major in memory first, "P16": two more passes over x and dy
-// and 2.3 of the 3.4 GB a call moved at 128x128 channels).  So the layer's forward input and the scaled dy of the
-// data-gradient convolution are shared with this kernel, without a conversion of their own.
-//   * a block (8 waves, two per SIMD, each with at most 6 accumulator tiles; rounds 1-2 ran 4 waves with up to 16) owns one
-//     filter row ky,
-//     up to 128 input x 128 output channels, and a range of output rows; it walks the rows in chunks
-//     of 32*KS pixels, staging the x piece (with an 8-pixel halo on both sides) and the dy piece in
-//     LDS by LDS-DMA, double buffered;
-//   * a wave owns a 32-channel ci tile, COTW co tiles and all KW taps of the row: KW*COTW accumulator
-//     tiles (at most 6: 256 registers per wave).  Per 16-pixel k-step it reads one 24-pixel window of x per plane (6 transposed
-//     reads of 4 pixels) and derives the KW shifted A fragments in registers (v_alignbit for odd shifts), so x is read
-//     from LDS once for all taps; a dy fragment is two transposed reads;
-//   * precision 3 adds the hi*lo and lo*hi products (fp32-grade, like MPG_PREC_F16X3); precision 1
-//     keeps hi*hi only;
+// gfx950 (rewriting both operands channel-major in memory first took two more passes over x and dy: 2.3 of the 3.4 GB a
+// call moved at 128x128 channels).  So the layer's forward input and the scaled dy of the data-gradient convolution are
+// shared with these kernels, without a conversion of their own.
+//
+// Two kernels, both with blocks of 8 waves (two per SIMD, so 256 registers per wave), chosen by wgrad_plan:
+//   * wgrad_ring_kernel (square 3x3, 4x4, 5x5 filters): a block owns a 32-channel ci tile x a cout window x ALL KH x KW
+//     taps over a column chunk of 64 pixels and sweeps a range of output rows.  The KH x rows of an output row stay in
+//     an LDS ring of KH + 1 row slots, so one new x row and one dy row are copied per output row.  The accumulator tiles
+//     are dealt to the waves in (ky, kx, cout tile) order, 7 at most per wave.
+//   * wgrad_mfma_kernel (every other filter: 1x1, 1x3, 2x4, 7x5, ...): a block owns ONE filter row ky, up to 128 input x
+//     128 output channels and a range of output rows.  It walks the rows in chunks of 32 or 64 pixels, double buffered
+//     in LDS; a wave owns a 32-channel ci tile, COTW cout tiles and the KW taps of the row (at most 6 accumulator
+//     tiles), left-over waves split the k-steps of a chunk.
+// What they share:
+//   * the x piece (with an 8-pixel halo on both sides) and the dy piece reach LDS by LDS-DMA, whole at the head of the
+//     step that precedes their use;
+//   * per 16-pixel k-step a wave reads one 24-pixel window of x per plane and filter row (6 transposed reads of 4 pixels)
+//     and derives the KW shifted A fragments in registers (v_alignbit for odd shifts), so x is read from LDS once for
+//     all taps of a row; a dy fragment is two transposed reads;
+//   * precision 3 adds the hi*lo and lo*hi products (fp32-grade, MPG_PREC_F16X3); precision 1 keeps hi*hi only;
 //   * partial sums of the pixel ranges are combined with fp32 atomics into dW.
 #include "mpgan_internal.h"
 #include "mpgan_mfma_dev.h"
@@ -60,31 +66,8 @@ __global__ void amax_init_kernel(float* __restrict__ amax, const float* __restri
     if (i < 64) amax[i] = i == 0 ? (x_amax ? *x_amax : 0.f) : (i == 1 ? (dy_amax ? *dy_amax : 0.f) : 0.f);
 }
 
-#ifndef MPG_WG_DIAG
-#define MPG_WG_DIAG 0
-#endif
-#define WG_MFMA(a_, b_, c_, x_, y_, z_) ((MPG_WG_EXP & 2) ? (c_) : __builtin_amdgcn_mfma_f32_32x32x16_f16(a_, b_, c_, x_, y_, z_))
-#ifndef MPG_WG_EXP         // timing experiments (results are garbage): 1 no LDS waits, 2 no MFMAs, 4 no copy of the next chunk
-#define MPG_WG_EXP 0
-#endif
-// MPG_WG_SPREAD 1 (development A/B, off): one LDS-DMA instruction of the next chunk's copy in front of each product of the
-// k-steps instead of the whole copy at the head of the chunk.  Measured on the 5x5 128->128 layer, 16 tiles of 256^2
-// (profiles/r03/wgrad_variants.md): 3.62 ms against 2.98 ms.  A wave waits for the CU's address unit at every LDS-DMA
-// instruction (~35 cycles each when the unit is free, 64 instructions per chunk and CU), and spread out, the waits of the
-// two waves of a SIMD fall into the MFMA phase of both; at the head of the chunk they cost 2100 cycles once, with idle
-// matrix pipes, and the k-steps then run undisturbed (4500 cycles for 3840 of MFMA work).
-#ifndef MPG_WG_SPREAD
-#define MPG_WG_SPREAD 0
-#endif
-#ifndef MPG_WG_RING        // 0: square 3x3 / 4x4 / 5x5 filters on the one-filter-row kernel too (development A/B)
-#define MPG_WG_RING 1
-#endif
-#if MPG_WG_DIAG
-__device__ unsigned long long g_wg_diag[8];
-#define WG_T() __builtin_readcyclecounter()
-#endif
-
-struct WgArgs {
+// what both kernels take from the call
+struct WgTensors {
     const char* xg;          // G8 of x  [N][x_cg][2][H][W][8]
     const char* dg;          // G8 of dy [N][d_cg][2][H][W][8]
     const float* x_amax;     // max |x| / max |dy| the G8 tensors were scaled with (null: unscaled)
@@ -93,14 +76,19 @@ struct WgArgs {
     float* dw;               // [kh][kw][cin_total][cout_total]
     int n, h, w;
     int x_cg, d_cg;          // channel groups of the two tensors
-    int cin_total, cout_total, ci0, co0, cin, cout;   // channel window of this launch (cin, cout <= 128)
-    int windows;                                       // equal cout windows handled by this launch (>= 1)
-    int kh, pt, pl;
+    int cin_total, cout_total;
+    float wscale;
+};
+
+struct WgArgs {
+    WgTensors t;
+    int ci0, co0, cin, cout; // channel window of this launch (cin, cout <= 128)
+    int windows;             // equal cout windows handled by this launch (>= 1)
+    int kh, pt;
     int cit, cog, ks;        // waves = cit * cog * ks = WG_WAVES
     int chunk;               // pixels per chunk = 32 * ks
     int xp, dp;              // pixels (16-byte units) per LDS row of a channel group, pad included
     int nsplit, rows_per_split;
-    float wscale;
 };
 
 constexpr int WG_WAVES = 8, WG_THREADS = WG_WAVES * 64;
@@ -110,8 +98,10 @@ constexpr size_t WG_LDS_MAX = 160 * 1024;   // LDS of a CU: both kernels have th
 constexpr int X_UNITS_DMA = 6;
 constexpr int D_UNITS_DMA = 5;
 constexpr int LDS_ROW_PAD = 4;       // units: a row of 16 k + 4 units starts 16 banks after its neighbour (see the reads)
+// units (pixels of 16 bytes) per LDS row of a channel group for a chunk of `px` pixels: x with its halo, dy
+constexpr int x_row_units(int px) { return px + 16 + LDS_ROW_PAD; }
+constexpr int d_row_units(int px) { return px + LDS_ROW_PAD; }
 
-typedef __fp16 h4raw __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // 4 rows (pixels) x 16 columns (channels: two G8 groups) per 16 lanes, delivered column-major: lane i of the 16 gets channel i
@@ -119,18 +109,12 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // The reads and their waits are volatile asm, in program order, with the waits counted by hand: to the compiler an LDS read
 // behind an LDS-DMA instruction may alias the DMA's target, and it puts `s_waitcnt vmcnt(0)` in front of the read -- the
 // builtin form of this read made every k-step wait for the copy of the NEXT chunk to land (the copy goes to the other
-// buffer; the barrier at the end of the chunk is what orders it against its readers).
+// buffer; the barrier at the end of the chunk is what orders it against its readers; profiles/r03/wgrad_variants.md).
 template <int OFF>
 __device__ __forceinline__ void lds_read_tr(u32x2& dst, unsigned addr) {
     static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds_read_b64_tr_b16 offset");
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
-// lgkm_wait<N>, unless the timing experiment MPG_WG_EXP & 1 drops the LDS waits
-template <int N>
-__device__ __forceinline__ void wg_wait() {
-    if constexpr (!(MPG_WG_EXP & 1)) lgkm_wait<N>();
-}
-
 __device__ __forceinline__ void tr_read_at(u32x2& dst, unsigned addr, int m) {      // m is a constant after unrolling
     switch (m) {
         case 0: lds_read_tr<0>(dst, addr); break;
@@ -139,6 +123,56 @@ __device__ __forceinline__ void tr_read_at(u32x2& dst, unsigned addr, int m) {  
         case 3: lds_read_tr<192>(dst, addr); break;
         case 4: lds_read_tr<256>(dst, addr); break;
         default: lds_read_tr<320>(dst, addr); break;
+    }
+}
+// Lane part of a transposed-read address in an image with `upr` units per row whose tile starts at channel group
+// `g0`: the 16 lanes (lane & 48) own 16 channels = two groups; lane 4q+p of them addresses pixel q, channels 4p .. 4p+3
+// of the block and receives 4 pixels of channel (lane & 15); the upper 32 lanes read 8 pixels on.  Rows of 16 k + 4
+// units put the four groups a 32-lane half reads 16 banks apart, the pixels 4 banks: no conflicts.
+__device__ __forceinline__ int tr_lane_off(int lane, int upr, int g0 = 0) {
+    const int hh = lane >> 5, sub = (lane >> 4) & 1, tq = (lane & 15) >> 2, tp = lane & 3;
+    return ((g0 + sub * 2 + (tp >> 1)) * upr + 8 * hh + tq) * 16 + (tp & 1) * 8;
+}
+// the B fragment (8 pixels of a 32-channel cout tile) out of its two transposed reads
+__device__ __forceinline__ half8 frag_of(const u32x2 (&b)[2]) {
+    u32x4 f;
+    f[0] = b[0][0]; f[1] = b[0][1]; f[2] = b[1][0]; f[3] = b[1][1];
+    return __builtin_bit_cast(half8, f);
+}
+// the A fragment of the tap S = kx - pl pixels off the centre (|S| <= 3): pixels [8 + S, 16 + S) of a 24-pixel window;
+// register q of the window is w[q / 2][q % 2]; odd shifts through v_alignbit
+template <int S>
+__device__ __forceinline__ half8 shifted(const u32x2 (&w)[6]) {
+    u32x4 f;
+    if constexpr ((S & 1) == 0) {
+        constexpr int q = (8 + S) / 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = w[(q + i) / 2][(q + i) % 2];
+    } else {
+        constexpr int q = (7 + S) / 2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            f[i] = __builtin_amdgcn_alignbit(w[(q + i + 1) / 2][(q + i + 1) % 2], w[(q + i) / 2][(q + i) % 2], 16);
+    }
+    return __builtin_bit_cast(half8, f);
+}
+// wscale over the scales the two G8 tensors carry
+__device__ __forceinline__ float wg_unscale(const WgTensors& t) {
+    return t.wscale / ((t.x_amax ? pow2_scale(*t.x_amax) : 1.f) * (t.d_amax ? pow2_scale(*t.d_amax) : 1.f));
+}
+// Epilogue of one accumulator tile: filter tap `tap`, ci tile `cit` of the window [ci0, ci0 + cin), cout tile `cot` of
+// the window [co0, co0 + cout).  D row (v&3) + 8*(v>>2) + 4*(lane>>5) is the input channel, column lane&31 the output
+// channel; zeros (channels a tile has beyond the tensor, empty ranges) are not sent to memory.
+__device__ __forceinline__ void add_tile(const WgTensors& t, const f32x16& acc, float unscale, int tap, int ci0, int cin, int cit,
+                                         int co0, int cout, int cot, int lane) {
+    const int co = cot * 32 + (lane & 31);
+    if (co >= cout) return;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int ci = cit * 32 + (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5);
+        const float val = acc[v];
+        if (ci < cin && val != 0.f)
+            atomicAdd(t.dw + ((size_t)tap * t.cin_total + ci0 + ci) * t.cout_total + co0 + co, val * unscale);
     }
 }
 
@@ -151,10 +185,9 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
     const int nwin = a.windows;
     const int co_base = a.co0 + ((blockIdx.x / 8) % nwin) * a.cout;
     const int tid = threadIdx.x, lane = tid & 63;
-    // the wave number as a scalar: everything derived from it (tile ownership, loop bounds, the placement of the copy
+    // the wave number as a scalar: everything derived from it (tile ownership, loop bounds, the targets of the copy
     // instructions) then stays on the scalar unit; taken from threadIdx it is a vector value to the compiler
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hh = lane >> 5;
     // XCD-aware order: the kh blocks of one row range land on the same XCD (shared L2)
     const int xcd = blockIdx.x % 8, jj = blockIdx.x / (8 * nwin);
     const int ky = jj % a.kh;
@@ -169,7 +202,8 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
     const int gx = xch / 8, gd = dch / 8;                        // channel groups of the two LDS images
     const int xbytes = gx * nplane * a.xp * 16, dbytes = gd * nplane * a.dp * 16;
     // the two buffers, x image then dy image each (address arithmetic, not a pointer table: indexed by the buffer number at
-    // run time such a table lives in scratch memory)
+    // run time such a table lives in scratch memory, and a scratch load in front of every LDS-DMA instruction made the
+    // launch 4.47 ms for 2.98, profiles/r03/wgrad_variants.md)
     auto xs = [&](int buf) { return lds + buf * (xbytes + dbytes); };
     auto dsm = [&](int buf) { return lds + buf * (xbytes + dbytes) + xbytes; };
 
@@ -181,10 +215,10 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
     const int xpx = a.chunk + 16, dpx = a.chunk;                      // ... that are pixels
     const int xunits = gx * nplane * xupr, dunits = gd * nplane * dupr;
     constexpr int XU = X_UNITS_DMA, DU = D_UNITS_DMA;                  // DMA instructions per wave and chunk
-    const int total_rows = a.n * a.h;
+    const int total_rows = a.t.n * a.t.h;
     const int row_begin = split * a.rows_per_split;
     const int row_end = min(total_rows, row_begin + a.rows_per_split);
-    const int chunks_per_row = (a.w + a.chunk - 1) / a.chunk;
+    const int chunks_per_row = (a.t.w + a.chunk - 1) / a.chunk;
     const int nwork = (row_end - row_begin) * chunks_per_row;
 
     f32x16 acc[KW][COTW];
@@ -196,12 +230,12 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
             for (int v = 0; v < 16; ++v) acc[k][t][v] = 0.f;
 
     // copy plan of this thread, formed once: per unit its offset (in 16-byte units) from the chunk's first pixel in plane
-    // 0 of group 0 of its image, and its pixel offset inside the chunk.  (A first version staged the chunk through registers: 10 global loads + 10 ds_write_b128 per thread
-    // and chunk took 2100 + 1700 cycles next to 3840 cycles of MFMA work, with nothing to hide them behind at one wave
-    // per SIMD -- measured with MPG_WG_DIAG; the wide LDS stores alone run at a third of the read rate.)
+    // 0 of group 0 of its image, and its pixel offset inside the chunk.  LDS-DMA and not registers: staged through
+    // registers, the 10 global loads + 10 ds_write_b128 per thread and chunk took 2100 + 1700 cycles next to 3840 cycles
+    // of MFMA work (profiles/r02/kloop_analysis.md, section 5; the wide LDS stores alone run at a third of the read rate).
     constexpr int NOPX = 1 << 28;                 // pixel offset of a unit that delivers zeros whatever the chunk
     constexpr int SKIP = -(1 << 28);              // ... of a unit that is not copied at all (pad unit, beyond the image)
-    const int plane_px = a.h * a.w;
+    const int plane_px = a.t.h * a.t.w;
     int xg[XU], xpo[XU], dg[DU], dpo[DU];
 #pragma unroll
     for (int i = 0; i < XU; ++i) {
@@ -209,7 +243,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
         const int rr = u / xupr, off = u % xupr;
         const int pln = rr / gx, g = a.ci0 / 8 + rr % gx;
         xg[i] = (g * 2 + pln) * plane_px + off - 8;
-        xpo[i] = (u >= xunits || off >= xpx) ? SKIP : (g < a.x_cg ? off - 8 : NOPX);
+        xpo[i] = (u >= xunits || off >= xpx) ? SKIP : (g < a.t.x_cg ? off - 8 : NOPX);
     }
 #pragma unroll
     for (int i = 0; i < DU; ++i) {
@@ -217,17 +251,13 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
         const int rr = u / dupr, off = u % dupr;
         const int pln = rr / gd, g = co_base / 8 + rr % gd;
         dg[i] = (g * 2 + pln) * plane_px + off;
-        dpo[i] = (u >= dunits || off >= dpx) ? SKIP : (g < a.d_cg ? off : NOPX);
+        dpo[i] = (u >= dunits || off >= dpx) ? SKIP : (g < a.t.d_cg ? off : NOPX);
     }
-    const int wave_u = wave;
-    // (the copy of a chunk is written in NPART parts so that variants can place them; the CU's address unit takes ~40 cycles
-    // per LDS-DMA instruction of this shape: 3000 cycles for the 68 instructions of a chunk, measured)
-    constexpr int NPART = XU + DU;             // one LDS-DMA instruction per part: x pieces first, then the dy pieces
     // position of the next chunk to copy: image b, output row oy, chunk ci of the row; stepped from chunk to chunk (the
     // divisions of a position formed from the chunk number were 800 cycles per chunk and wave: hipcc does them on the
     // vector unit).  Plain scalars, not a struct handed around by reference: that one ended up in scratch memory, and
     // every copy instruction then waited for a scratch load -- and with it for all the copies in flight.
-    int nb = row_begin / a.h, noy = row_begin % a.h, nci = 0;
+    int nb = row_begin / a.t.h, noy = row_begin % a.t.h, nci = 0;
     // source of the chunk at (nb, noy, nci): rows of x and dy, first pixel, and whether the x row exists
     const char* c_xrow = nullptr;
     const char* c_drow = nullptr;
@@ -236,77 +266,46 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
     auto take_chunk = [&]() {
         const int iy = noy + ky - a.pt;
         c_x0 = nci * a.chunk;
-        c_ok = iy >= 0 && iy < a.h;
-        c_xrow = a.xg + (((size_t)nb * a.x_cg * 2) * plane_px + (size_t)iy * a.w + c_x0) * 16;
-        c_drow = a.dg + (((size_t)nb * a.d_cg * 2) * plane_px + (size_t)noy * a.w + c_x0) * 16;
+        c_ok = iy >= 0 && iy < a.t.h;
+        c_xrow = a.t.xg + (((size_t)nb * a.t.x_cg * 2) * plane_px + (size_t)iy * a.t.w + c_x0) * 16;
+        c_drow = a.t.dg + (((size_t)nb * a.t.d_cg * 2) * plane_px + (size_t)noy * a.t.w + c_x0) * 16;
         if (++nci == chunks_per_row) {
             nci = 0;
-            if (++noy == a.h) { noy = 0; ++nb; }
+            if (++noy == a.t.h) { noy = 0; ++nb; }
         }
     };
-    auto dma_part = [&](int buf, auto part_c) {
-        constexpr int P = decltype(part_c)::value;
-        const int x0 = c_x0;
-        const bool row_ok = c_ok;
-        const char* xrow = c_xrow;
-        const char* drow = c_drow;
-        if constexpr (P < XU) {
-            constexpr int i = P;
+    // the copy of the chunk taken last, whole: every wave issues its XU + DU instructions one behind the other.  The CU's
+    // address unit takes ~35 cycles per LDS-DMA instruction of this shape and the wave waits for it at each one; issued
+    // at the head of the chunk that is ~2100 cycles once, with idle matrix pipes, and the k-steps then run undisturbed
+    // (4500 cycles for 3840 of MFMA work).  One instruction in front of each product of the k-steps instead puts the
+    // waits of the two waves of a SIMD into the MFMA phase of both: 3.62 ms against 2.98 ms on the 5x5 128->128 layer,
+    // 16 tiles of 256^2 (profiles/r03/wgrad_variants.md).
+    auto copy_chunk = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < XU; ++i)
             if (xpo[i] != SKIP) {
-                const int px = x0 + xpo[i];
-                const char* src = (row_ok && px >= 0 && px < a.w) ? xrow + (ptrdiff_t)xg[i] * 16 : a.zeros;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(xs(buf) + (i * WG_WAVES + wave_u) * 1024),
-                                                 16, 0, 0);
+                const int px = c_x0 + xpo[i];
+                dma16((c_ok && px >= 0 && px < a.t.w) ? c_xrow + (ptrdiff_t)xg[i] * 16 : a.t.zeros,
+                      xs(buf) + (i * WG_WAVES + wave) * 1024);
             }
-        }
-        if constexpr (P >= XU) {
-            constexpr int i = P - XU;
-            if (dpo[i] != SKIP) {
-                const char* src = (row_ok && x0 + dpo[i] < a.w) ? drow + (ptrdiff_t)dg[i] * 16 : a.zeros;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(dsm(buf) + (i * WG_WAVES + wave_u) * 1024),
-                                                 16, 0, 0);
-            }
-        }
+#pragma unroll
+        for (int i = 0; i < DU; ++i)
+            if (dpo[i] != SKIP)
+                dma16((c_ok && c_x0 + dpo[i] < a.t.w) ? c_drow + (ptrdiff_t)dg[i] * 16 : a.t.zeros,
+                      dsm(buf) + (i * WG_WAVES + wave) * 1024);
     };
-
-    auto dma_parts = [&](int buf, int first, int end) {      // parts first .. end-1 (wave-uniform bounds)
-        static_for<0, NPART>([&](auto pc) {
-            constexpr int P = decltype(pc)::value;
-            if (first <= P && P < end) dma_part(buf, pc);
-        });
-    };
-    if (nwork > 0) { take_chunk(); dma_parts(0, 0, NPART); }
+    if (nwork > 0) { take_chunk(); copy_chunk(0); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const int ksteps = a.chunk / 16;
-#if MPG_WG_DIAG
-    unsigned long long d_fetch = 0, d_comp = 0, d_stash = 0, d_bar = 0, d_wait = 0;
-    const unsigned long long t_begin = WG_T();
-#endif
     for (int wi = 0; wi < nwork; ++wi) {
         const int buf = wi & 1;
-#if MPG_WG_DIAG
-        const unsigned long long t0 = WG_T();
-#endif
-        // the whole copy of the next chunk first (see MPG_WG_SPREAD), then the k-steps
-        const bool has_next = wi + 1 < nwork && !(MPG_WG_EXP & 4);
-        if (has_next) take_chunk();
+        // the whole copy of the next chunk first (every wave its share, also one without k-steps), then the k-steps
+        const bool has_next = wi + 1 < nwork;
+        if (has_next) { take_chunk(); copy_chunk(buf ^ 1); }
         const int my_steps = ks < a.ks ? (ksteps - ks + a.ks - 1) / a.ks : 0;
-        int next_part = 0;
-#if !MPG_WG_SPREAD
-        if (has_next) { dma_parts(buf ^ 1, 0, NPART); next_part = NPART; }
-#endif
-#if MPG_WG_DIAG
-        const unsigned long long t1 = WG_T();
-#endif
-        // transposed reads: the 16 lanes (lane & 48) own 16 channels = two groups; lane 4q+p of them addresses pixel q,
-        // channels 4p .. 4p+3 of the block and receives 4 pixels of channel (lane & 15).  Rows of 16 k + 4 units put the
-        // four groups a 32-lane half reads 16 banks apart, the pixels 4 banks: no conflicts.
-        const int sub = (lane >> 4) & 1, tq = (lane & 15) >> 2, tp = lane & 3;
-        const char* xb = xs(buf) + ((cit * 4 + sub * 2 + (tp >> 1)) * a.xp + 8 * hh + tq) * 16 + (tp & 1) * 8;
-        const char* db = dsm(buf) + ((cog * COTW * 4 + sub * 2 + (tp >> 1)) * a.dp + 8 * hh + tq) * 16 + (tp & 1) * 8;
+        const char* xb = xs(buf) + tr_lane_off(lane, a.xp, cit * 4);
+        const char* db = dsm(buf) + tr_lane_off(lane, a.dp, cog * COTW * 4);
         const int xplane = gx * a.xp * 16, dplane = gd * a.dp * 16, dtile = 4 * a.dp * 16;
         // Per 16-pixel k-step: a 24-pixel window of x per plane -- pixels [16j + 8h - 8, 16j + 8h + 16) relative to the chunk
         // start -- as 6 transposed reads of 4 pixels, and a dy fragment (8 pixels) per cout tile and plane as two.  The reads
@@ -338,79 +337,52 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
 #pragma unroll
             for (int m = 0; m < 6; ++m) tr_read_at(w[m], xa, m);
         };
-        // the KW shifted A fragments of a window: pixels [8 + s, 16 + s), s = kx - pl (|s| <= 3); register q of the window is
-        // w[q / 2][q % 2]; odd shifts through v_alignbit
-        auto shifted = [&](const u32x2 (&w)[6], half8 (&afr)[KW]) {
-#pragma unroll
-            for (int kx = 0; kx < KW; ++kx) {
-                const int s = kx - (KW - 1) / 2;
-                u32x4 f;
-                if ((s & 1) == 0) {
-                    const int q = (8 + s) / 2;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) f[i] = w[(q + i) / 2][(q + i) % 2];
-                } else {
-                    const int q = (7 + s) / 2;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        f[i] = __builtin_amdgcn_alignbit(w[(q + i + 1) / 2][(q + i + 1) % 2], w[(q + i) / 2][(q + i) % 2], 16);
-                }
-                afr[kx] = __builtin_bit_cast(half8, f);
-            }
-        };
-        auto frag_of = [](const u32x2 (&b)[2]) {
-            u32x4 f;
-            f[0] = b[0][0]; f[1] = b[0][1]; f[2] = b[1][0]; f[3] = b[1][1];
-            return __builtin_bit_cast(half8, f);
+        // the KW shifted A fragments of a window
+        auto taps_of = [](const u32x2 (&w)[6], half8 (&afr)[KW]) {
+            static_for<0, KW>([&](auto kc) {
+                constexpr int kx = decltype(kc)::value;
+                afr[kx] = shifted<kx - (KW - 1) / 2>(w);
+            });
         };
         // one k-step: its hi fragments in (wc, bc), the look-ahead hi reads go to (wn, bn) -- the two sets alternate, so that no
         // register is copied while its read is still in flight (nothing but the counted waits orders these reads)
         auto kstep = [&](u32x2 (&wc)[6], u32x2 (&bc)[COTW][2], u32x2 (&wn)[6], u32x2 (&bn)[COTW][2], int j) {
-            auto dma_slot = [&]() {       // the next chunk's copy: one LDS-DMA instruction in front of each product
-                if (has_next && next_part < NPART) {
-                    dma_parts(buf ^ 1, next_part, next_part + 1);
-                    ++next_part;
-                }
-            };
-            dma_slot();
             const int jn = j + a.ks < ksteps ? j + a.ks : j;
             half8 ah[KW], bh[COTW];
-            wg_wait<(PREC == 3 ? NB + 6 : 0)>();
+            lgkm_wait<(PREC == 3 ? NB + 6 : 0)>();
 #pragma unroll
             for (int m = 0; m < 6; ++m) tie(wc[m]);
 #pragma unroll
             for (int t = 0; t < COTW; ++t) { tie(bc[t][0]); tie(bc[t][1]); bh[t] = frag_of(bc[t]); }
-            shifted(wc, ah);
+            taps_of(wc, ah);
             // the products in product-major order: consecutive MFMAs go to different accumulators
 #pragma unroll
             for (int kx = 0; kx < KW; ++kx)
 #pragma unroll
                 for (int t = 0; t < COTW; ++t)
-                    acc[kx][t] = WG_MFMA(ah[kx], bh[t], acc[kx][t], 0, 0, 0);
+                    acc[kx][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kx], bh[t], acc[kx][t], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);      // the products stay in front of the reads and waits behind them
             if (PREC == 3) {
                 half8 bl[COTW], al[KW];
-                dma_slot();
-                wg_wait<6>();
+                lgkm_wait<6>();
 #pragma unroll
                 for (int t = 0; t < COTW; ++t) { tie(b1[t][0]); tie(b1[t][1]); bl[t] = frag_of(b1[t]); }
 #pragma unroll
                 for (int kx = 0; kx < KW; ++kx)
 #pragma unroll
                     for (int t = 0; t < COTW; ++t)
-                        acc[kx][t] = WG_MFMA(ah[kx], bl[t], acc[kx][t], 0, 0, 0);
+                        acc[kx][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kx], bl[t], acc[kx][t], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 read_hi(wn, bn, jn);
-                dma_slot();
-                wg_wait<6 + NB>();
+                lgkm_wait<6 + NB>();
 #pragma unroll
                 for (int m = 0; m < 6; ++m) tie(w1[m]);
-                shifted(w1, al);
+                taps_of(w1, al);
 #pragma unroll
                 for (int kx = 0; kx < KW; ++kx)
 #pragma unroll
                     for (int t = 0; t < COTW; ++t)
-                        acc[kx][t] = WG_MFMA(al[kx], bh[t], acc[kx][t], 0, 0, 0);
+                        acc[kx][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[kx], bh[t], acc[kx][t], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 read_lo(w1, b1, jn);
             } else {
@@ -426,53 +398,17 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
             kstep(w0, b0, w0b, b0b, j);
             if (t + 1 < my_steps) kstep(w0b, b0b, w0, b0, j + a.ks);
         }
-        if (my_steps > 0) wg_wait<0>();      // the look-ahead reads of the last k-step
-        if (has_next) dma_parts(buf ^ 1, next_part, NPART);     // waves without k-steps, or whatever is left
-#if MPG_WG_DIAG
-        const unsigned long long t2a = WG_T();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t2 = WG_T();
-        d_wait += t2 - t2a;
-#endif
+        if (my_steps > 0) lgkm_wait<0>();      // the look-ahead reads of the last k-step
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next chunk has landed in the other buffer
-#if MPG_WG_DIAG
-        const unsigned long long t3 = WG_T();
-#endif
         __syncthreads();
-#if MPG_WG_DIAG
-        const unsigned long long t4 = WG_T();
-        d_fetch += t1 - t0; d_comp += t2a - t1; d_stash += t3 - t2; d_bar += t4 - t3;
-#endif
     }
-#if MPG_WG_DIAG
-    const unsigned long long t_loop = WG_T();
-#endif
 
-    // epilogue: D row = (v&3) + 8*(v>>2) + 4*(lane>>5) is the input channel, column lane&31 the output channel
-    const float unscale = a.wscale / ((a.x_amax ? pow2_scale(*a.x_amax) : 1.f) * (a.d_amax ? pow2_scale(*a.d_amax) : 1.f));
+    const float unscale = wg_unscale(a.t);
 #pragma unroll
     for (int kx = 0; kx < KW; ++kx)
 #pragma unroll
-        for (int t = 0; t < COTW; ++t) {
-            const int co = (cog * COTW + t) * 32 + r;
-            if (co >= a.cout) continue;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int ci = cit * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
-                const float val = acc[kx][t][v];
-                if (ci < a.cin && val != 0.f)
-                    atomicAdd(a.dw + ((size_t)(ky * KW + kx) * a.cin_total + a.ci0 + ci) * a.cout_total + co_base + co,
-                              val * unscale);
-            }
-        }
-#if MPG_WG_DIAG
-    if (lane == 0 && blockIdx.x % 64 == 0) {
-        const unsigned long long t_end = WG_T();
-        atomicAdd(&g_wg_diag[0], d_fetch); atomicAdd(&g_wg_diag[1], d_comp); atomicAdd(&g_wg_diag[2], d_stash);
-        atomicAdd(&g_wg_diag[3], d_bar); atomicAdd(&g_wg_diag[4], t_loop - t_begin); atomicAdd(&g_wg_diag[5], d_wait);
-        atomicAdd(&g_wg_diag[6], 1ull); atomicAdd(&g_wg_diag[7], (unsigned long long)nwork);
-    }
-#endif
+        for (int t = 0; t < COTW; ++t)
+            add_tile(a.t, acc[kx][t], unscale, ky * KW + kx, a.ci0, a.cin, cit, co_base, a.cout, cog * COTW + t, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -488,26 +424,19 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
 // of the one or two filter rows its tiles touch.  Which tiles a wave owns is a compile-time property of its number: the
 // k-step body exists once per wave (`switch` on the scalar wave number), registers are statically indexed.
 struct WrArgs {
-    const char* xg;
-    const char* dg;
-    const float* x_amax;
-    const float* d_amax;
-    const char* zeros;
-    float* dw;
-    int n, h, w;
-    int x_cg, d_cg;
-    int cin_total, cout_total;
+    WgTensors t;
     int pt;
     int chunks;              // column chunks of WR_PX pixels per row
     int ranges, rows_per_range;
     int n_ci, n_cow;         // ci tiles of 32, cout windows of 32 * COTW
     int n_outer;             // n * ranges * chunks
-    float wscale;
 };
 
 constexpr int WR_PX = 64;                      // pixels of a column chunk
-constexpr int WR_XP = WR_PX + 16 + LDS_ROW_PAD, WR_DP = WR_PX + LDS_ROW_PAD;      // units per LDS row of a group
+constexpr int WR_XP = x_row_units(WR_PX), WR_DP = d_row_units(WR_PX);             // units per LDS row of a group
 constexpr int WR_XSLOT = 2 * 4 * WR_XP * 16;   // an x row: 2 planes x 4 groups
+constexpr int wr_dbuf_bytes(int cotw) { return 2 * cotw * 4 * WR_DP * 16; }          // a dy row: 2 planes x the window's groups
+constexpr int wr_lds_bytes(int kh, int cotw) { return (kh + 1) * WR_XSLOT + 2 * wr_dbuf_bytes(cotw); }   // ring + 2 dy buffers
 constexpr int wr_pairs(int kh, int kw, int cotw) { return kh * kw * cotw; }
 constexpr int wr_first(int wave, int np) { return wave * np / WG_WAVES; }        // first (ky, kx, cot) pair of a wave
 constexpr int wr_max_pairs(int np) { return (np + WG_WAVES - 1) / WG_WAVES; }
@@ -517,12 +446,12 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NP = wr_pairs(KH, KW, COTW), MAXP = wr_max_pairs(NP), RX = KH + 1;
     constexpr int GD = COTW * 4;                                   // channel groups of the dy image
-    constexpr int DBUF = 2 * GD * WR_DP * 16;                      // one dy buffer (both planes laid out; PREC 1 reads plane 0)
+    constexpr int DBUF = wr_dbuf_bytes(COTW);                      // one dy buffer (both planes laid out; PREC 1 reads plane 0)
+    static_assert((size_t)wr_lds_bytes(KH, COTW) <= WG_LDS_MAX, "ring kernel LDS plan");
     constexpr int XUNITS = 2 * 4 * WR_XP, DUNITS = 2 * GD * WR_DP;
     constexpr int XU = (XUNITS + WG_THREADS - 1) / WG_THREADS, DU = (DUNITS + WG_THREADS - 1) / WG_THREADS;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hh = lane >> 5;
     // block -> (image, row range, column chunk) x (ci tile, cout window); the combinations of one outer index run next to
     // each other on one XCD (they share the x rows / the dy rows through its L2)
     const int ncombo = a.n_ci * a.n_cow;
@@ -532,9 +461,9 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
     const int cit = combo % a.n_ci, cow = combo / a.n_ci;
     const int chunk = outer % a.chunks, rng = (outer / a.chunks) % a.ranges, b = outer / (a.chunks * a.ranges);
     const int x0 = chunk * WR_PX;
-    const int row0 = rng * a.rows_per_range, row1 = min(a.h, row0 + a.rows_per_range);
+    const int row0 = rng * a.rows_per_range, row1 = min(a.t.h, row0 + a.rows_per_range);
     if (row0 >= row1) return;
-    const int plane_px = a.h * a.w;
+    const int plane_px = a.t.h * a.t.w;
     char* xs = lds;
     char* dsm = lds + RX * WR_XSLOT;
 
@@ -551,7 +480,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
         const int pln = rr / 4, g = cit * 4 + rr % 4;
         const int px = x0 + off - 8;
         const bool unused = u >= XUNITS || off >= WR_PX + 16 || (PREC != 3 && pln == 1);
-        const bool zero = !unused && (g >= a.x_cg || px < 0 || px >= a.w);
+        const bool zero = !unused && (g >= a.t.x_cg || px < 0 || px >= a.t.w);
         xg[i] = (unused || zero) ? NOCOPY : (g * 2 + pln) * plane_px + off - 8;
         if (zero)
             for (int slot = 0; slot < RX; ++slot)
@@ -563,34 +492,28 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
         const int rr = u / WR_DP, off = u % WR_DP;
         const int pln = rr / GD, g = cow * GD + rr % GD;
         const bool unused = u >= DUNITS || off >= WR_PX || (PREC != 3 && pln == 1);
-        const bool zero = !unused && (g >= a.d_cg || x0 + off >= a.w);
+        const bool zero = !unused && (g >= a.t.d_cg || x0 + off >= a.t.w);
         dg[i] = (unused || zero) ? NOCOPY : (g * 2 + pln) * plane_px + off;
         if (zero)
             for (int bufi = 0; bufi < 2; ++bufi)
                 *reinterpret_cast<u32x4*>(dsm + bufi * DBUF + u * 16) = u32x4{0u, 0u, 0u, 0u};
     }
-    const char* ximg = a.xg + ((size_t)b * a.x_cg * 2) * plane_px * 16;
-    const char* dimg = a.dg + ((size_t)b * a.d_cg * 2) * plane_px * 16;
+    const char* ximg = a.t.xg + ((size_t)b * a.t.x_cg * 2) * plane_px * 16;
+    const char* dimg = a.t.dg + ((size_t)b * a.t.d_cg * 2) * plane_px * 16;
     auto copy_x_row = [&](int iy, int slot) {          // image row iy (zeros outside the image) -> ring slot
-        const bool ok = iy >= 0 && iy < a.h;
-        const char* row = ximg + ((size_t)(ok ? iy : 0) * a.w + x0) * 16;
+        const bool ok = iy >= 0 && iy < a.t.h;
+        const char* row = ximg + ((size_t)(ok ? iy : 0) * a.t.w + x0) * 16;
 #pragma unroll
         for (int i = 0; i < XU; ++i)
-            if (xg[i] != NOCOPY) {
-                const char* src = ok ? row + (ptrdiff_t)xg[i] * 16 : a.zeros;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(xs + slot * WR_XSLOT + (i * WG_WAVES + wave) * 1024),
-                                                 16, 0, 0);
-            }
+            if (xg[i] != NOCOPY)
+                dma16(ok ? row + (ptrdiff_t)xg[i] * 16 : a.t.zeros, xs + slot * WR_XSLOT + (i * WG_WAVES + wave) * 1024);
     };
     auto copy_d_row = [&](int oy, int buf) {
-        const char* row = dimg + ((size_t)oy * a.w + x0) * 16;
+        const char* row = dimg + ((size_t)oy * a.t.w + x0) * 16;
 #pragma unroll
         for (int i = 0; i < DU; ++i)
             if (dg[i] != NOCOPY)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(row + (ptrdiff_t)dg[i] * 16),
-                                                 (__attribute__((address_space(3))) void*)(dsm + buf * DBUF + (i * WG_WAVES + wave) * 1024),
-                                                 16, 0, 0);
+                dma16(row + (ptrdiff_t)dg[i] * 16, dsm + buf * DBUF + (i * WG_WAVES + wave) * 1024);
     };
 
     f32x16 acc[MAXP];
@@ -607,11 +530,8 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    const int ksteps = (min(WR_PX, a.w - x0) + 15) / 16;
-    // lane part of the transposed-read addresses (see wgrad_mfma_kernel): 16 lanes own 16 channels = two groups
-    const int sub = (lane >> 4) & 1, tq = (lane & 15) >> 2, tp = lane & 3;
-    const unsigned xlane = lds_off(xs) + ((sub * 2 + (tp >> 1)) * WR_XP + 8 * hh + tq) * 16 + (tp & 1) * 8;
-    const unsigned dlane = lds_off(dsm) + ((sub * 2 + (tp >> 1)) * WR_DP + 8 * hh + tq) * 16 + (tp & 1) * 8;
+    const int ksteps = (min(WR_PX, a.t.w - x0) + 15) / 16;
+    const unsigned xlane = lds_off(xs) + tr_lane_off(lane, WR_XP), dlane = lds_off(dsm) + tr_lane_off(lane, WR_DP);
     constexpr int XPLANE = 4 * WR_XP * 16, DPLANE = GD * WR_DP * 16, DTILE = 4 * WR_DP * 16;
 
     // the k-steps of one output row for wave W: compile-time list of its (ky, kx, cot) pairs.  LDS reads run ahead of their
@@ -657,34 +577,13 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
                     for (int m = 0; m < 6; ++m) tr_read_at(wl[k][m], xa0[k] + XPLANE + j * 256, m);
             }
         };
-        auto frag_of = [](const u32x2 (&q)[2]) {
-            u32x4 f;
-            f[0] = q[0][0]; f[1] = q[0][1]; f[2] = q[1][0]; f[3] = q[1][1];
-            return __builtin_bit_cast(half8, f);
-        };
-        // pixels [8 + s, 16 + s) of a window, s = kx - pl
-        auto shifted = [&](const u32x2 (&wq)[6], auto kxc) {
-            constexpr int kx = decltype(kxc)::value, s = kx - (KW - 1) / 2;
-            u32x4 f;
-            if constexpr ((s & 1) == 0) {
-                constexpr int q = (8 + s) / 2;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) f[i] = wq[(q + i) / 2][(q + i) % 2];
-            } else {
-                constexpr int q = (7 + s) / 2;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    f[i] = __builtin_amdgcn_alignbit(wq[(q + i + 1) / 2][(q + i + 1) % 2], wq[(q + i) / 2][(q + i) % 2], 16);
-            }
-            return __builtin_bit_cast(half8, f);
-        };
         constexpr int NW = 6 * NKY, NB = 2 * COTW;
         read_wh(0);
         read_rest(0);
         for (int j = 0; j < ksteps; ++j) {
             const int jn = j + 1 < ksteps ? j + 1 : j;
             // in flight, oldest first: wh, bh [, bl, wl]
-            wg_wait<(PREC == 3 ? NB + NW : 0)>();
+            lgkm_wait<(PREC == 3 ? NB + NW : 0)>();
 #pragma unroll
             for (int k = 0; k < NKY; ++k)
 #pragma unroll
@@ -695,27 +594,27 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
             // product-major: consecutive MFMAs go to different accumulators
             static_for<0, CNT>([&](auto sc) {
                 constexpr int p = P0 + decltype(sc)::value, ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
-                acc[decltype(sc)::value] = WG_MFMA(shifted(wh[ky - KY0], std::integral_constant<int, kx>{}), bh[c], acc[decltype(sc)::value], 0, 0, 0);
+                acc[decltype(sc)::value] = __builtin_amdgcn_mfma_f32_32x32x16_f16(shifted<kx - (KW - 1) / 2>(wh[ky - KY0]), bh[c], acc[decltype(sc)::value], 0, 0, 0);
             });
             __builtin_amdgcn_sched_barrier(0);
             if (PREC == 3) {
-                wg_wait<NW>();
+                lgkm_wait<NW>();
 #pragma unroll
                 for (int c = 0; c < COTW; ++c) { tie(blq[c][0]); tie(blq[c][1]); bl[c] = frag_of(blq[c]); }
                 static_for<0, CNT>([&](auto sc) {
                     constexpr int p = P0 + decltype(sc)::value, ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
-                    acc[decltype(sc)::value] = WG_MFMA(shifted(wh[ky - KY0], std::integral_constant<int, kx>{}), bl[c], acc[decltype(sc)::value], 0, 0, 0);
+                    acc[decltype(sc)::value] = __builtin_amdgcn_mfma_f32_32x32x16_f16(shifted<kx - (KW - 1) / 2>(wh[ky - KY0]), bl[c], acc[decltype(sc)::value], 0, 0, 0);
                 });
                 __builtin_amdgcn_sched_barrier(0);
                 read_wh(jn);                        // behind the last reader of this k-step's hi windows
-                wg_wait<NW>();                    // ... the lo windows are there
+                lgkm_wait<NW>();                    // ... the lo windows are there
 #pragma unroll
                 for (int k = 0; k < NKY; ++k)
 #pragma unroll
                     for (int m = 0; m < 6; ++m) tie(wl[k][m]);
                 static_for<0, CNT>([&](auto sc) {
                     constexpr int p = P0 + decltype(sc)::value, ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
-                    acc[decltype(sc)::value] = WG_MFMA(shifted(wl[ky - KY0], std::integral_constant<int, kx>{}), bh[c], acc[decltype(sc)::value], 0, 0, 0);
+                    acc[decltype(sc)::value] = __builtin_amdgcn_mfma_f32_32x32x16_f16(shifted<kx - (KW - 1) / 2>(wl[ky - KY0]), bh[c], acc[decltype(sc)::value], 0, 0, 0);
                 });
                 __builtin_amdgcn_sched_barrier(0);
                 read_rest(jn);
@@ -724,12 +623,12 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
                 read_rest(jn);
             }
         }
-        wg_wait<0>();                             // the look-ahead reads of the last k-step
+        lgkm_wait<0>();                             // the look-ahead reads of the last k-step
     };
 
     for (int oy = row0; oy < row1; ++oy) {
         const int buf = (oy - row0) & 1;
-        // the x row the NEXT output row adds and its dy row, whole at the head of the step (see MPG_WG_SPREAD above): the
+        // the x row the NEXT output row adds and its dy row, whole at the head of the step (see copy_chunk above): the
         // slot it goes to held filter row 0 of the previous output row
         if (oy + 1 < row1) {
             int slot = base + KH;
@@ -753,37 +652,20 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
         base = base + 1 >= RX ? 0 : base + 1;
     }
 
-    // epilogue: D row = (v&3) + 8*(v>>2) + 4*(lane>>5) is the input channel, column lane&31 the output channel
-    const float unscale = a.wscale / ((a.x_amax ? pow2_scale(*a.x_amax) : 1.f) * (a.d_amax ? pow2_scale(*a.d_amax) : 1.f));
+    const float unscale = wg_unscale(a.t);
     const int p0 = wave * NP / WG_WAVES, p1 = (wave + 1) * NP / WG_WAVES;
 #pragma unroll
     for (int s = 0; s < MAXP; ++s) {
         const int p = p0 + s;
         if (p >= p1) break;
-        const int ky = p / (KW * COTW), kx = (p / COTW) % KW, c = p % COTW;
-        const int co = (cow * COTW + c) * 32 + r;
-        if (co >= a.cout_total) continue;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int ci = cit * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
-            const float val = acc[s][v];
-            if (ci < a.cin_total && val != 0.f)
-                atomicAdd(a.dw + ((size_t)(ky * KW + kx) * a.cin_total + ci) * a.cout_total + co, val * unscale);
-        }
+        // tap (ky, kx) = p / COTW, cout tile p % COTW of the window
+        add_tile(a.t, acc[s], unscale, p / COTW, 0, a.t.cin_total, cit, 0, a.t.cout_total, cow * COTW + p % COTW, lane);
     }
 }
 
-template <int KH, int KW, int COTW, int PREC>
-hipError_t launch_ring(hipStream_t s, const WrArgs& a, int blocks) {
-    constexpr size_t lds = (size_t)(KH + 1) * WR_XSLOT + 2 * (size_t)(2 * COTW * 4 * WR_DP * 16);
-    static_assert(lds <= WG_LDS_MAX, "ring kernel LDS plan");
-    const hipError_t e = mpg::launch_dyn_lds<wgrad_ring_kernel<KH, KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks), dim3(WG_THREADS), lds, s, a);
-    return e != hipSuccess ? e : hipGetLastError();
-}
-
-template <int KW, int COTW, int PREC>
-hipError_t launch(hipStream_t s, const WgArgs& a, int blocks, size_t lds_bytes) {
-    const hipError_t e = mpg::launch_dyn_lds<wgrad_mfma_kernel<KW, COTW, PREC>, WG_LDS_MAX>(dim3(blocks), dim3(WG_THREADS), lds_bytes, s, a);
+template <auto Kernel, class Args>
+hipError_t launch(hipStream_t s, const Args& a, int blocks, int lds_bytes) {
+    const hipError_t e = mpg::launch_dyn_lds<Kernel, WG_LDS_MAX>(dim3(blocks), dim3(WG_THREADS), (size_t)lds_bytes, s, a);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
@@ -805,7 +687,7 @@ int wgrad_plan(int n, int h, int w, int cin, int cout, int kh, int kw, int prec,
     // all filter rows of a tile in one block, x rows in an LDS ring (wgrad_ring_kernel): 1.02 .. 3x faster than the
     // one-filter-row kernel on every 3x3 / 4x4 / 5x5 shape of the training steps (tools/probe_wgrad_shapes.py,
     // profiles/r03/wgrad_variants.md); other filter shapes stay on that kernel
-    if (MPG_WG_RING && kh == kw && (kh == 3 || kh == 4 || kh == 5)) {
+    if (kh == kw && (kh == 3 || kh == 4 || kh == 5)) {
         const int nco = (cout + 31) / 32;
         // cout tiles per window: as many as the registers of a wave take beside its windows (5x5 with a 64-wide window is 7
         // tiles on two of the waves and compiled to 28 spilled registers: 32-wide windows there, 4 tiles on one wave, 3 on
@@ -828,7 +710,7 @@ int wgrad_plan(int n, int h, int w, int cin, int cout, int kh, int kw, int prec,
         l.ranges = (h + l.rows_per_range - 1) / l.rows_per_range;
         l.n_outer = n * l.ranges * l.chunks;
         l.blocks = ((l.n_outer + 7) / 8) * 8 * l.n_ci * l.n_cow;
-        l.lds = (kh + 1) * WR_XSLOT + 2 * (2 * cotw * 4 * WR_DP * 16);
+        l.lds = wr_lds_bytes(kh, cotw);
         return emit(l);
     }
     // a wave keeps KW * COTW accumulator tiles of 16 registers, 6 at most beside its fragments (256 registers per wave at two
@@ -857,8 +739,8 @@ int wgrad_plan(int n, int h, int w, int cin, int cout, int kh, int kw, int prec,
             const int xu = X_UNITS_DMA;
             const int gx = l.cit * 4, gd = l.cog * l.cotw * 4;    // channel groups of the LDS images
             // short rows, and at most xu (x) / D_UNITS_DMA (dy) LDS-DMA instructions per wave in the copy plan
-            auto x_units = [&](int chunk) { return gx * npl * (chunk + 16 + LDS_ROW_PAD); };
-            auto d_units = [&](int chunk) { return gd * npl * (chunk + LDS_ROW_PAD); };
+            auto x_units = [&](int chunk) { return gx * npl * x_row_units(chunk); };
+            auto d_units = [&](int chunk) { return gd * npl * d_row_units(chunk); };
             while (l.chunk > 32 && (l.chunk / 2 >= w || x_units(l.chunk) > xu * WG_THREADS || d_units(l.chunk) > D_UNITS_DMA * WG_THREADS))
                 l.chunk /= 2;
             if (l.chunk / 16 < l.ks) l.ks = l.chunk / 16;         // the other waves idle (tiny layers)
@@ -885,47 +767,39 @@ int wgrad_launches(hipStream_t s, const char* xg, const char* dg, const float* x
     MPG_REQUIRE((size_t)((cin > cout ? cin : cout) + 7) / 8 * 2 * h * w < (1u << 30), "mpg_conv2d_wgrad: image too large");
     hipError_t e = mpg::zero_async(dw, (size_t)kh * kw * cin * cout * sizeof(float), s);
     if (e != hipSuccess) return mpg::hip_check(e, "mpg_conv2d_wgrad: memset");
+    const WgTensors t = {xg, dg, x_amax, d_amax, zeros, dw, n, h, w, (cin + 7) / 8, (cout + 7) / 8, cin, cout, wscale};
     const int rc = wgrad_plan(n, h, w, cin, cout, kh, kw, prec, [&](const WgLaunch& l) -> int {
         hipError_t le = hipErrorInvalidValue;
         if (l.form == MPG_WGRAD_FORM_RING) {
             WrArgs a;
-            a.xg = xg; a.dg = dg; a.x_amax = x_amax; a.d_amax = d_amax; a.zeros = zeros; a.dw = dw;
-            a.n = n; a.h = h; a.w = w;
-            a.x_cg = (cin + 7) / 8; a.d_cg = (cout + 7) / 8;
-            a.cin_total = cin; a.cout_total = cout;
+            a.t = t;
             a.pt = (kh - 1) / 2;
-            a.wscale = wscale;
             a.chunks = l.chunks; a.n_ci = l.n_ci; a.n_cow = l.n_cow;
             a.ranges = l.ranges; a.rows_per_range = l.rows_per_range; a.n_outer = l.n_outer;
-#define MPG_WR(K, C)                                                                      \
-    if (l.k == K && l.cotw == C)                                                          \
-        le = l.prec == 3 ? launch_ring<K, K, C, 3>(s, a, l.blocks) : launch_ring<K, K, C, 1>(s, a, l.blocks)
-            MPG_WR(3, 1); MPG_WR(3, 2); MPG_WR(4, 1); MPG_WR(4, 2); MPG_WR(5, 1);
-            if (l.k == 3 && l.cotw == 4) le = launch_ring<3, 3, 4, 1>(s, a, l.blocks);
+#define MPG_WR(K, C, P) \
+    if (l.k == K && l.cotw == C && l.prec == P) le = launch<wgrad_ring_kernel<K, K, C, P>>(s, a, l.blocks, l.lds)
+            MPG_WR(3, 1, 3); MPG_WR(3, 1, 1); MPG_WR(3, 2, 3); MPG_WR(3, 2, 1); MPG_WR(3, 4, 1); MPG_WR(4, 1, 3);
+            MPG_WR(4, 1, 1); MPG_WR(4, 2, 3); MPG_WR(4, 2, 1); MPG_WR(5, 1, 3); MPG_WR(5, 1, 1);
 #undef MPG_WR
             return le != hipSuccess ? mpg::hip_check(le, "wgrad_ring_kernel") : MPG_OK;
         }
         WgArgs a;
-        a.xg = xg; a.dg = dg; a.x_amax = x_amax; a.d_amax = d_amax; a.dw = dw; a.zeros = zeros;
-        a.n = n; a.h = h; a.w = w;
-        a.x_cg = (cin + 7) / 8; a.d_cg = (cout + 7) / 8;
-        a.cin_total = cin; a.cout_total = cout; a.ci0 = l.ci0; a.co0 = l.co0;
-        a.cin = l.cin; a.cout = l.cout;
+        a.t = t;
+        a.ci0 = l.ci0; a.co0 = l.co0; a.cin = l.cin; a.cout = l.cout;
         a.windows = l.windows;
-        a.kh = kh; a.pt = (kh - 1) / 2; a.pl = (kw - 1) / 2;
+        a.kh = kh; a.pt = (kh - 1) / 2;
         a.cit = l.cit; a.cog = l.cog; a.ks = l.ks;
         a.chunk = l.chunk;
-        a.xp = l.chunk + 16 + LDS_ROW_PAD;
-        a.dp = l.chunk + LDS_ROW_PAD;
+        a.xp = x_row_units(l.chunk);
+        a.dp = d_row_units(l.chunk);
         a.nsplit = l.nsplit; a.rows_per_split = l.rows_per_split;
-        a.wscale = wscale;
         const int npl = l.prec == 3 ? 2 : 1;
         const int xunits = l.cit * 4 * npl * a.xp, dunits = l.cog * l.cotw * 4 * npl * a.dp;
         MPG_REQUIRE((size_t)l.lds <= WG_LDS_MAX, "mpg_conv2d_wgrad: LDS plan %d bytes", l.lds);
         MPG_REQUIRE(xunits <= X_UNITS_DMA * WG_THREADS && dunits <= D_UNITS_DMA * WG_THREADS, "mpg_conv2d_wgrad: copy plan");
-#define MPG_WGM(K, C)                                                                        \
-    if (l.k == K && l.cotw == C)                                                             \
-        le = l.prec == 3 ? launch<K, C, 3>(s, a, l.blocks, (size_t)l.lds) : launch<K, C, 1>(s, a, l.blocks, (size_t)l.lds)
+#define MPG_WGM(K, C)                                                                                        \
+    if (l.k == K && l.cotw == C && l.prec == 3) le = launch<wgrad_mfma_kernel<K, C, 3>>(s, a, l.blocks, l.lds); \
+    if (l.k == K && l.cotw == C && l.prec == 1) le = launch<wgrad_mfma_kernel<K, C, 1>>(s, a, l.blocks, l.lds)
         MPG_WGM(1, 1); MPG_WGM(1, 2); MPG_WGM(3, 1); MPG_WGM(3, 2); MPG_WGM(4, 1); MPG_WGM(5, 1);
 #undef MPG_WGM
         return le != hipSuccess ? mpg::hip_check(le, "wgrad_mfma_kernel") : MPG_OK;
@@ -934,15 +808,13 @@ int wgrad_launches(hipStream_t s, const char* xg, const char* dg, const float* x
     MPG_LAUNCH_CHECK("mpg_conv2d_wgrad");
 }
 
-}  // namespace
-
-#if MPG_WG_DIAG
-extern "C" int mpg_debug_wg_diag(unsigned long long* out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_wg_diag), 64) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_wg_diag), z, 64) != hipSuccess) return 1; }
-    return 0;
+// blocks of absmax_kernel for n >= 1 elements: 16 per thread, 4096 blocks at most
+unsigned absmax_grid(size_t n) {
+    const size_t b = (n + BLK * 16 - 1) / (BLK * 16);
+    return (unsigned)(b > 4096 ? 4096 : b);
 }
-#endif
+
+}  // namespace
 
 extern "C" int mpg_absmax(mpg_stream_t stream, const float* x, size_t n, float* out) {
     MPG_REQUIRE(x && out, "mpg_absmax: null pointer");
@@ -950,9 +822,7 @@ extern "C" int mpg_absmax(mpg_stream_t stream, const float* x, size_t n, float* 
     hipError_t e = mpg::zero_async(out, sizeof(float), s);
     if (e != hipSuccess) return mpg::hip_check(e, "mpg_absmax: zero");
     if (n == 0) return MPG_OK;
-    size_t b = (n + BLK * 16 - 1) / (BLK * 16);
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)b), dim3(BLK), 0, s, x, n, (unsigned int*)out);
+    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(n)), dim3(BLK), 0, s, x, n, (unsigned int*)out);
     MPG_LAUNCH_CHECK("absmax_kernel");
 }
 
@@ -1017,11 +887,10 @@ extern "C" int mpg_conv2d_wgrad_mfma(mpg_stream_t stream, const float* x, int n,
     // nodes than a launch), zero where the reductions below fill them in
     hipLaunchKernelGGL(amax_init_kernel, dim3(1), dim3(64), 0, s, amax, x_amax, dy_amax);
     const size_t nx = (size_t)n * h * w * cin, nd = (size_t)n * h * w * cout;
-    auto am_grid = [](size_t n) { const size_t b = (n + BLK * 16 - 1) / (BLK * 16); return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); };
     if (x_amax == nullptr)       // else: e.g. a forward activation whose scale the caller fixes (no reduction pass over x)
-        hipLaunchKernelGGL(absmax_kernel, dim3(am_grid(nx)), dim3(BLK), 0, s, x, nx, (unsigned int*)amax);
+        hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(nx)), dim3(BLK), 0, s, x, nx, (unsigned int*)amax);
     if (dy_amax == nullptr)      // else: the caller already has max |dy| (it scales the data gradient with it too)
-        hipLaunchKernelGGL(absmax_kernel, dim3(am_grid(nd)), dim3(BLK), 0, s, dy, nd, (unsigned int*)(amax + 1));
+        hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(nd)), dim3(BLK), 0, s, dy, nd, (unsigned int*)(amax + 1));
     int e = mpg_f32_to_g8_scaled(stream, x, n, h, w, cin, 0, cin, MPG_G8_F16, amax, xg);
     if (e != MPG_OK) return e;
     e = mpg_f32_to_g8_scaled(stream, dy, n, h, w, cout, 0, cout, MPG_G8_F16, amax + 1, dg);
