@@ -4,7 +4,9 @@ called directly and held against the plain references of tests/valu_ref.py (chec
 The host entry points choose a kernel by channel count, 16-byte pointer alignment, element count or a grid cap with a
 grid-stride loop.  The conditions are copied here; a case names the one it is there for in its id.  When a constant changes
 in the source, this table says which shapes have to move with it.  ("chan_sum4", "apply4", "cutoff4", "space_to_depth4":
-the V = 4 instantiation of chan_sum_kernel, bn_apply_kernel, cutoff_kernel, space_to_depth_kernel.)
+the V = 4 instantiation of chan_sum_kernel, bn_apply_kernel, cutoff_kernel, space_to_depth_kernel.)  The branches of
+mpgan_train_conv.hip (mpg_conv2d_wgrad, mpg_conv2d_dgrad, mpg_fc_forward) are not in this file: they are covered bit for
+bit by test_train_conv_gpu.py, and those of mpgan_optim.hip by test_optim_gpu.py, each with a table of its own.
 
   constant                  value   source (file: constant or function)          cases that cross it
   BLK                       256     mpgan_valu.h: BLK
