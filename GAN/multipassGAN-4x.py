@@ -62,7 +62,7 @@ for name, default in [
         ("simLowHeight", 64), ("overlappedpixel", 3), ("startIndex", 0), ("useAvgDepool", False), ("avgMode", 0),
         ("velScale", 1.0), ("upsamplingMode", 2), ("upsampledData", False), ("sliceMode", 0), ("interpMode", 1),
         ("genUni", False), ("setVelZero", False), ("upsampleFirst", True), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("deviceTiles", 1), ("uniCodec", 0)]:
+        ("deviceTiles", 1), ("uniCodec", 0), ("deviceLoader", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -116,6 +116,16 @@ def train_main():
             return DeviceTileCreator(device=device, **kw)
     else:
         Tiles = tc.TileCreator
+    # deviceLoader 1: the slice conversion of the training set (axis view, both zooms, density filter, row selection) runs
+    # in HIP kernels on the uploaded source, only the kept slices come back (fluiddataloader_device); 0 (default): the
+    # host FluidDataLoader (scipy.ndimage.zoom of every whole entry on one thread)
+    if int(P["deviceLoader"]) > 0:
+        from mpgan_amd.fluiddataloader_device import DeviceFluidDataLoader
+
+        def Loader(**kw):
+            return DeviceFluidDataLoader(device=device, **kw)
+    else:
+        Loader = FDL.FluidDataLoader
     if mode == 1:
         # second network (:234,241-248,253-262,291-299): slices along x of volumes zoomed to the high resolution,
         # their density channel replaced by the first network's output (density_low_2x2_%04d.uni)
@@ -130,18 +140,17 @@ def train_main():
                       axis_scaling_y=[1, 1, 1, 1], axis_scaling=[upRes, upRes, upRes, 1], filename="density_low_%04d.uni",
                       oldNamingScheme=False, filename_index_max=frame_max, filename_index_min=frame_min, indices=dirIDs,
                       data_fraction=data_fraction, multi_file_list_y=mfh * 3, multi_file_idxOff_y=moh)
-        fl2 = FDL.FluidDataLoader(filename_y="density_low_2x2_%04d.uni", multi_file_list=["density"] * 3,
-                                  multi_file_idxOff=[0, 1, 2], **common)
-        fl = FDL.FluidDataLoader(filename_y="density_high_%04d.uni", multi_file_list=mfl * 3, multi_file_idxOff=mol, **common)
+        fl2 = Loader(filename_y="density_low_2x2_%04d.uni", multi_file_list=["density"] * 3, multi_file_idxOff=[0, 1, 2], **common)
+        fl = Loader(filename_y="density_high_%04d.uni", multi_file_list=mfl * 3, multi_file_idxOff=mol, **common)
     elif not useTempoD:
         tiCr = Tiles(tileSizeLow=tileSizeLow, simSizeLow=simSizeLow, dim=2, dim_t=1, channelLayout_low=channelLayout_low,
                               upres=upRes, premadeTiles=False, channelLayout_high='d')
-        fl = FDL.FluidDataLoader(print_info=1, base_path=packedSimPath, base_path_y=packedSimPath, numpy_seed=randSeed,
-                                 conv_slices=True, conv_axis=0, select_random=0.1, density_threshold=0.002,
-                                 axis_scaling_y=[1.0 / upRes, 1, 1, 1], axis_scaling=[1, 1, 1, 1],
-                                 filename="density_low_%04d.uni", filename_index_min=frame_min, oldNamingScheme=False,
-                                 filename_y="density_high_%04d.uni", filename_index_max=frame_max, indices=dirIDs,
-                                 data_fraction=data_fraction, multi_file_list=mfl, multi_file_list_y=mfh)
+        fl = Loader(print_info=1, base_path=packedSimPath, base_path_y=packedSimPath, numpy_seed=randSeed,
+                    conv_slices=True, conv_axis=0, select_random=0.1, density_threshold=0.002,
+                    axis_scaling_y=[1.0 / upRes, 1, 1, 1], axis_scaling=[1, 1, 1, 1],
+                    filename="density_low_%04d.uni", filename_index_min=frame_min, oldNamingScheme=False,
+                    filename_y="density_high_%04d.uni", filename_index_max=frame_max, indices=dirIDs,
+                    data_fraction=data_fraction, multi_file_list=mfl, multi_file_list_y=mfh)
         n_t = 1
     else:                                                              # three coherent frames per sample (:214-262)
         n_t = 3
@@ -149,13 +158,13 @@ def train_main():
         moh = [o for o in range(3) for _ in mfh]
         tiCr = Tiles(tileSizeLow=tileSizeLow, densityMinimum=0.005, channelLayout_high='d', simSizeLow=simSizeLow,
                               dim=2, dim_t=3, channelLayout_low=channelLayout_low, upres=upRes, premadeTiles=False)
-        fl = FDL.FluidDataLoader(print_info=0, base_path=packedSimPath, base_path_y=packedSimPath, numpy_seed=randSeed,
-                                 conv_slices=True, conv_axis=0, select_random=0.1, density_threshold=0.002,
-                                 axis_scaling_y=[1.0 / upRes, 1, 1, 1], axis_scaling=[1, 1, 1, 1],
-                                 filename="density_low_%04d.uni", oldNamingScheme=False, filename_y="density_high_%04d.uni",
-                                 filename_index_max=frame_max, filename_index_min=frame_min, indices=dirIDs,
-                                 data_fraction=data_fraction, multi_file_list=mfl * 3, multi_file_idxOff=mol,
-                                 multi_file_list_y=mfh * 3, multi_file_idxOff_y=moh)
+        fl = Loader(print_info=0, base_path=packedSimPath, base_path_y=packedSimPath, numpy_seed=randSeed,
+                    conv_slices=True, conv_axis=0, select_random=0.1, density_threshold=0.002,
+                    axis_scaling_y=[1.0 / upRes, 1, 1, 1], axis_scaling=[1, 1, 1, 1],
+                    filename="density_low_%04d.uni", oldNamingScheme=False, filename_y="density_high_%04d.uni",
+                    filename_index_max=frame_max, filename_index_min=frame_min, indices=dirIDs,
+                    data_fraction=data_fraction, multi_file_list=mfl * 3, multi_file_idxOff=mol,
+                    multi_file_list_y=mfh * 3, multi_file_idxOff_y=moh)
     if int(P["dataAugmentation"]):
         tiCr.initDataAugmentation(rot=int(P["rot"]), minScale=float(P["minScale"]), maxScale=float(P["maxScale"]),
                                   flip=int(P["flip"]))

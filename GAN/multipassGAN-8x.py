@@ -59,7 +59,7 @@ for name, default in [
         ("stageIter", 25000), ("decayIter", 25000), ("maxFms", 256), ("use_wgan_gp", False), ("use_res_net", False),
         ("use_mb_stddev", False), ("deviceTiles", 1), ("use_LSGAN", False), ("startFms", 512), ("filterSize", 3), ("outNNTestNo", 17),
         ("firstNNArch", False), ("gDrop", False), ("add_adj_idcs", False), ("gpu", 2), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("uniCodec", 0)]:
+        ("uniCodec", 0), ("deviceLoader", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -187,6 +187,16 @@ device = "cuda:0"
 device_tiles = int(P["deviceTiles"]) > 0
 if device_tiles:
     from mpgan_amd.tiles_device import DeviceTileCreator  # noqa: E402
+# deviceLoader 1: the slice conversion of the training set (axis view, zoom, density filter, adjacent slices, row selection)
+# runs in HIP kernels on the uploaded source and only the kept slices come back (fluiddataloader_device); 0 (default):
+# the host FluidDataLoader
+if int(P["deviceLoader"]) > 0:
+    from mpgan_amd.fluiddataloader_device import DeviceFluidDataLoader  # noqa: E402
+
+    def Loader(**kw):
+        return DeviceFluidDataLoader(device=device, **kw)
+else:
+    Loader = FDL.FluidDataLoader
 
 channelLayout_low, channelLayout_high, mfl, mfh = 'd', ('d,d' if later_net else 'd'), ["density"], ["density"]
 if useVelocities:
@@ -225,10 +235,10 @@ def load_stage(currentUpres, first):
     first_fraction = max(data_fraction * 2 / currentUpres, min_data_fraction)
     x_2 = None
     if later_net:      # the same slices of the previous network's output, read as the `y` of a density-only loader (:324-333)
-        fl2 = FDL.FluidDataLoader(filename_y=lowfilename_2, data_fraction=first_fraction, multi_file_list=["density"] * 3,
-                                  multi_file_idxOff=[0, 1, 2], **common)
-    fl = FDL.FluidDataLoader(filename_y=high, data_fraction=first_fraction if first else data_fraction,
-                             multi_file_list=mfl * 3, multi_file_idxOff=mol, **common)
+        fl2 = Loader(filename_y=lowfilename_2, data_fraction=first_fraction, multi_file_list=["density"] * 3,
+                     multi_file_idxOff=[0, 1, 2], **common)
+    fl = Loader(filename_y=high, data_fraction=first_fraction if first else data_fraction, multi_file_list=mfl * 3,
+                multi_file_idxOff=mol, **common)
     if aug:
         tiCr.initDataAugmentation(rot=int(P["rot"]), minScale=float(P["minScale"]), maxScale=float(P["maxScale"]),
                                   flip=int(P["flip"]))

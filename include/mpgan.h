@@ -533,6 +533,29 @@ int mpg_tile_orient(mpg_stream_t stream, const float* src, int zs, int ys, int x
                     const float* chan_sign, float* dst);
 int mpg_semilagr_positions(mpg_stream_t stream, const float* vel, const float* dt, int n_batch, int h, int w, int n_out,
                            float* pos);
+/* ------------------------------------------------------------------------
+ * Slice mode of the training-set loader on a device-resident source (tools_wscale/fluiddataloader.py:387-544; SURVEY 8f
+ * rank 2).  File handling and every random draw stay on the host (multi-pass-gan_amd/fluiddataloader_device.py).
+ * Both entries work on the virtual array V = scipy.ndimage.zoom(transpose(src, perm3 + (3,)), order=1), which is never
+ * stored: src [dims3[0], dims3[1], dims3[2], c] fp32, perm3 the axis order of the slice view (:416-431; NULL = identity),
+ * out3 V's spatial size (int(round(n * factor)) per axis, from the caller).  Along an axis of n source and o output
+ * points index i reads the coordinate i * ((n - 1) / (o - 1)), in float64 (i * 1.0 where o == 1), and is 0 where that
+ * exceeds n - 1, as scipy's; fp32 linear weights, axis by axis; an axis whose weight is 0 takes no blend, so factor 1
+ * returns the source's bits.
+ *   mpg_slice_zoom_means: means[s] = mean over (i, j) of V[s, i, j, chan], s in [0, out3[0]) -- the quantity
+ *     removeSlices compares with density_threshold (:295-313).  Block sums added in a fixed order: the same bits on every
+ *     run.  workspace: at least 64 * out3[0] floats of device memory.
+ *   mpg_slice_zoom_gather: out[r, i, j, c_off + q] = V[slices[r], i, j, chan_map[q]], q in [0, n_chan); slices (device
+ *     memory) holds n_slices indices along V's axis 0; a row of out has out_c channels, so several sources fill their
+ *     channel windows of one array.  chan_map (host memory, NULL = identity, n_chan <= 16) carries the exchange of
+ *     velocity components of the slice view.  adj != 0 is addAdjSlices (:315-336): n_chan is three packed frames, each
+ *     followed by channel 0 of that frame in V[slices[r] - 1] and in V[slices[r] + 1] (0 beyond the ends), n_chan + 6
+ *     channels written. */
+int mpg_slice_zoom_means(mpg_stream_t stream, const float* src, const int* dims3, int c, const int* perm3,
+                         const int* out3, int chan, float* means, float* workspace, size_t workspace_floats);
+int mpg_slice_zoom_gather(mpg_stream_t stream, const float* src, const int* dims3, int c, const int* perm3,
+                          const int* out3, const int* slices, int n_slices, const int* chan_map, int n_chan, int adj,
+                          float* out, int out_c, int c_off);
 
 /* the reductions of the generator losses (multipassGAN-4x.py:754,764-765): out[0] = sum |a - b| (mode 0,
  * tf.reduce_mean(tf.abs(..)) after division by n) or sum (a - b)^2 (mode 1, 2 * tf.nn.l2_loss); b NULL = 0 */

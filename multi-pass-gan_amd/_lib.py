@@ -174,6 +174,10 @@ PROTOTYPES = {
     "mpg_tile_orient": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
                             ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_float), _P]),
     "mpg_semilagr_positions": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    # slice mode of the training-set loader
+    "mpg_slice_zoom_means": (_I, [_P, _P, ctypes.POINTER(_I), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _P, _P, _Z]),
+    "mpg_slice_zoom_gather": (_I, [_P, _P, ctypes.POINTER(_I), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _I,
+                                  ctypes.POINTER(_I), _I, _I, _P, _I, _I]),
     "mpg_pair_reduce": (_I, [_P, _P, _P, _Z, _I, _P]),
     "mpg_adam_step": (_I, [_P, _P, _P, _P, _P, _Z, _P, _F, _F, _F]),
     "mpg_adam_step_staged": (_I, [_P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _F]),
