@@ -62,7 +62,7 @@ for name, default in [
         ("simLowHeight", 64), ("overlappedpixel", 3), ("startIndex", 0), ("useAvgDepool", False), ("avgMode", 0),
         ("velScale", 1.0), ("upsamplingMode", 2), ("upsampledData", False), ("sliceMode", 0), ("interpMode", 1),
         ("genUni", False), ("setVelZero", False), ("upsampleFirst", True), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("deviceTiles", 1), ("uniCodec", 0), ("deviceLoader", 0)]:
+        ("deviceTiles", 1), ("uniCodec", 0), ("deviceLoader", 0), ("previews", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -344,34 +344,48 @@ gen = multipass.Generator("gen_resnet", dict(tile_low=simSizeLow, up_res=upRes, 
                           params, prec=ops.parse_prec(P["prec"]), device=device, seed=int(P["randSeed"]))
 print('*****OUTPUT ONLY*****')
 s = simSizeHigh
+previews = int(P["previews"])                # extension: 1 = source_%04d.png per frame into test_path (4x.py:1134,1146)
+pictures = 0
+if previews:
+    from mpgan_amd import preview
+    os.makedirs(basePath + 'test_%04d/' % load_model_test, exist_ok=True)
+    test_path, _ = ph.getNextGenericPath('out_%04d-%04d' % (load_model_test, load_model_no), 0,
+                                         basePath + 'test_%04d/' % load_model_test)      # 4x.py:356-357
 for layerno in range(frame_min, frame_max):
     i = layerno - frame_min
     start = time.time()
     low = torch.as_tensor(np.ascontiguousarray(x[i])).to(device)
     slices = simSizeHigh
+    sink = preview.PreviewSink(test_path, layerno, int(P["tileSize"]) * upRes) if previews else None
     if upsampling_mode == 2 and not upsample_first:
+        # (the reference writes no picture in this branch, 4x.py:1135-1136)
         vol = multipass.plane_pass_4x(gen, low, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni))
         name = 'density_low_2x2x1_%04d.uni'
         slices = simSizeLow
     elif upsampling_mode == 0:
         v1 = torch.as_tensor(np.ascontiguousarray(x_2[i][..., 0])).to(device)
-        vol = multipass.upsample_pass_4x(gen, low, v1, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni))
+        vol = multipass.upsample_pass_4x(gen, low, v1, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni),
+                                         previews=sink)
         name = 'density_low_1x1x1_%04d.uni'
     elif upsampling_mode == 2:
         if n_ch > 1:
             low[..., 1:4] *= velScale                                        # 4x.py:283
         xs = ops.axis_zoom_linear(low, 0, upRes)                             # 4x.py:1103
         out = multipass._run_pass(gen, xs, None, 0, s, 8)                    # (z, y, x)
+        if sink is not None:
+            sink.projection(None, out, (0, 1, 2))                            # 4x.py:1133-1134, before the cutoff
         vol = ops.cutoff(out, multipass.CUTOFF) if generateUni else out
         name = 'density_low_2x2_%04d.uni'
     else:
         # upsamplingMode 1: planes (z,y) along x -> density_low_1x1; upsamplingMode 3: planes (z,x) along y -> density_low_0x0
         v1 = torch.as_tensor(np.ascontiguousarray(x_2[i][..., 0])).to(device)
         vol = multipass.refine_pass_4x(gen, low, v1, upRes, mode=upsampling_mode, batch=8, vel_scale=velScale,
-                                       apply_cutoff=bool(generateUni))
+                                       apply_cutoff=bool(generateUni), previews=sink)
         name = 'density_low_1x1_%04d.uni' if upsampling_mode == 1 else 'density_low_0x0_%04d.uni'
     torch.cuda.synchronize()
     print(time.time() - start)
+    if sink is not None:
+        pictures += len(sink.written)
     if generateUni:
         head, _ = uniio.readUni(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, layerno))
         head['dimX'] = head['dimY'] = simSizeHigh
@@ -380,3 +394,5 @@ for layerno in range(frame_min, frame_max):
                                  codec="device" if int(P["uniCodec"]) else "host")
     print('')
 print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))
+if previews:
+    print('%d pngs written to %s.' % (pictures, test_path))

@@ -59,7 +59,7 @@ for name, default in [
         ("stageIter", 25000), ("decayIter", 25000), ("maxFms", 256), ("use_wgan_gp", False), ("use_res_net", False),
         ("use_mb_stddev", False), ("deviceTiles", 1), ("use_LSGAN", False), ("startFms", 512), ("filterSize", 3), ("outNNTestNo", 17),
         ("firstNNArch", False), ("gDrop", False), ("add_adj_idcs", False), ("gpu", 2), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("uniCodec", 0), ("deviceLoader", 0)]:
+        ("uniCodec", 0), ("deviceLoader", 0), ("previews", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -129,13 +129,22 @@ def output_main():
     probe = sims + "sim_%04d/density_low_%04d.uni" % (from_sim, 0)
     head_0, _ = uniio.readUni(probe if os.path.exists(probe) else sims + "sim_%04d/density_low_%04d.uni" % (from_sim, f0))
     gen_uni = int(P["genUni"]) > 0
+    previews = int(P["previews"])            # extension: 1 = source_%04d.png per frame into test_path (8x.py:1718)
+    pictures = 0
+    if previews:
+        from mpgan_amd import preview
+        os.makedirs(base + 'test_%04d/' % test_no, exist_ok=True)
+        test_path, _ = ph.getNextGenericPath('out_%04d-%04d' % (test_no, model_no), 0, base + 'test_%04d/' % test_no)   # :428-429
     for layerno in range(f0, f1):
         print(layerno)
         t0 = time.time()
         low = torch.as_tensor(np.ascontiguousarray(x_3d[layerno - f0])).to("cuda:0")
         prev = None if x_2 is None else torch.as_tensor(np.ascontiguousarray(x_2[layerno - f0][..., 0])).to("cuda:0")
-        vol = multipass.single_pass_8x(gen, low, prev, up, ta, batch=2, apply_cutoff=gen_uni)
+        sink = preview.PreviewSink(test_path, layerno, int(P["tileSize"]) * up) if previews else None
+        vol = multipass.single_pass_8x(gen, low, prev, up, ta, batch=2, apply_cutoff=gen_uni, previews=sink)
         torch.cuda.synchronize()
+        if sink is not None:
+            pictures += len(sink.written)
         print("time for network: {0:.6f}".format(time.time() - t0))
         if gen_uni:
             head = dict(head_0)
@@ -143,6 +152,8 @@ def output_main():
             uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol,
                                      codec="device" if int(P["uniCodec"]) else "host")
     print('Test finished, %d volumes written to %s.' % (f1 - f0, sims))
+    if previews:
+        print('%d pngs written to %s.' % (pictures, test_path))
 
 
 if int(P["out"]) > 0:

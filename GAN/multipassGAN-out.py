@@ -6,7 +6,11 @@ HIP path (volumes stay in HBM between the passes).
 
 Differences, all deliberate: weights come from ``model_%04d.ckpt.npz`` (see checkpoint.py);
 ``synthWeights 1`` (extra, optional) falls back to seeded random weights when a checkpoint is
-missing; PNG previews are skipped (scipy.misc.imsave no longer exists); three loaded networks
+missing; ``previews 1`` (extra, optional, default 0) writes the reference's PNG previews into ``test_path``
+(``basePath/test_%04d/out_%04d-%04d_%04d/``): after each pass the stacked axis sums ``source_1st/2nd/3rd_%04d.png``
+(:461,523,585), after the last one the mid planes ``slice_xy/yz/xz_<i>_<frame>.png`` gated on the xy mean, and every
+plane of frame 110 (:592-604) -- made on the GPU from the pass volumes before the cutoff (mpgan_amd/preview.py), encoded
+without scipy.misc or Pillow; three loaded networks
 run as three passes (the reference exits on an inverted check, :624-626); ``prec`` selects the
 arithmetic (2 = MPG_PREC_F16F6, default; 3 = MPG_PREC_F16X3).  ``transposeAxis`` 0..3 pick the slicing
 axes of the passes exactly as :397-547 do, including what is broken there: the third pass of
@@ -23,7 +27,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 import mpgan_amd  # noqa: E402,F401
-from mpgan_amd import checkpoint, multipass, uniio  # noqa: E402
+from mpgan_amd import checkpoint, multipass, preview, uniio  # noqa: E402
 from mpgan_amd import fluiddataloader as FDL  # noqa: E402
 from mpgan_amd import paramhelpers as ph  # noqa: E402
 
@@ -57,6 +61,7 @@ gpu = ph.getParam("gpu", "0")
 synthWeights = int(ph.getParam("synthWeights", 0))          # extension: seeded random weights if no checkpoint
 prec = ph.getParam("prec", "2")                             # extension: 2 = f16f6 (default), 3 = f16x3 (fp32-grade)
 uniCodec = int(ph.getParam("uniCodec", 0))                  # extension: .uni deflate on 0 = the host (zlib), 1 = the GPU
+previews = int(ph.getParam("previews", 0))                  # extension: 1 = write the reference's PNG previews (out.py:461-604)
 nets = []
 for k in (1, 2, 3):
     nets.append(dict(
@@ -99,6 +104,8 @@ for k, n in enumerate(nets):
         print('ERROR: Test to load does not exist.')
     path = checkpoint.model_path(basePath, n["load_model_test"], n["load_model_no"], ema=bool(load_emas))
     prefix = 'out_%04d-%04d' % (n["load_model_test"], n["load_model_no"])
+    if previews:                                                 # the pictures need test_path (synthWeights 1: no test directory yet)
+        os.makedirs(basePath + 'test_%04d/' % n["load_model_test"], exist_ok=True)
     if os.path.isdir(basePath + 'test_%04d/' % n["load_model_test"]):
         test_path, _ = ph.getNextGenericPath(prefix, 0, basePath + 'test_%04d/' % n["load_model_test"])
     cfg = dict(tile_low=simSizeLow, up_res=upRes, channels=n_ch, first_gen=(k == 0), filter_size=n["filter_size"],
@@ -124,17 +131,23 @@ print('*****OUTPUT ONLY*****')
 head_0, _ = uniio.readUni(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, 0)) \
     if os.path.exists(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, 0)) \
     else uniio.readUni(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, frame_min))
+pictures = 0
 for layerno in range(frame_min, frame_max):
     print(layerno)
     start = time.time()
     low = torch.as_tensor(np.ascontiguousarray(x_3d[layerno - frame_min])).to(device)
-    vol = multipass.multipass_8x(gens, low, upRes, apply_cutoff=bool(generateUni), transpose_axis=transposeAxis)
+    sink = preview.PreviewSink(test_path, layerno, tileSizeLow * upRes) if previews else None
+    vol = multipass.multipass_8x(gens, low, upRes, apply_cutoff=bool(generateUni), transpose_axis=transposeAxis,
+                                 previews=sink)
     torch.cuda.synchronize()
     print("time for %d network(s): %.6f" % (len(gens), time.time() - start))
+    if sink is not None:
+        pictures += len(sink.written)
     if generateUni:
         head = dict(head_0)
         head['dimX'] = head['dimY'] = head['dimZ'] = simSizeHigh
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/source_%04d.uni' % (fromSim, layerno), head, vol,
                                  codec="device" if uniCodec else "host")
         print('stored .uni file')
-print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))
+print('Test finished, %d volumes written to %s%s.' % (frame_max - frame_min, packedSimPath,
+                                                        ', %d pngs written to %s' % (pictures, test_path) if previews else ''))

@@ -587,6 +587,27 @@ int mpg_bn_infer_act(mpg_stream_t stream, const float* x, int n, int h, int w, i
 int mpg_tiles_to_gray8(mpg_stream_t stream, const float* tiles, int n_tiles, int th, int tw, int c, int channel,
                        int rows, int cols, unsigned char* out);
 
+/* Preview images of the inference drivers, taken from a pass volume vol [a,b,c] fp32 where it lies in device memory.
+ *   mpg_volume_projections: the three axis sums of save_img_3d (multipassGAN-out.py:208-210, called with dim_output / 80
+ *     at :461,523,585; multipassGAN-4x.py:1134,1146; multipassGAN-8x.py:1718):
+ *       p0[j,k] = sum_i fl(vol[i,j,k] / divisor), p1[i,k] = sum_j ..., p2[i,j] = sum_k ...
+ *     The division is per element and correctly rounded, before the sums, as the reference orders it.  One read of the
+ *     volume: tiles write partial sums into ws (mpg_volume_projections_ws_bytes(a,b,c) bytes of device memory, 16-byte
+ *     aligned), a second kernel adds them in a fixed order.  No atomics: the same volume gives the same bits on every run.
+ *     16-byte loads where c % 4 == 0 and vol is 16-byte aligned, scalar loads otherwise.  Any a, b, c >= 1.
+ *   mpg_volume_planes_gray8: the planes of the slice loop (multipassGAN-out.py:592-604).  For t in [0, n_idx) the plane of
+ *     vol at index idx[t] (HOST memory) of `axis` (0..2), its two remaining axes in array order, or swapped when
+ *     `transposed`, as 8-bit grey into gray[t] (device memory).  mean (device memory, n_idx floats, may be NULL): the fp32
+ *     mean of the unquantised plane, from a sum in a fixed order (the quantity :595,601 compare with 0.0001).
+ *   mpg_gray8: save_img's quantisation (multipassGAN-out.py:204-206) of n floats: uint8(clip(v * 255, 0, 255)), a float32
+ *     product, truncated.  mpg_volume_planes_gray8 applies the same. */
+size_t mpg_volume_projections_ws_bytes(int a, int b, int c);
+int mpg_volume_projections(mpg_stream_t stream, const float* vol, int a, int b, int c, float divisor, float* p0,
+                           float* p1, float* p2, void* ws);
+int mpg_volume_planes_gray8(mpg_stream_t stream, const float* vol, int a, int b, int c, int axis, const int* idx,
+                            int n_idx, int transposed, unsigned char* gray, float* mean);
+int mpg_gray8(mpg_stream_t stream, const float* img, size_t n, unsigned char* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,11 @@ PROTOTYPES = {
     "mpg_logit_stats": (_I, [_P, _P, _Z, _P]),
     "mpg_bn_infer_act": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _I, _F, _P, _P]),
     "mpg_tiles_to_gray8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # preview images of the inference drivers
+    "mpg_volume_projections_ws_bytes": (_Z, [_I, _I, _I]),
+    "mpg_volume_projections": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "mpg_volume_planes_gray8": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), _I, _I, _P, _P]),
+    "mpg_gray8": (_I, [_P, _P, _Z, _P]),
 }
 
 _lib = None

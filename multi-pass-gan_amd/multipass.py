@@ -259,11 +259,13 @@ def _pass2_4x(gen2, low, hand, up_res, batch, comm, backend, vel_scale):
     return _start_gather(comm, out2, s), v1
 
 
-def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True):
+def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True,
+                   previews=None):
     """One refining invocation of multipassGAN-4x.py (upsamplingMode 1: planes (z,y) along x, :1113-1119,1139-1142;
     upsamplingMode 3: planes (z,x) along y, :1121-1124,1144).  prev: the [z,y,x] volume of the previous network.
-    Returns the [z,y,x] volume the reference writes (cutoff :1156-1157)."""
-    comm = comm or LocalComm()
+    Returns the [z,y,x] volume the reference writes (cutoff :1156-1157).  previews: a preview.PreviewSink that receives
+    the volume where the reference calls save_img_3d (:1146), before the cutoff."""
+    comm = _preview_comm(comm, previews)
     nch = low.shape[3]
     s = low.shape[0] * up_res
     lo, hi = slice_range(s, comm)
@@ -278,7 +280,17 @@ def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend
         xin = backend.volume_transpose(prev.reshape(s, s, s), perm).reshape(s, s, s, 1)
     out = _run_pass(gen, xin, None, lo, hi, batch)
     vol = comm.all_gather_slabs(out, s)
+    if previews is not None:
+        previews.projection(None, vol, back)                         # 4x.py:1142-1146
     return backend.volume_transpose(vol, back, cutoff=CUTOFF if apply_cutoff else 0.0)
+
+
+def _preview_comm(comm, previews):
+    """the communicator of a pass; a preview sink wants the whole pass volume in this process"""
+    comm = comm or LocalComm()
+    if previews is not None:
+        previews.check_comm(comm)
+    return comm
 
 
 def _single_process(comm, what):
@@ -301,7 +313,8 @@ def plane_pass_4x(gen1, low, up_res=4, batch=8, comm=None, backend=ops, vel_scal
     return backend.cutoff(out, CUTOFF) if apply_cutoff else out
 
 
-def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True):
+def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True,
+                     previews=None):
     """upsamplingMode 0 (4x.py:277-283,1097,1107-1111,1139-1142,1166): the second network upsamples z itself.  prev: the
     [z_low, Y, X] volume of plane_pass_4x; gen0: Generator("gen_resnet", upsampling_mode=0).  The velocities are taken
     without the upres factor of modes 1 / 3 (:280); vy and vz times the velocity scale (:283 indexes the three-channel
@@ -309,8 +322,9 @@ def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops,
     1 and 2 times upRes (:1108), channels 1 and 3 swapped (:1109-1111): (d, vz, vy * upRes, vx * upRes).
     The output stack [x][y][z] goes through transpose(1, 2, 0) as :1141-1142 writes it.  That transpose was written for
     the [x][z][y] stack of mode 1; for mode 0 it leaves the axes as (y, z, x), and so does this function: the returned
-    volume (density_low_1x1x1) is what the reference stores, not a [z, y, x] one."""
-    _single_process(comm, "upsample_pass_4x")
+    volume (density_low_1x1x1) is what the reference stores, not a [z, y, x] one.  previews: a preview.PreviewSink
+    that receives the volume where the reference calls save_img_3d (:1146), before the cutoff."""
+    _preview_comm(_single_process(comm, "upsample_pass_4x"), previews)
     nch = low.shape[3]
     zl = low.shape[0]
     s = zl * up_res
@@ -325,6 +339,8 @@ def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops,
     else:
         xin = backend.volume_transpose(prev.reshape(zl, s, s), (2, 1, 0)).reshape(s, s, zl, 1)
     out = _run_pass(gen0, xin, None, 0, s, batch)                    # [x][y][z]
+    if previews is not None:
+        previews.projection(None, out, (1, 2, 0))                    # 4x.py:1142-1146
     return backend.volume_transpose(out, (1, 2, 0), cutoff=CUTOFF if apply_cutoff else 0.0)
 
 
@@ -459,11 +475,13 @@ def slice_batch_8x(low, up_res, pass_no, transpose_axis, backend=ops):
 
 
 def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops, apply_cutoff=True, transpose_axis=0,
-                 exchange="all_gather"):
+                 exchange="all_gather", previews=None):
     """gens: 1..3 Generator objects (first one firstGen).  low: device [z,y,x,4] with velocities
     already scaled by velScale (out.py:138).  Returns the density volume after the reference's final
-    axis restore (:587-590): [z,y,x] for transposeAxis 0."""
-    comm = comm or LocalComm()
+    axis restore (:587-590): [z,y,x] for transposeAxis 0.  previews: a preview.PreviewSink that receives every pass's
+    volume where the reference calls save_img_3d (:461,523,585) and the last one where its slice loop runs (:592-604),
+    all before the cutoff, each with the permutation that makes it the reference's dim_output at that line."""
+    comm = _preview_comm(comm, previews)
     a2a = _check_exchange(exchange)
     sim = low.shape[0]
     s = sim * up_res
@@ -475,19 +493,27 @@ def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops,
         out = _run_pass(gens[0], xs_r, None, 0, hi - lo, batches[0])
     else:
         out = _run_pass(gens[0], xs, None, lo, hi, batches[0])
+    if previews is not None:
+        previews.projection("1st", out, (2, 1, 0))                   # :459-461
     if len(gens) > 1:
         # pass 2 (463-523): conditioned on planes of dim_output.transpose(2,1,0) (:459)
         ys, _ = _hand_over(comm, out, s, (2, 1, 0), a2a, backend)
         xl = slice_batch_8x(low, up_res, 2, transpose_axis, backend)
         out = _run_pass(gens[1], xl[lo:hi], ys, 0, hi - lo, batches[1])
+        if previews is not None:
+            previews.projection("2nd", out, (1, 2, 0))               # :521-523
     if len(gens) > 2:
         # pass 3 (525-585): conditioned on the previous result .transpose(1,2,0) (:521)
         ys, _ = _hand_over(comm, out, s, (1, 2, 0), a2a, backend)
         xl = slice_batch_8x(low, up_res, 3, transpose_axis, backend)
         out = _run_pass(gens[2], xl[lo:hi], ys, 0, hi - lo, batches[2])
+        if previews is not None:
+            previews.projection("3rd", out, (0, 1, 2))               # :583-585
     vol = comm.all_gather_slabs(out, s)
     # the transposes the reference applies to its last dim_output, composed (459 / 521 / 583, then 587-590)
     perm = {1: (0, 1, 2), 2: (2, 1, 0), 3: (1, 0, 2)}[len(gens)]
+    if previews is not None:
+        previews.slices(vol, perm)                                   # :592-604, before the cutoff of :614
     thr = CUTOFF if apply_cutoff else 0.0
     if perm == (0, 1, 2):
         return backend.cutoff(vol, CUTOFF) if apply_cutoff else vol
@@ -504,11 +530,14 @@ _SINGLE_PASS = {0: (None, None, (0, 1, 2)), 1: ((1, 0, 2), _SWAP_YZ, (1, 0, 2)),
 _ZOOM_AXIS = {0: 0, 1: 1, 2: 2, 3: 2}
 
 
-def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, comm=None, backend=ops, apply_cutoff=True):
+def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, comm=None, backend=ops, apply_cutoff=True,
+                   previews=None):
     """One `multipassGAN-8x.py out 1` invocation.  low: device [z,y,x,C]; prev: None for the first network
     (upsamplingMode 2) or the previous network's [z,y,x] volume as stored in its .uni file (modes 1 / 3).
-    Returns the volume the reference writes: [z,y,x] with the <5e-4 cutoff (:1720-1725, 1766-1767)."""
-    comm = comm or LocalComm()
+    Returns the volume the reference writes: [z,y,x] with the <5e-4 cutoff (:1720-1725, 1766-1767).  previews: a
+    preview.PreviewSink that receives the slice stack where the reference calls save_img_3d (:1709-1718), before the
+    axis restore and the cutoff."""
+    comm = _preview_comm(comm, previews)
     sim, nch = low.shape[0], low.shape[3]
     s = sim * up_res
     lo, hi = slice_range(s, comm)
@@ -527,6 +556,8 @@ def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, com
     else:
         out = _run_pass(gen, xs, ys, lo, hi, batch)
     vol = comm.all_gather_slabs(out, s)
+    if previews is not None:
+        previews.projection(None, vol, (0, 1, 2))                    # 8x.py:1718
     thr = CUTOFF if apply_cutoff else 0.0
     if back == (0, 1, 2):
         return backend.cutoff(vol, CUTOFF) if apply_cutoff else vol

@@ -742,3 +742,56 @@ def deflate_compact(slots, sizes, units, out=None):
     _dev(out, "out", torch.uint8)
     _lib.check(lib.mpg_deflate_compact(_stream(), _ptr(slots), _ptr(sizes), units, _ptr(out), out.numel()), "mpg_deflate_compact")
     return out
+
+
+# ---------------------------------------------------------------- preview images of the inference drivers
+def _volume3(vol, what):
+    vol = _dev(vol, "vol")
+    if vol.dim() != 3 or vol.numel() == 0:
+        raise _lib.MpgError("%s: expected a non-empty [a, b, c] volume, got %s" % (what, tuple(vol.shape)))
+    return vol, [int(d) for d in vol.shape]
+
+
+def volume_projections(vol, divisor=80.0):
+    """(sum over axis 0 [b,c], over axis 1 [a,c], over axis 2 [a,b]) of vol / divisor, from one read of the volume:
+    np.sum(img, axis=0..2) of save_img_3d (multipassGAN-out.py:208-210)."""
+    lib = _lib.load()
+    vol, (a, b, c) = _volume3(vol, "volume_projections")
+    p0 = torch.empty((b, c), dtype=torch.float32, device=vol.device)
+    p1 = torch.empty((a, c), dtype=torch.float32, device=vol.device)
+    p2 = torch.empty((a, b), dtype=torch.float32, device=vol.device)
+    ws = torch.empty(int(lib.mpg_volume_projections_ws_bytes(a, b, c)), dtype=torch.uint8, device=vol.device)
+    _lib.check(lib.mpg_volume_projections(_stream(), _ptr(vol), a, b, c, float(divisor), _ptr(p0), _ptr(p1), _ptr(p2), _ptr(ws)),
+               "mpg_volume_projections")
+    return p0, p1, p2
+
+
+def volume_planes_gray8(vol, axis, idx, transposed=False):
+    """the planes of vol [a,b,c] at the indices idx of `axis` as 8-bit grey [len(idx), rows, cols] (the two remaining axes
+    in array order, swapped when transposed) and their float32 means [len(idx)] (multipassGAN-out.py:592-604)."""
+    lib = _lib.load()
+    vol, dims = _volume3(vol, "volume_planes_gray8")
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise _lib.MpgError("volume_planes_gray8: axis %r (0..2)" % (axis,))
+    idx = [int(i) for i in idx]
+    rest = [d for k, d in enumerate(dims) if k != axis]
+    if transposed:
+        rest.reverse()
+    gray = torch.empty([len(idx)] + rest, dtype=torch.uint8, device=vol.device)
+    mean = torch.empty(len(idx), dtype=torch.float32, device=vol.device)
+    if not idx:
+        return gray, mean
+    arr = (ctypes.c_int * len(idx))(*idx)
+    _lib.check(lib.mpg_volume_planes_gray8(_stream(), _ptr(vol), dims[0], dims[1], dims[2], axis, arr, len(idx),
+                                           1 if transposed else 0, _ptr(gray), _ptr(mean)), "mpg_volume_planes_gray8")
+    return gray, mean
+
+
+def gray8(img):
+    """uint8(clip(img * 255, 0, 255)) of a float32 image (save_img, multipassGAN-out.py:204-206)."""
+    lib = _lib.load()
+    img = _dev(img, "img")
+    out = torch.empty(img.shape, dtype=torch.uint8, device=img.device)
+    _lib.check(lib.mpg_gray8(_stream(), _ptr(img), img.numel(), _ptr(out)), "mpg_gray8")
+    return out
