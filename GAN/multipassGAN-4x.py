@@ -391,7 +391,7 @@ for layerno in range(frame_min, frame_max):
         head['dimX'] = head['dimY'] = simSizeHigh
         head['dimZ'] = slices                                                # 2x2x1: the slices the file holds (see above)
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/' % fromSim + name % layerno, head, vol,
-                                 codec="device" if int(P["uniCodec"]) else "host")
+                                 codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"))
     print('')
 print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))
 if previews:

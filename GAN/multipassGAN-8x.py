@@ -150,7 +150,7 @@ def output_main():
             head = dict(head_0)
             head['dimX'] = head['dimY'] = head['dimZ'] = s
             uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol,
-                                     codec="device" if int(P["uniCodec"]) else "host")
+                                     codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"))
     print('Test finished, %d volumes written to %s.' % (f1 - f0, sims))
     if previews:
         print('%d pngs written to %s.' % (pictures, test_path))

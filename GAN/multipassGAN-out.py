@@ -60,7 +60,7 @@ transposeAxis = int(ph.getParam("transposeAxis", 0))
 gpu = ph.getParam("gpu", "0")
 synthWeights = int(ph.getParam("synthWeights", 0))          # extension: seeded random weights if no checkpoint
 prec = ph.getParam("prec", "2")                             # extension: 2 = f16f6 (default), 3 = f16x3 (fp32-grade)
-uniCodec = int(ph.getParam("uniCodec", 0))                  # extension: .uni deflate on 0 = the host (zlib), 1 = the GPU
+uniCodec = int(ph.getParam("uniCodec", 0))                  # extension: .uni deflate on 0 = the host (zlib), 1 = the GPU, 2 = the GPU, Huffman code per unit
 previews = int(ph.getParam("previews", 0))                  # extension: 1 = write the reference's PNG previews (out.py:461-604)
 nets = []
 for k in (1, 2, 3):
@@ -147,7 +147,7 @@ for layerno in range(frame_min, frame_max):
         head = dict(head_0)
         head['dimX'] = head['dimY'] = head['dimZ'] = simSizeHigh
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/source_%04d.uni' % (fromSim, layerno), head, vol,
-                                 codec="device" if uniCodec else "host")
+                                 codec={0: "host", 2: "device_dynamic"}.get(uniCodec, "device"))
         print('stored .uni file')
 print('Test finished, %d volumes written to %s%s.' % (frame_max - frame_min, packedSimPath,
                                                         ', %d pngs written to %s' % (pictures, test_path) if previews else ''))

@@ -324,6 +324,13 @@ size_t mpg_deflate_ws_bytes(size_t n_bytes);
  * its length to sizes[u], and the CRC-32 (zlib.crc32) of its input bytes to crcs[u]; ceil(n_bytes / unit) units. */
 int mpg_deflate_encode(mpg_stream_t stream, const void* src, size_t n_bytes, void* slots, uint32_t* sizes,
                        uint32_t* crcs);
+/* mpg_deflate_encode with a Huffman code per unit (uniio.py:91-123): same arguments, units, tokens, slots and CRCs; the
+ * literal/length symbols of a unit are coded with canonical codes of at most 15 bits built from the unit's own counts
+ * (ties by symbol index, so a unit always gives the same bytes) in one dynamic block (BTYPE 10) closed by the empty
+ * stored block.  A unit is written in whichever of the dynamic, fixed and stored forms is shortest, so sizes[u] is
+ * never above what mpg_deflate_encode reports. */
+int mpg_deflate_encode_dynamic(mpg_stream_t stream, const void* src, size_t n_bytes, void* slots, uint32_t* sizes,
+                               uint32_t* crcs);
 /* compaction (uniio.py:91-123): out[sum(sizes[0..u)) ...] = the sizes[u] bytes of slot u, for u < n_units; nothing is
  * written at or beyond out + out_bytes. */
 int mpg_deflate_compact(mpg_stream_t stream, const void* slots, const uint32_t* sizes, size_t n_units, void* out,

@@ -139,6 +139,7 @@ PROTOTYPES = {
     # device codec of the .uni writer
     "mpg_deflate_ws_bytes": (_Z, [_Z]),
     "mpg_deflate_encode": (_I, [_P, _P, _Z, _P, _P, _P]),
+    "mpg_deflate_encode_dynamic": (_I, [_P, _P, _Z, _P, _P, _P]),
     "mpg_deflate_compact": (_I, [_P, _P, _P, _Z, _P, _Z]),
     # training step
     "mpg_conv2d_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P]),

@@ -709,10 +709,11 @@ def deflate_ws_bytes(n_bytes):
     return int(_lib.load().mpg_deflate_ws_bytes(int(n_bytes)))
 
 
-def deflate_encode(src, slots=None, sizes=None, crcs=None):
+def deflate_encode(src, slots=None, sizes=None, crcs=None, dynamic=False):
     """Deflate the bytes of `src` (contiguous float32 GPU tensor, at most DEFLATE_SLAB bytes, 16-byte aligned) in units
     of DEFLATE_UNIT bytes -> (slots uint8 [units * DEFLATE_SLOT], sizes int32 [units], crcs int32 [units]): unit u's
-    raw DEFLATE stream is slots[u * DEFLATE_SLOT:][:sizes[u]], crcs[u] (read as uint32) the CRC-32 of its input."""
+    raw DEFLATE stream is slots[u * DEFLATE_SLOT:][:sizes[u]], crcs[u] (read as uint32) the CRC-32 of its input.
+    dynamic: a Huffman code per unit (mpg_deflate_encode_dynamic) instead of the fixed one; same workspace."""
     lib = _lib.load()
     src = _dev(src, "src")
     n_bytes = src.numel() * 4
@@ -726,7 +727,8 @@ def deflate_encode(src, slots=None, sizes=None, crcs=None):
     _dev(slots, "slots", torch.uint8), _dev(sizes, "sizes", torch.int32), _dev(crcs, "crcs", torch.int32)
     if slots.numel() < units * DEFLATE_SLOT or sizes.numel() < units or crcs.numel() < units:
         raise _lib.MpgError("deflate_encode: workspace too small for %d units" % units)
-    _lib.check(lib.mpg_deflate_encode(_stream(), _ptr(src), n_bytes, _ptr(slots), _ptr(sizes), _ptr(crcs)), "mpg_deflate_encode")
+    name = "mpg_deflate_encode_dynamic" if dynamic else "mpg_deflate_encode"
+    _lib.check(getattr(lib, name)(_stream(), _ptr(src), n_bytes, _ptr(slots), _ptr(sizes), _ptr(crcs)), name)
     return slots, sizes, crcs
 
 

@@ -6,7 +6,8 @@ then the raw C-order payload [dimZ, dimY, dimX, channels] of float32 (scalar:
 elementType 1, 4 bytes/element; vec3: elementType 2, 12 bytes/element) or int32
 (elementType 0).  Files are always written as MNT3.  Large grids stream through a chunked, multi-threaded codec
 (below) whose output every gzip reader, the reference's included, decodes to the same bytes.  writeUniFromDevice can
-instead deflate the payload on the GPU (codec "device", further below): same bytes after inflation, larger files.
+instead deflate the payload on the GPU (codecs "device" and "device_dynamic", further below): same bytes after
+inflation; the fixed-code files are larger, those with a Huffman code per unit about the host codec's size.
 """
 import concurrent.futures
 import gzip
@@ -163,17 +164,19 @@ def writeUni(filename, header, content, level=None, threads=None, chunk_bytes=CH
 def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk_bytes=CHUNK_BYTES, codec=None):
     """writeUni for a float32 CUDA tensor: the volume is copied to pinned host memory chunk by chunk on a side stream
     while the previous chunks are being deflated, so neither the 537 MB device-to-host copy of a 512^3 volume nor its
-    compression waits for the other.  codec: "host" (zlib on the thread pool, the default) or "device" (deflated by
-    HIP kernels, only compressed bytes cross to the host; larger files, see _write_device); None = MPG_UNI_CODEC."""
+    compression waits for the other.  codec: "host" (zlib on the thread pool, the default), "device" (deflated by
+    HIP kernels with the fixed Huffman code, only compressed bytes cross to the host; larger files, see _write_device)
+    or "device_dynamic" (the same with a Huffman code per unit: files about as small as the host's);
+    None = MPG_UNI_CODEC."""
     import torch
     if level is None:
         level = int(os.environ.get("MPG_UNI_LEVEL", "6"))
     if codec is None:
         codec = os.environ.get("MPG_UNI_CODEC", "") or "host"
-    if codec not in ("host", "device"):
-        raise UniError("unknown codec %r: expected \"host\" or \"device\"" % (codec,))
-    if codec == "device":
-        return _write_device(filename, header, volume, level)
+    if codec not in ("host", "device", "device_dynamic"):
+        raise UniError("unknown codec %r: expected \"host\", \"device\" or \"device_dynamic\"" % (codec,))
+    if codec != "host":
+        return _write_device(filename, header, volume, level, dynamic=codec == "device_dynamic")
     flat = volume.contiguous().reshape(-1)
     if flat.dtype != torch.float32:
         flat = flat.float()
@@ -212,7 +215,8 @@ def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk
 
 # ----------------------------------------------------------------------------------------------
 # device codec.  ops.deflate_encode turns every UNIT bytes of the payload into a byte-aligned, non-final raw DEFLATE
-# stream (fixed Huffman code over word-granular runs, or a stored block) and the CRC-32 of those bytes; the streams of
+# stream (fixed Huffman code over word-granular runs, or a stored block; codec "device_dynamic": or the same tokens under
+# a Huffman code of the unit's own, whichever of the three is shortest) and the CRC-32 of those bytes; the streams of
 # consecutive units concatenate into a valid deflate body, which an empty final block closes.  The host only frames
 # members around bodies it never inflates: MEMBER_UNITS units each, the CRCs of their units combined.
 # ----------------------------------------------------------------------------------------------
@@ -299,13 +303,13 @@ def write_unit_members(out, bodies, sizes, crcs, lengths, member_units=MEMBER_UN
         raise UniError("unit sizes describe %d bytes, %d were given" % (at, len(bodies)))
 
 
-def _write_device(filename, header, volume, level):
-    """The device codec of writeUniFromDevice.  The payload is encoded in slabs of SLAB_BYTES on the caller's current
+def _write_device(filename, header, volume, level, dynamic=False):
+    """The device codecs of writeUniFromDevice (dynamic: a Huffman code per unit).  The payload is encoded in slabs of SLAB_BYTES on the caller's current
     stream (one slot workspace, reused in stream order); each slab's compacted streams go to pinned memory on a side
     stream while the next slab is being encoded, so only compressed bytes cross to the host."""
     import torch
     if not (isinstance(volume, torch.Tensor) and volume.is_cuda):
-        raise UniError("codec \"device\" needs a GPU tensor")
+        raise UniError("codec \"%s\" needs a GPU tensor" % ("device_dynamic" if dynamic else "device"))
     from . import ops
     flat = volume.contiguous().reshape(-1)
     if flat.dtype != torch.float32:
@@ -340,7 +344,7 @@ def _write_device(filename, header, volume, level):
             buf = bufs[k % 2]
             piece = flat[cuts[k]:cuts[k] + per]
             units = (piece.numel() * 4 + UNIT - 1) // UNIT
-            ops.deflate_encode(piece, slots, buf["meta"][0], buf["meta"][1])
+            ops.deflate_encode(piece, slots, buf["meta"][0], buf["meta"][1], dynamic=dynamic)
             ops.deflate_compact(slots, buf["meta"][0], units, buf["packed"])
             buf["done"].record(main)
             return units

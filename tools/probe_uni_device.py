@@ -1,7 +1,8 @@
-"""f3, device codec: seconds per volume through uniio.writeUniFromDevice with codec "host" (zlib level 6 on the thread
-pool) and codec "device" (HIP deflate kernels), alternating in one process into one directory: two warm-up writes of
-each, then five timed ones; file sizes, readUni seconds, and the encode + compaction kernels' own time from device
-events.  usage: python tools/probe_uni_device.py [n ...]   (volumes of n^3, default 256 512)"""
+"""f3, device codecs: seconds per volume through uniio.writeUniFromDevice with codec "host" (zlib level 6 on the thread
+pool), codec "device" (HIP deflate kernels, fixed Huffman code) and codec "device_dynamic" (the same with a Huffman code
+per unit), alternating in one process into one directory: two warm-up writes of each, then five timed ones; file sizes,
+readUni seconds, and the encode + compaction kernels' own time from device events for both device codecs.
+usage: python tools/probe_uni_device.py [n ...]   (volumes of n^3, default 256 512)"""
 import os, statistics, sys, tempfile, time
 sys.path.insert(0, ".")
 import numpy as np, torch
@@ -15,7 +16,10 @@ def fmt(ts):
     return "%.3f (%.3f .. %.3f) s" % (statistics.median(ts), min(ts), max(ts))
 
 
-def kernels_ms(dev, reps=5):
+CODECS = ("host", "device", "device_dynamic")
+
+
+def kernels_ms(dev, dynamic, reps=5):
     """device-event time of encode + compaction over the whole payload, slab by slab as the writer runs them"""
     flat = dev.reshape(-1)
     per = uniio.SLAB_BYTES // 4
@@ -31,7 +35,7 @@ def kernels_ms(dev, reps=5):
         for c in range(0, flat.numel(), per):
             piece = flat[c:c + per]
             e[0].record()
-            ops.deflate_encode(piece, slots, sizes, crcs)
+            ops.deflate_encode(piece, slots, sizes, crcs, dynamic=dynamic)
             e[1].record()
             ops.deflate_compact(slots, sizes, (piece.numel() * 4 + uniio.UNIT - 1) // uniio.UNIT, packed)
             e[2].record()
@@ -52,23 +56,24 @@ def main():
         vol[vol < 5e-4] = 0
         dev = torch.as_tensor(vol).cuda()
         h = uniio.make_header(n, n, n)
-        paths = {c: os.path.join(d, "v_%s.uni" % c) for c in ("host", "device")}
-        times = {"host": [], "device": []}
+        paths = {c: os.path.join(d, "v_%s.uni" % c) for c in CODECS}
+        times = {c: [] for c in CODECS}
         for k in range(7):
-            for c in ("host", "device"):
+            for c in CODECS:
                 torch.cuda.synchronize(); t = time.perf_counter()
                 uniio.writeUniFromDevice(paths[c], h, dev, level=6, codec=c)
                 if k >= 2:
                     times[c].append(time.perf_counter() - t)
         mb = {c: os.path.getsize(paths[c]) / 1e6 for c in paths}
         print("%d^3 (%.0f MB payload, %.0f %% zero words)" % (n, vol.nbytes / 1e6, 100.0 * float((vol == 0).mean())))
-        for c in ("host", "device"):
+        for c in CODECS:
             t = time.perf_counter(); hh, a = uniio.readUni(paths[c]); tr = time.perf_counter() - t
             assert hh == h and np.array_equal(a[..., 0].view(np.uint32), vol.view(np.uint32))
-            print("  codec %-6s write %s, file %.2f MB, readUni %.3f s" % (c, fmt(times[c]), mb[c], tr), flush=True)
-        enc, tot = kernels_ms(dev)
-        print("  device kernels: encode %.3f ms (%.0f GB/s of payload), encode + compaction %.3f ms; file size ratio device / host %.3f"
-              % (enc, vol.nbytes / enc / 1e6, tot, mb["device"] / mb["host"]), flush=True)
+            print("  codec %-14s write %s, file %.2f MB, readUni %.3f s" % (c, fmt(times[c]), mb[c], tr), flush=True)
+        for c in CODECS[1:]:
+            enc, tot = kernels_ms(dev, c == "device_dynamic")
+            print("  %s kernels: encode %.3f ms (%.0f GB/s of payload), encode + compaction %.3f ms; file size ratio %s / host %.3f"
+                  % (c, enc, vol.nbytes / enc / 1e6, tot, c, mb[c] / mb["host"]), flush=True)
 
 
 main()
