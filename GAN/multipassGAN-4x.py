@@ -62,7 +62,7 @@ for name, default in [
         ("simLowHeight", 64), ("overlappedpixel", 3), ("startIndex", 0), ("useAvgDepool", False), ("avgMode", 0),
         ("velScale", 1.0), ("upsamplingMode", 2), ("upsampledData", False), ("sliceMode", 0), ("interpMode", 1),
         ("genUni", False), ("setVelZero", False), ("upsampleFirst", True), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("deviceTiles", 1), ("uniCodec", 0), ("deviceLoader", 0), ("previews", 0)]:
+        ("deviceTiles", 1), ("uniCodec", 0), ("deviceLoader", 0), ("previews", 0), ("uniIndex", 0), ("deviceRead", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -310,6 +310,12 @@ if upsampling_mode not in (0, 1, 2, 3) or int(P["dataDim"]) != 2 or int(P["useAv
 if upsampling_mode == 0 and not upsampled_data:
     print("ERROR: upsamplingMode 0 refines the volumes of density_low_2x2x1_%04d.uni (upsampledData 1)")
     exit(1)
+# extensions: uniIndex 1 = the written volumes record their unit sizes (device codecs), which lets deviceRead 1 = the
+# previous network's volume of each frame is read inside the frame loop and inflated on the GPU (uniio.readUniToDevice)
+uni_index, device_read = int(P["uniIndex"]), int(P["deviceRead"])
+if uni_index and not int(P["uniCodec"]):
+    print("ERROR: uniIndex 1 needs the device codec (uniCodec 1 or 2)")
+    exit(1)
 simSizeHigh = simSizeLow * upRes
 n_ch = 4 if useVelocities else 1
 device = "cuda:0"
@@ -321,11 +327,11 @@ floader = FDL.FluidDataLoader(print_info=1, base_path=packedSimPath, base_path_y
                               multi_file_list=mfl, multi_file_list_y=["density"])
 x, _, _ = floader.get()
 x_2 = None
-if upsampled_data:
+prev_name = {3: "density_low_1x1_%04d.uni", 0: "density_low_2x2x1_%04d.uni"}.get(upsampling_mode, "density_low_2x2_%04d.uni")
+if upsampled_data and not device_read:
     # the previous network's volumes (4x.py:180-185)
     fl2 = FDL.FluidDataLoader(print_info=1, base_path=packedSimPath, numpy_seed=int(P["randSeed"]),
-                              filename={3: "density_low_1x1_%04d.uni", 0: "density_low_2x2x1_%04d.uni"}.get(
-                                  upsampling_mode, "density_low_2x2_%04d.uni"),
+                              filename=prev_name,
                               filename_index_min=frame_min, oldNamingScheme=False,
                               filename_index_max=frame_max, indices=[fromSim], data_fraction=1.0, multi_file_list=["density"])
     x_2, _, _ = fl2.get()
@@ -346,6 +352,15 @@ print('*****OUTPUT ONLY*****')
 s = simSizeHigh
 previews = int(P["previews"])                # extension: 1 = source_%04d.png per frame into test_path (4x.py:1134,1146)
 pictures = 0
+
+
+def previous_volume(i, layerno):
+    """[z, y, x] of the previous network's volume for frame layerno"""
+    if device_read:
+        return uniio.readUniToDevice(os.path.join(packedSimPath, "sim_%04d/" % fromSim, prev_name % layerno), device)[1][..., 0]
+    return torch.as_tensor(np.ascontiguousarray(x_2[i][..., 0])).to(device)
+
+
 if previews:
     from mpgan_amd import preview
     os.makedirs(basePath + 'test_%04d/' % load_model_test, exist_ok=True)
@@ -363,7 +378,7 @@ for layerno in range(frame_min, frame_max):
         name = 'density_low_2x2x1_%04d.uni'
         slices = simSizeLow
     elif upsampling_mode == 0:
-        v1 = torch.as_tensor(np.ascontiguousarray(x_2[i][..., 0])).to(device)
+        v1 = previous_volume(i, layerno)
         vol = multipass.upsample_pass_4x(gen, low, v1, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni),
                                          previews=sink)
         name = 'density_low_1x1x1_%04d.uni'
@@ -378,7 +393,7 @@ for layerno in range(frame_min, frame_max):
         name = 'density_low_2x2_%04d.uni'
     else:
         # upsamplingMode 1: planes (z,y) along x -> density_low_1x1; upsamplingMode 3: planes (z,x) along y -> density_low_0x0
-        v1 = torch.as_tensor(np.ascontiguousarray(x_2[i][..., 0])).to(device)
+        v1 = previous_volume(i, layerno)
         vol = multipass.refine_pass_4x(gen, low, v1, upRes, mode=upsampling_mode, batch=8, vel_scale=velScale,
                                        apply_cutoff=bool(generateUni), previews=sink)
         name = 'density_low_1x1_%04d.uni' if upsampling_mode == 1 else 'density_low_0x0_%04d.uni'
@@ -391,7 +406,7 @@ for layerno in range(frame_min, frame_max):
         head['dimX'] = head['dimY'] = simSizeHigh
         head['dimZ'] = slices                                                # 2x2x1: the slices the file holds (see above)
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/' % fromSim + name % layerno, head, vol,
-                                 codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"))
+                                 codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"), unit_index=bool(uni_index))
     print('')
 print('Test finished, %d volumes written to %s.' % (frame_max - frame_min, packedSimPath))
 if previews:

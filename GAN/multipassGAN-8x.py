@@ -59,7 +59,7 @@ for name, default in [
         ("stageIter", 25000), ("decayIter", 25000), ("maxFms", 256), ("use_wgan_gp", False), ("use_res_net", False),
         ("use_mb_stddev", False), ("deviceTiles", 1), ("use_LSGAN", False), ("startFms", 512), ("filterSize", 3), ("outNNTestNo", 17),
         ("firstNNArch", False), ("gDrop", False), ("add_adj_idcs", False), ("gpu", 2), ("synthWeights", 0), ("prec", "2"), ("trainPrec", "3"),
-        ("uniCodec", 0), ("deviceLoader", 0), ("previews", 0)]:
+        ("uniCodec", 0), ("deviceLoader", 0), ("previews", 0), ("uniIndex", 0), ("deviceRead", 0)]:
     P[name] = ph.getParam(name, default)
 ph.checkUnusedParams()
 
@@ -85,6 +85,11 @@ def output_main():
     ta = int(P["transposeAxis"])
     if ta not in (0, 1, 2, 3):
         fail("transposeAxis %d (0..3)" % ta)
+    # extensions: uniIndex 1 = the written volumes record their unit sizes (device codecs), which lets deviceRead 1 = the
+    # previous network's volume of each frame is read inside the frame loop and inflated on the GPU (uniio.readUniToDevice)
+    uni_index, device_read = int(P["uniIndex"]), int(P["deviceRead"])
+    if uni_index and not int(P["uniCodec"]):
+        fail("uniIndex 1 needs the device codec (uniCodec 1 or 2)")
     up, sim = int(P["upRes"]), int(P["simSize"])
     s = sim * up
     base, sims = P["basePath"], P["packedSimPath"]
@@ -101,8 +106,8 @@ def output_main():
     x_3d, _, _ = fl.get()
     x_3d[:, :, :, :, 1:4] = float(P["velScale"]) * x_3d[:, :, :, :, 1:4]                     # :361
     x_2 = None
-    if upsampled:
-        prev_name = ("density_low_t%04d_2x2" if mode == 1 else "density_low_t%04d_1x1") % int(P["outNNTestNo"]) + "_%04d.uni"
+    prev_name = ("density_low_t%04d_2x2" if mode == 1 else "density_low_t%04d_1x1") % int(P["outNNTestNo"]) + "_%04d.uni"
+    if upsampled and not device_read:
         fl2 = FDL.FluidDataLoader(print_info=0, base_path=sims, numpy_seed=int(P["randSeed"]), filename=prev_name,
                                   filename_index_min=f0, oldNamingScheme=False, filename_index_max=f1, indices=[from_sim],
                                   data_fraction=1.0, multi_file_list=["density"])
@@ -139,7 +144,10 @@ def output_main():
         print(layerno)
         t0 = time.time()
         low = torch.as_tensor(np.ascontiguousarray(x_3d[layerno - f0])).to("cuda:0")
-        prev = None if x_2 is None else torch.as_tensor(np.ascontiguousarray(x_2[layerno - f0][..., 0])).to("cuda:0")
+        if upsampled and device_read:
+            prev = uniio.readUniToDevice(os.path.join(sims, "sim_%04d/" % from_sim, prev_name % layerno), "cuda:0")[1][..., 0]
+        else:
+            prev = None if x_2 is None else torch.as_tensor(np.ascontiguousarray(x_2[layerno - f0][..., 0])).to("cuda:0")
         sink = preview.PreviewSink(test_path, layerno, int(P["tileSize"]) * up) if previews else None
         vol = multipass.single_pass_8x(gen, low, prev, up, ta, batch=2, apply_cutoff=gen_uni, previews=sink)
         torch.cuda.synchronize()
@@ -150,7 +158,8 @@ def output_main():
             head = dict(head_0)
             head['dimX'] = head['dimY'] = head['dimZ'] = s
             uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol,
-                                     codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"))
+                                     codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"),
+                                     unit_index=bool(uni_index))
     print('Test finished, %d volumes written to %s.' % (f1 - f0, sims))
     if previews:
         print('%d pngs written to %s.' % (pictures, test_path))

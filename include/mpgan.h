@@ -335,6 +335,19 @@ int mpg_deflate_encode_dynamic(mpg_stream_t stream, const void* src, size_t n_by
  * written at or beyond out + out_bytes. */
 int mpg_deflate_compact(mpg_stream_t stream, const void* slots, const uint32_t* sizes, size_t n_units, void* out,
                         size_t out_bytes);
+/* The way back: replaces the gzip.open(...).read() of the reference reader (tools_wscale/uniio.py:81-88) for files whose
+ * members record their unit sizes (uniio.unit_index).  Decodes n_units = ceil(n_bytes / MPG_DEFLATE_UNIT) unit streams in
+ * parallel.  offsets and sizes are HOST arrays: unit u's stream is the sizes[u] bytes at packed + offsets[u] (any
+ * alignment).  packed (device, 16-byte aligned, packed_bytes a multiple of 16) is read only in the 16-byte lines a stream
+ * touches.  The call fails with MPG_ERR_ARG before anything is launched if a stream leaves packed_bytes; it uploads the two
+ * arrays in stream order and returns once they are on the device (the kernel may still be running).
+ * Unit u's bytes go to out + u * MPG_DEFLATE_UNIT (device, 16-byte aligned; the last unit takes the rest of n_bytes, a
+ * positive multiple of 4), their CRC-32 to crcs[u], and to status[u] 0 = decoded, 1 = valid DEFLATE outside the token
+ * language of mpg_deflate_encode (another distance, a final block, output that is not word-granular), 2 = corrupt
+ * (bad code, LEN / NLEN, input or output that ends early or late).  With a non-zero status the unit's output and CRC are
+ * unspecified, but nothing outside the unit's output range is written, whatever the bytes say. */
+int mpg_inflate_units(mpg_stream_t stream, const void* packed, size_t packed_bytes, const uint64_t* offsets,
+                      const uint32_t* sizes, size_t n_units, void* out, size_t n_bytes, uint32_t* crcs, uint32_t* status);
 
 /* ------------------------------------------------------------------------
  * Training step: what tf.gradients produces for

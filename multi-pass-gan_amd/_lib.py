@@ -141,6 +141,7 @@ PROTOTYPES = {
     "mpg_deflate_encode": (_I, [_P, _P, _Z, _P, _P, _P]),
     "mpg_deflate_encode_dynamic": (_I, [_P, _P, _Z, _P, _P, _P]),
     "mpg_deflate_compact": (_I, [_P, _P, _P, _Z, _P, _Z]),
+    "mpg_inflate_units": (_I, [_P, _P, _Z, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), _Z, _P, _Z, _P, _P]),
     # training step
     "mpg_conv2d_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "mpg_conv2d_wgrad_mfma_ws_bytes": (_Z, [_I, _I, _I, _I, _I]),

@@ -21,6 +21,7 @@
 // shorter).  tests/deflate_dynamic_ref.py restates all of this in Python, and the kernel is held to it byte for byte.
 #include <cstdint>
 
+#include "mpgan_crc.h"
 #include "mpgan_internal.h"
 
 namespace {
@@ -94,17 +95,8 @@ struct HeaderWriter {
     }
 };
 
-constexpr uint32_t POLY = 0xEDB88320u;         // gzip CRC-32, bit-reflected
-
-// a * b mod P in the reflected representation (bit 31 is x^0), as zlib's multmodp
-constexpr uint32_t gf_mul(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? POLY : 0u);
-    }
-    return p;
-}
+using mpg_crc::gf_mul;
+using mpg_crc::POLY;                           // gzip CRC-32, bit-reflected
 
 struct Tables {
     uint32_t crc[4][256];      // slice-by-4: crc[k][b] = register after byte b and k zero bytes
@@ -113,13 +105,7 @@ struct Tables {
 
 constexpr Tables make_tables() {
     Tables t{};
-    for (uint32_t b = 0; b < 256; ++b) {
-        uint32_t c = b;
-        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? POLY : 0u);
-        t.crc[0][b] = c;
-    }
-    for (int k = 1; k < 4; ++k)
-        for (int b = 0; b < 256; ++b) t.crc[k][b] = (t.crc[k - 1][b] >> 8) ^ t.crc[0][t.crc[k - 1][b] & 255u];
+    mpg_crc::fill_slice_tables(t.crc);
     uint32_t step = 0x40000000u;                                    // x^1
     for (int bits = 1; bits < 32 * WPT; bits *= 2) step = gf_mul(step, step);
     t.xp[0] = 0x80000000u;                                          // x^0

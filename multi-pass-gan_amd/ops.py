@@ -746,6 +746,41 @@ def deflate_compact(slots, sizes, units, out=None):
     return out
 
 
+def inflate_units(packed, offsets, sizes, n_bytes, out=None):
+    """Decode the unit streams of the device .uni codecs on the GPU (tools_wscale/uniio.py:81-88 reads with gzip): unit u
+    is the sizes[u] bytes at packed[offsets[u]:] (packed: uint8 GPU tensor; offsets, sizes: host sequences, one entry per
+    DEFLATE_UNIT of the n_bytes of output) -> (out uint8 [n_bytes], crcs int32 [units], status int32 [units]): crcs[u]
+    (read as uint32) is the CRC-32 of unit u's bytes, status[u] 0 = decoded, 1 = outside the writer's token language,
+    2 = corrupt.  Streams that leave `packed` are refused before anything is launched."""
+    import numpy as np
+    lib = _lib.load()
+    packed = _dev(packed, "packed", torch.uint8)
+    n_bytes = int(n_bytes)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+    units = (n_bytes + DEFLATE_UNIT - 1) // DEFLATE_UNIT
+    if len(offsets) != units or len(sizes) != units:
+        raise _lib.MpgError("inflate_units: %d offsets and %d sizes for %d units" % (len(offsets), len(sizes), units))
+    packed_bytes = packed.numel()
+    if units and int((offsets + sizes).max()) > packed_bytes:
+        raise _lib.MpgError("inflate_units: a stream leaves the %d packed bytes" % packed_bytes)
+    if packed_bytes % 16 or packed.data_ptr() % 16:                # the kernel reads whole 16-byte lines
+        padded = torch.zeros((packed_bytes + 15) // 16 * 16, dtype=torch.uint8, device=packed.device)
+        padded[:packed_bytes].copy_(packed)
+        packed = padded
+    if out is None:
+        out = torch.empty(n_bytes, dtype=torch.uint8, device=packed.device)
+    _dev(out, "out", torch.uint8)
+    if out.numel() != n_bytes:
+        raise _lib.MpgError("inflate_units: out holds %d bytes, not %d" % (out.numel(), n_bytes))
+    crcs = torch.empty(units, dtype=torch.int32, device=packed.device)
+    status = torch.empty(units, dtype=torch.int32, device=packed.device)
+    _lib.check(lib.mpg_inflate_units(_stream(), _ptr(packed), packed.numel(), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                     sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), units, _ptr(out), n_bytes, _ptr(crcs),
+                                     _ptr(status)), "mpg_inflate_units")
+    return out, crcs, status
+
+
 # ---------------------------------------------------------------- preview images of the inference drivers
 def _volume3(vol, what):
     vol = _dev(vol, "vol")

@@ -103,8 +103,13 @@ def _member_sizes(raw):
     return sizes
 
 
+def _body_start(raw, at):
+    """offset of the deflate body of the member at `at`: behind the fixed header, XLEN and the extra field"""
+    return at + 12 + struct.unpack_from("<H", raw, at + 10)[0]
+
+
 def _inflate_member(raw, at, size):
-    data = zlib.decompress(raw[at + _MEMBER_HEAD:at + size - 8], -15)
+    data = zlib.decompress(raw[_body_start(raw, at):at + size - 8], -15)
     crc, isize = struct.unpack_from("<II", raw, at + size - 8)
     if (zlib.crc32(data) & 0xffffffff) != crc or (len(data) & 0xffffffff) != isize:
         raise UniError("corrupt gzip member at offset %d" % at)
@@ -161,13 +166,14 @@ def writeUni(filename, header, content, level=None, threads=None, chunk_bytes=CH
                 out.write(member(i))
 
 
-def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk_bytes=CHUNK_BYTES, codec=None):
+def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk_bytes=CHUNK_BYTES, codec=None, unit_index=None):
     """writeUni for a float32 CUDA tensor: the volume is copied to pinned host memory chunk by chunk on a side stream
     while the previous chunks are being deflated, so neither the 537 MB device-to-host copy of a 512^3 volume nor its
     compression waits for the other.  codec: "host" (zlib on the thread pool, the default), "device" (deflated by
     HIP kernels with the fixed Huffman code, only compressed bytes cross to the host; larger files, see _write_device)
     or "device_dynamic" (the same with a Huffman code per unit: files about as small as the host's);
-    None = MPG_UNI_CODEC."""
+    None = MPG_UNI_CODEC.  unit_index (device codecs only): record the unit sizes in every member, see write_unit_members;
+    None = MPG_UNI_INDEX ("1" = on), off when unset."""
     import torch
     if level is None:
         level = int(os.environ.get("MPG_UNI_LEVEL", "6"))
@@ -175,8 +181,12 @@ def writeUniFromDevice(filename, header, volume, level=None, threads=None, chunk
         codec = os.environ.get("MPG_UNI_CODEC", "") or "host"
     if codec not in ("host", "device", "device_dynamic"):
         raise UniError("unknown codec %r: expected \"host\", \"device\" or \"device_dynamic\"" % (codec,))
+    if unit_index is None:
+        unit_index = os.environ.get("MPG_UNI_INDEX", "") == "1"
     if codec != "host":
-        return _write_device(filename, header, volume, level, dynamic=codec == "device_dynamic")
+        return _write_device(filename, header, volume, level, dynamic=codec == "device_dynamic", unit_index=bool(unit_index))
+    if unit_index:
+        raise UniError("the unit index needs a device codec: codec \"host\" writes no units")
     flat = volume.contiguous().reshape(-1)
     if flat.dtype != torch.float32:
         flat = flat.float()
@@ -226,6 +236,8 @@ SLAB_BYTES = 64 << 20             # payload bytes per encode call (MPG_DEFLATE_S
 MEMBER_UNITS = CHUNK_BYTES // UNIT    # units per gzip member: members as large as the host codec's, so readUni's
 #                                       thread pool gets the same work items either way
 _FINAL_BLOCK = b"\x03\x00"        # BFINAL 1, BTYPE 01, end-of-block: an empty last block
+_UNIT_SUBFIELD = b"MU"            # second extra-field subfield, opt-in: uint32 stream length of every unit of the member
+MAX_INDEX_UNITS = 16380           # 8 + 4 + 4 * k <= 65535, the most an extra field holds
 _CRC_POLY = 0xEDB88320
 
 
@@ -276,17 +288,25 @@ def crc32_combine(crcs, lengths):
     return crc
 
 
-def _frame_member(body_len, crc, isize):
-    """(head, tail) of a gzip member around a deflate body of body_len bytes that lacks its final block"""
-    total = _MEMBER_HEAD + body_len + len(_FINAL_BLOCK) + 8
-    head = struct.pack("<BBBBIBBH", 0x1f, 0x8b, 8, 4, 0, 0, 255, 8) + _SUBFIELD + struct.pack("<HI", 4, total)
+def _frame_member(body_len, crc, isize, unit_sizes=None):
+    """(head, tail) of a gzip member around a deflate body of body_len bytes that lacks its final block.  unit_sizes:
+    the stream lengths of the member's units, recorded in an MU subfield behind the MP one (the unit index)"""
+    index = b""
+    if unit_sizes is not None:
+        if len(unit_sizes) > MAX_INDEX_UNITS:
+            raise UniError("%d units in one member: the unit index holds at most %d" % (len(unit_sizes), MAX_INDEX_UNITS))
+        index = _UNIT_SUBFIELD + struct.pack("<H%dI" % len(unit_sizes), 4 * len(unit_sizes), *unit_sizes)
+    total = _MEMBER_HEAD + len(index) + body_len + len(_FINAL_BLOCK) + 8
+    head = struct.pack("<BBBBIBBH", 0x1f, 0x8b, 8, 4, 0, 0, 255, 8 + len(index)) + _SUBFIELD + struct.pack("<HI", 4, total) + index
     return head, _FINAL_BLOCK + struct.pack("<II", crc & 0xffffffff, isize & 0xffffffff)
 
 
-def write_unit_members(out, bodies, sizes, crcs, lengths, member_units=MEMBER_UNITS):
+def write_unit_members(out, bodies, sizes, crcs, lengths, member_units=MEMBER_UNITS, unit_index=False):
     """Write gzip members for device-encoded units to the file object `out`.  bodies: the unit streams back to back
     (bytes-like), sizes[u] the stream length of unit u, crcs[u] / lengths[u] the CRC-32 and byte count of its input.
-    Every member holds up to member_units units and carries the MP size subfield and a CRC-32 / ISIZE trailer."""
+    Every member holds up to member_units units and carries the MP size subfield and a CRC-32 / ISIZE trailer.
+    unit_index: every member also records the stream lengths of its units (MU subfield, 4 + 4 * units bytes), which lets
+    readUniToDevice inflate the units in parallel on the GPU; every gzip reader skips the subfield."""
     bodies = memoryview(bodies).cast("B")
     sizes = [int(x) for x in sizes]
     lengths = [int(x) for x in lengths]
@@ -294,7 +314,8 @@ def write_unit_members(out, bodies, sizes, crcs, lengths, member_units=MEMBER_UN
     for a in range(0, len(sizes), member_units):
         b = min(a + member_units, len(sizes))
         body_len = sum(sizes[a:b])
-        head, tail = _frame_member(body_len, crc32_combine(crcs[a:b], lengths[a:b]), sum(lengths[a:b]))
+        head, tail = _frame_member(body_len, crc32_combine(crcs[a:b], lengths[a:b]), sum(lengths[a:b]),
+                                   sizes[a:b] if unit_index else None)
         out.write(head)
         out.write(bodies[at:at + body_len])
         out.write(tail)
@@ -303,7 +324,7 @@ def write_unit_members(out, bodies, sizes, crcs, lengths, member_units=MEMBER_UN
         raise UniError("unit sizes describe %d bytes, %d were given" % (at, len(bodies)))
 
 
-def _write_device(filename, header, volume, level, dynamic=False):
+def _write_device(filename, header, volume, level, dynamic=False, unit_index=False):
     """The device codecs of writeUniFromDevice (dynamic: a Huffman code per unit).  The payload is encoded in slabs of SLAB_BYTES on the caller's current
     stream (one slot workspace, reused in stream order); each slab's compacted streams go to pinned memory on a side
     stream while the next slab is being encoded, so only compressed bytes cross to the host."""
@@ -364,8 +385,129 @@ def _write_device(filename, header, volume, level, dynamic=False):
                 side.synchronize()
             nbytes = min(per, n - cuts[k]) * 4
             lengths = [UNIT] * (units - 1) + [nbytes - UNIT * (units - 1)]
-            write_unit_members(out, buf["host"][:total].numpy(), meta[0], meta[1], lengths)
+            write_unit_members(out, buf["host"][:total].numpy(), meta[0], meta[1], lengths, unit_index=unit_index)
         # `flat`, the workspace and the pinned buffers are released only now: every copy has completed
+
+
+# ----------------------------------------------------------------------------------------------
+# device reader.  With the unit index a reader knows where every unit stream starts without inflating anything, and the
+# streams are independent, so ops.inflate_units decodes all units of a file in one launch.  The host keeps what it is good
+# at: the member walk, the 292-byte header member, and the trailer check (unit CRCs combined per member).
+# ----------------------------------------------------------------------------------------------
+def unit_index(raw):
+    """[(body offset, [unit stream sizes])] for the payload members (all but the first) of the bytes of a .uni file written
+    with unit_index=True; None if the file has no member sizes or any payload member lacks the MU subfield"""
+    raw = memoryview(raw).cast("B")
+    sizes = _member_sizes(raw)
+    if sizes is None or len(sizes) < 2:
+        return None
+    out, at = [], sizes[0]
+    for size in sizes[1:]:
+        xlen = struct.unpack_from("<H", raw, at + 10)[0]
+        if xlen < 12 or bytes(raw[at + 20:at + 22]) != _UNIT_SUBFIELD:
+            return None
+        (nbytes,) = struct.unpack_from("<H", raw, at + 22)
+        if nbytes % 4 or 12 + nbytes != xlen or at + 12 + xlen + len(_FINAL_BLOCK) + 8 > at + size:
+            return None
+        out.append((at + 12 + xlen, list(struct.unpack_from("<%dI" % (nbytes // 4), raw, at + 24))))
+        at += size
+    return out
+
+
+def _device_plan(raw):
+    """(header, dims, offsets, sizes, members) for the device path of readUniToDevice, or a string: why it does not apply.
+    members: (first unit, one past the last, CRC-32, ISIZE) of every payload member"""
+    member_sizes = _member_sizes(raw)
+    if member_sizes is None:
+        return "no member sizes: not written by this package"
+    index = unit_index(raw)
+    if index is None:
+        return "no unit index"
+    first_xlen = struct.unpack_from("<H", raw, 10)[0]
+    if first_xlen != 8:
+        return "the first member is not a plain header member"
+    try:
+        first = _inflate_member(raw, 0, member_sizes[0])
+    except (UniError, zlib.error):
+        return "the header member does not inflate"
+    if len(first) != 4 + HEADER_BYTES:
+        return "the first member is not exactly the header"
+    try:
+        head = _parse_header(io.BytesIO(first))
+    except UniError:
+        return "unreadable header"
+    et, bpe = head["elementType"], head["bytesPerElement"]
+    if not ((bpe == 12 and et == 2) or (bpe == 4 and et == 1)):
+        return "element type %d with %d bytes per element" % (et, bpe)
+    dims = [head["dimZ"], head["dimY"], head["dimX"], 3 if et == 2 else 1]
+    if head["dimT"] > 1:
+        dims = [head["dimT"]] + dims
+    n_bytes = 4 * int(np.prod(dims, dtype=np.int64))
+    offsets, sizes, members = [], [], []
+    at = member_sizes[0]
+    for (body, units), msize in zip(index, member_sizes[1:]):
+        if body + sum(units) + len(_FINAL_BLOCK) + 8 != at + msize:
+            return "a unit index disagrees with its member's size"
+        crc, isize = struct.unpack_from("<II", raw, at + msize - 8)
+        members.append((len(sizes), len(sizes) + len(units), crc, isize))
+        for n in units:
+            offsets.append(body)
+            body += n
+        sizes += units
+        at += msize
+    if n_bytes < 4 or len(sizes) != (n_bytes + UNIT - 1) // UNIT:
+        return "%d units for %d payload bytes" % (len(sizes), n_bytes)
+    return head, dims, offsets, sizes, members
+
+
+def readUniToDevice(filename, device="cuda:0", info=None):
+    """readUni with the volume left on the GPU -> (header dict, float32 CUDA tensor [Z,Y,X,C]).  A file written with
+    unit_index=True goes up as it is and ops.inflate_units decodes its units in parallel; the member trailers (CRC-32, ISIZE)
+    are checked on the host against the unit CRCs the kernel returns.  Every other file, and every file for which the device
+    decode reports anything but success, is read by readUni (which raises UniError for a corrupt one) and uploaded.
+    info: a dict that receives "path" ("device" or "host") and "reason"."""
+    import torch
+    dev = torch.device(device)
+
+    def note(path, reason):
+        if isinstance(info, dict):
+            info["path"], info["reason"] = path, reason
+
+    nbytes = os.path.getsize(filename)
+    pinned = torch.empty((nbytes + 15) // 16 * 16, dtype=torch.uint8, pin_memory=True)   # whole 16-byte lines for the kernel
+    with open(filename, "rb") as f:
+        got = f.readinto(memoryview(pinned.numpy())[:nbytes])
+    raw = memoryview(pinned.numpy())[:got]
+    pinned[got:] = 0
+    plan = _device_plan(raw)
+    reason = plan if isinstance(plan, str) else None
+    if reason is None:
+        head, dims, offsets, sizes, members = plan
+        from . import ops
+        with torch.cuda.device(dev):
+            packed = pinned.to(dev, non_blocking=True)
+            n_bytes = 4 * int(np.prod(dims, dtype=np.int64))
+            out, crcs, status = ops.inflate_units(packed, offsets, sizes, n_bytes)
+            meta = torch.stack([crcs, status]).cpu().numpy().view(np.uint32)        # waits for the decode
+        if meta[1].any():
+            reason = "unit %d: decode status %d" % (int(np.flatnonzero(meta[1])[0]), int(meta[1][np.flatnonzero(meta[1])[0]]))
+        else:
+            lengths = [UNIT] * (len(sizes) - 1) + [n_bytes - UNIT * (len(sizes) - 1)]
+            for a, b, crc, isize in members:
+                if crc32_combine(meta[0][a:b], lengths[a:b]) != crc or (sum(lengths[a:b]) & 0xffffffff) != isize:
+                    reason = "member of units %d..%d: CRC-32 or ISIZE mismatch" % (a, b - 1)
+                    break
+        if reason is None:
+            note("device", "")
+            return head, out.view(torch.float32).reshape(dims)
+    note("host", reason)
+    try:
+        head, content = readUni(filename)
+    except zlib.error as e:
+        raise UniError("corrupt deflate data in %s: %s" % (filename, e))
+    host = torch.empty(content.shape, dtype=torch.int32 if content.dtype == np.int32 else torch.float32, pin_memory=True)
+    np.copyto(host.numpy(), content)
+    return head, host.to(dev)
 
 
 def make_header(dim_x, dim_y, dim_z, vec3=False, info=b"", timestamp=0, grid_type=1):
