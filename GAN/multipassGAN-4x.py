@@ -25,6 +25,15 @@ Training mode (``out 0``) trains the first network (upsamplingMode 2, upsampledD
 the reference loop does (:196-300 data, :728-902 graph, :1300-1360 iteration): FluidDataLoader slices ->
 TileCreator tiles (augmentation, coherent triples) -> ``train.Trainer4x`` (spatial + temporal
 discriminator) -> ``basePath/test_%04d/model_%04d.ckpt.npz``.
+
+``useVorticities 1`` (the tempoGAN vorticity input, addVorticity :491-499,1026-1029): every generator takes three more
+input channels behind all others (:344), computed from the velocity channels of each tile or slice by
+``mpgan_amd/vorticity.py`` -- the HIP kernel mpg_vorticity_append on device tiles, its numpy restatement on host tiles
+(``deviceTiles 0``).  Deviations: (a) without ``useVelocities 1`` it is refused with a message (the reference widens the
+network and feeds nothing); (b) the output modes compute the channels on the slice batch exactly as the network
+receives it (the reference only counts them there, so a network trained with them cannot be run); (c) the temporal
+batches of the second network (upsamplingMode 1) are taken at the tile's own size (:493 reshapes them with tileSizeLow);
+upsamplingMode 0 has no vorticity channels.
 """
 import os
 import sys
@@ -36,7 +45,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 import mpgan_amd  # noqa: E402,F401
-from mpgan_amd import checkpoint, heldout, multipass, ops, uniio  # noqa: E402
+from mpgan_amd import checkpoint, heldout, multipass, ops, uniio, vorticity  # noqa: E402
 from mpgan_amd import fluiddataloader as FDL  # noqa: E402
 from mpgan_amd import paramhelpers as ph  # noqa: E402
 
@@ -71,6 +80,10 @@ basePath, packedSimPath = P["basePath"], P["packedSimPath"]
 simSizeLow, upRes = int(P["simSize"]), int(P["upRes"])
 fromSim, frame_min, frame_max = int(P["fromSim"]), int(P["frame_min"]), int(P["frame_max"])
 useVelocities, velScale = int(P["useVelocities"]), float(P["velScale"])
+useVorticities = int(P["useVorticities"]) > 0
+if useVorticities and not useVelocities:
+    print("ERROR: useVorticities 1 computes its channels from the velocity channels: useVelocities 1")
+    exit(1)
 upsampling_mode, upsampled_data = int(P["upsamplingMode"]), int(P["upsampledData"])
 upsample_first = int(P["upsampleFirst"])
 generateUni = int(P["genUni"])
@@ -87,8 +100,8 @@ def train_main():
         print("ERROR: training is implemented for the first network (upsamplingMode 2, upsampledData 0) and the second "
               "one (upsamplingMode 1, upsampledData 1), dataDim 2")
         exit(1)
-    if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["premadeTiles"]):
-        print("ERROR: vorticity / flag / k-eps inputs and premade tiles are not supported")
+    if int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["premadeTiles"]):
+        print("ERROR: flag / k-eps inputs and premade tiles are not supported")
         exit(1)
     if int(P["pretrain"]) or int(P["pretrainDisc"]) or int(P["pretrainGen"]):
         print("ERROR: the pretraining phases (pretrain / pretrainDisc / pretrainGen, 4x.py:1232-1296) are not built")
@@ -185,7 +198,8 @@ def train_main():
     print("\nUsing parameters:\n" + ph.paramsToString())
     ph.writeParams(test_path + "params.json")
     batch = int(P["batchSize"])
-    trainer = Trainer4x(tileSizeLow=tileSizeLow, upRes=upRes, n_inputChannels=n_ch, batch_norm=batch_norm,
+    n_net = n_ch + (vorticity.CHANNELS if useVorticities else 0)      # the networks' input channels (:344)
+    trainer = Trainer4x(tileSizeLow=tileSizeLow, upRes=upRes, n_inputChannels=n_net, batch_norm=batch_norm,
                         upsampling_mode=mode, device=device, learning_rate=float(P["learningRate"]),
                         beta1=float(P["adam_beta1"]), lambda_l1=float(P["lambda"]), lambda2=float(P["lambda2"]),
                         lambda2_l=tuple(float(P["lambda2_l%d" % i]) for i in (1, 2, 3, 4)),
@@ -202,19 +216,26 @@ def train_main():
         print("Model restored (%d variables with optimiser slots)." % n_slots)
     aug = int(P["dataAugmentation"]) > 0
     n_out = (tileSizeLow * upRes) ** 2
-    n_in = (tileSizeLow * tileSizeLow if mode == 2 else n_out) * n_ch
+    n_in = (tileSizeLow * tileSizeLow if mode == 2 else n_out) * n_net
+    side = tileSizeLow if mode == 2 else tileSizeLow * upRes         # of a low tile as the tile creator cuts it
+
+    def widen(bx):
+        """addVorticity (:491-499): the three vorticity channels behind every tile's own, computed where the tiles live"""
+        return vorticity.append(bx.reshape(-1, 1, side, side, n_ch)) if useVorticities else bx
 
     def getinput(size=batch, isTraining=True, augment=aug):
         if device_tiles:
             bx, by = tiCr.selectRandomTilesDevice(size, isTraining, augment=augment)
         else:
             bx, by = tiCr.selectRandomTiles(selectionSize=size, isTraining=isTraining, augment=augment)
-        return bx.reshape(-1, n_in), by.reshape(-1, n_out)
+        return widen(bx).reshape(-1, n_in), by.reshape(-1, n_out)
 
     def gettempo(size=batch, isTraining=True, augment=aug):
         if device_tiles:
-            return tiCr.selectRandomTempoTilesDevice(size, isTraining, augment, n_t=3, dt=0.5)
-        return tiCr.selectRandomTempoTiles(size, isTraining, augment, n_t=3, dt=0.5)
+            bx, by, bp = tiCr.selectRandomTempoTilesDevice(size, isTraining, augment, n_t=3, dt=0.5)
+        else:
+            bx, by, bp = tiCr.selectRandomTempoTiles(size, isTraining, augment, n_t=3, dt=0.5)
+        return widen(bx).reshape(bx.shape[0], -1), by, bp             # :1026-1029
 
     keep_max, kept = int(P["keepMax"]), []
 
@@ -287,7 +308,7 @@ def train_main():
             print('\t{} epochs took {:.2f} seconds.'.format(outputInterval, time.time() - t0))
             if image_now:
                 trainer.sample_frame_image(tiCr, heldout.frame_index(fromSim, fromSim, frame_max), test_path + 'test_img/',
-                                           image_no, simSizeHigh)
+                                           image_no, simSizeHigh, use_vorticity=useVorticities)
                 image_no += 1
             t0 = time.time()
         if (epoch + 1) % saveInterval == 0:
@@ -306,6 +327,9 @@ if not outputOnly:
     exit(0)
 if upsampling_mode not in (0, 1, 2, 3) or int(P["dataDim"]) != 2 or int(P["useAvgDepool"]):
     print("ERROR: upsamplingMode 0 to 3 of the 2D slice path are implemented; useAvgDepool and dataDim 3 are not")
+    exit(1)
+if upsampling_mode == 0 and useVorticities:
+    print("ERROR: upsamplingMode 0 has no vorticity channels (no training path produces such a network)")
     exit(1)
 if upsampling_mode == 0 and not upsampled_data:
     print("ERROR: upsamplingMode 0 refines the volumes of density_low_2x2x1_%04d.uni (upsampledData 1)")
@@ -346,7 +370,8 @@ except FileNotFoundError as e:
         exit(1)
     params = None
 gen = multipass.Generator("gen_resnet", dict(tile_low=simSizeLow, up_res=upRes, channels=n_ch,
-                                             upsampling_mode=upsampling_mode, batch_norm=batch_norm),
+                                             upsampling_mode=upsampling_mode, batch_norm=batch_norm,
+                                             vorticity=useVorticities),
                           params, prec=ops.parse_prec(P["prec"]), device=device, seed=int(P["randSeed"]))
 print('*****OUTPUT ONLY*****')
 s = simSizeHigh
@@ -386,7 +411,7 @@ for layerno in range(frame_min, frame_max):
         if n_ch > 1:
             low[..., 1:4] *= velScale                                        # 4x.py:283
         xs = ops.axis_zoom_linear(low, 0, upRes)                             # 4x.py:1103
-        out = multipass._run_pass(gen, xs, None, 0, s, 8)                    # (z, y, x)
+        out = multipass._run_pass(gen, multipass._with_vorticity(gen, xs), None, 0, s, 8)   # (z, y, x)
         if sink is not None:
             sink.projection(None, out, (0, 1, 2))                            # 4x.py:1133-1134, before the cutoff
         vol = ops.cutoff(out, multipass.CUTOFF) if generateUni else out

@@ -15,7 +15,17 @@ checkpoints ``model_%04d.ckpt.npz`` and the moving-average weights ``model_ema_%
 
 ``out 1`` is the per-network output mode (see output_main).
 
-Not rebuilt: upsamplingMode 0 (the linear-interpolation variant no example run uses), vorticity / flag / k-eps
+``useVorticities 1`` (the tempoGAN vorticity input, addVorticity :1440-1446, called at :1482-1490,1508-1511): every
+generator takes three more input channels behind all others (:350), computed from the velocity channels of each tile or
+slice by ``mpgan_amd/vorticity.py`` -- the HIP kernel mpg_vorticity_append on device tiles, its numpy restatement on host
+tiles (``deviceTiles 0``); in getinput before the 1-in-20 blanking, which scales the velocities and not the vorticity
+(:1508-1532).  Deviations: (a) without ``useVelocities 1`` it is refused with a message (the reference widens the network
+and feeds nothing); (b) ``out 1`` computes the channels on the low-res slice batch exactly as the network receives it
+(the reference only counts them there, so a network trained with them cannot be run); (d) ``adv_mode 1 / 2`` and
+``useVelInTDisc`` read the velocity as channels 1..3 of the 7-channel tile (the reference's 4-channel reshape, :1185,
+fails there).
+
+Not rebuilt: upsamplingMode 0 (the linear-interpolation variant no example run uses), flag / k-eps
 inputs, PNG test images, TensorBoard.  ``lossScaling 1`` runs the dynamic loss scaling of :490-541 and every
 stage uses its own optimisers over its own variable subset (:1305-1362) -- train.StagedAdam.
 """
@@ -34,6 +44,7 @@ from mpgan_amd import checkpoint  # noqa: E402
 from mpgan_amd import fluiddataloader as FDL  # noqa: E402
 from mpgan_amd import paramhelpers as ph  # noqa: E402
 from mpgan_amd import tilecreator_t as tc  # noqa: E402
+from mpgan_amd import vorticity  # noqa: E402
 
 P = {}
 for name, default in [
@@ -69,6 +80,11 @@ def fail(msg):
     exit(1)
 
 
+useVorticities = int(P["useVorticities"]) > 0
+if useVorticities and not int(P["useVelocities"]):
+    fail("useVorticities 1 computes its channels from the velocity channels: useVelocities 1")
+
+
 def output_main():
     """``out 1`` (generate3DUniForNewNetwork :1600-1780, output loop :2316-2324): ONE network per invocation, the
     volumes travel through .uni files as in the commented alternative of example_run_output.py:64-70:
@@ -80,8 +96,8 @@ def output_main():
     mode, upsampled = int(P["upsamplingMode"]), int(P["upsampledData"])
     if (mode, upsampled) not in ((2, 0), (1, 1), (3, 1)) or int(P["dataDim"]) != 2 or not int(P["upsampleFirst"]):
         fail("output mode: upsamplingMode 2 (upsampledData 0) or 1 / 3 (upsampledData 1), dataDim 2, upsampleFirst 1")
-    if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]):
-        fail("vorticity / flag / k-eps inputs are not supported")
+    if int(P["useFlags"]) or int(P["useK_Eps_Turb"]):
+        fail("flag / k-eps inputs are not supported")
     ta = int(P["transposeAxis"])
     if ta not in (0, 1, 2, 3):
         fail("transposeAxis %d (0..3)" % ta)
@@ -116,7 +132,8 @@ def output_main():
                start_fms=int(P["startFms"]), max_fms=int(P["maxFms"]), add_adj=int(P["add_adj_idcs"]) > 0 and first,
                first_nn_arch=int(P["firstNNArch"]) > 0 and first, use_res_net=int(P["use_res_net"]) > 0,
                pixel_norm=int(P["pixelNorm"]) > 0, batch_norm=int(P["batchNorm"]) > 0, upsample_mode=int(P["upsampleMode"]),
-               add_bicubic=int(P["addBicubicUpsample"]) > 0, pixel_shuffle=int(P["usePixelShuffle"]) > 0 and first)
+               add_bicubic=int(P["addBicubicUpsample"]) > 0, pixel_shuffle=int(P["usePixelShuffle"]) > 0 and first,
+               vorticity=useVorticities)
     path = checkpoint.model_path(base, test_no, model_no, ema=int(P["loadEmas"]) > 0)
     try:
         params = checkpoint.load(path)
@@ -173,13 +190,13 @@ if (upsampling_mode, upsampled_data) not in ((2, 0), (1, 1), (3, 1)) or int(P["d
     fail("training is implemented for the first network (upsamplingMode 2, upsampledData 0) and the second / third "
          "one (upsamplingMode 1 / 3, upsampledData 1), dataDim 2")
 later_net = upsampling_mode != 2
-if int(P["useVorticities"]) or int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["premadeTiles"]):
-    fail("vorticity / flag / k-eps inputs and premade tiles are not supported")
+if int(P["useFlags"]) or int(P["useK_Eps_Turb"]) or int(P["premadeTiles"]):
+    fail("flag / k-eps inputs and premade tiles are not supported")
 use_gdrop, useVelInTDisc = int(P["gDrop"]) > 0, int(P["useVelInTDisc"]) > 0
 if use_gdrop and not int(P["use_LSGAN"]):
     fail("gDrop 1 needs use_LSGAN 1: the reference feeds the noise strengths only under use_LSGAN (:1993-2014)")
 if useVelInTDisc and not (int(P["adv_flag"]) and int(P["useVelocities"]) and not int(P["add_adj_idcs"])):
-    fail("useVelInTDisc 1 appends the velocity channels 1..3 of a 4-channel low-res tile to the advected frames "
+    fail("useVelInTDisc 1 appends the velocity channels 1..3 of a 4-channel low-res tile (7 with vorticity) to the advected frames "
          "(:1185,1204-1208): adv_flag 1, useVelocities 1, add_adj_idcs 0")
 upRes = int(P["upRes"])
 if upRes != 8:
@@ -224,7 +241,8 @@ if useVelocities:
     mfl = mfl + ["velocity"]
 if add_adj_idcs:
     channelLayout_low += ',d,d'
-n_inputChannels = len(channelLayout_low.split(','))
+n_tileChannels = len(channelLayout_low.split(','))                  # of a tile as the tile creator cuts it
+n_inputChannels = n_tileChannels + (vorticity.CHANNELS if useVorticities else 0)   # of the networks (:350)
 if later_net and int(P["firstNNArch"]):
     fail("firstNNArch belongs to the first network")
 # previous network's output volumes (:231-238) and the slicing axis of this pass (:301-307)
@@ -267,12 +285,12 @@ def load_stage(currentUpres, first):
         _, x_2, _ = fl2.get()
     simSizeHigh = simSizeLow * upRes
     if not later_net:
-        x = x.reshape(-1, 1, simSizeLow, simSizeLow, n_inputChannels * 3)
+        x = x.reshape(-1, 1, simSizeLow, simSizeLow, n_tileChannels * 3)
         y = y.reshape(-1, 1, simSizeLow * currentUpres, simSizeLow * currentUpres, 3)
     else:
         # (:372-376) per frame the pair (target, previous pass): the reference's reshape / concatenate / reshape of
         # the three-frame arrays is this interleave of their last axes
-        x = x.reshape(-1, 1, simSizeLow, simSizeLow, n_inputChannels * 3)
+        x = x.reshape(-1, 1, simSizeLow, simSizeLow, n_tileChannels * 3)
         y = y.reshape(-1, 1, simSizeHigh, simSizeHigh, 3)
         x_2 = x_2.reshape(-1, 1, simSizeHigh, simSizeHigh, 3)
         y = np.stack((y, x_2), axis=-1).reshape(-1, 1, simSizeHigh, simSizeHigh, 6)
@@ -316,12 +334,18 @@ if int(P["load_model_test"]) >= 0:
     print("Model restored (%d optimiser slot pairs)." % n_slots)
 
 
+def widen(bx):
+    """addVorticity (:1440-1446): the three vorticity channels behind every tile's own, computed where the tiles live"""
+    return vorticity.append(bx.reshape(-1, 1, tileSizeLow, tileSizeLow, n_tileChannels)) if useVorticities else bx
+
+
 def getinput(size=batch, isTraining=True, augment=aug):
     """:1497-1537 incl. the 1-in-20 empty-density batches"""
     if device_tiles:
         batch_xs, batch_ys = tiCr.selectRandomTilesDevice(size, isTraining, augment=augment)
     else:
         batch_xs, batch_ys = tiCr.selectRandomTiles(selectionSize=size, isTraining=isTraining, augment=augment)
+    batch_xs = widen(batch_xs)                                       # :1508-1511, before the blanking
     if not min(np.random.randint(0, 20), 1):
         batch_xs[:, :, :, :, 0:1] = 0
         if add_adj_idcs:
@@ -337,7 +361,7 @@ def getTempoinput(size=batch, isTraining=True, augment=aug):
     else:
         bx, by, bp = tiCr.selectRandomTempoTiles(size, isTraining, augment, 3, 0.5)
     n = bx.shape[0]
-    return bx.reshape(n, -1), by.reshape(n, -1), bp.reshape(n, -1)
+    return widen(bx).reshape(n, -1), by.reshape(n, -1), bp.reshape(n, -1)    # :1482-1490
 
 
 save_no = 0
@@ -468,7 +492,7 @@ for it in range(startingIter, trainingIterations):
             print('\tgdrop_strength_d: {:.6f}, gdrop_strength_t: {:.6f}'.format(gdrop_strength_d, gdrop_strength_t))
         if image_now:
             trainer.sample_frame_image(tiCr, heldout.frame_index(fromSim, fromSim, frame_max), test_path + 'test_img/',
-                                       image_no, simSizeLow * upRes, percentage=currBlendPer)
+                                       image_no, simSizeLow * upRes, percentage=currBlendPer, use_vorticity=useVorticities)
             image_no += 1
         t0 = time.time()
     if (it + 1) % saveInterval == 0:

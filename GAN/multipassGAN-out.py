@@ -16,6 +16,13 @@ arithmetic (2 = MPG_PREC_F16F6, default; 3 = MPG_PREC_F16X3).  ``transposeAxis``
 axes of the passes exactly as :397-547 do, including what is broken there: the third pass of
 transposeAxis 2 raises the reference's IndexError (:542); ``add_adj_idcs2/3`` are ignored (the
 reference's code for them writes past the array it allocates, :488-500).
+
+``useVorticities 1`` (the tempoGAN vorticity input; the switch is global, so every loaded network gets it): each network
+takes three more input channels behind all others (:148), and every pass computes them on its low-res slice batch exactly
+as the network receives it (mpg_vorticity_append through ``mpgan_amd/vorticity.py``; the later networks then resize them
+with the slice, as in training).  Deviations: the reference only counts the channels here and never fills them, so a
+network trained with them cannot be run there; without ``useVelocities 1`` the switch is refused with a message (the
+reference widens the networks and feeds nothing).
 """
 import os
 import sys
@@ -76,8 +83,11 @@ ph.checkUnusedParams()
 from mpgan_amd import ops as _ops  # noqa: E402
 prec = _ops.parse_prec(prec)
 
-if useVorticities or useFlags or useK_Eps_Turb:
-    print("ERROR: vorticity / flag / turbulence channels are not part of the multi-pass hot path")
+if useFlags or useK_Eps_Turb:
+    print("ERROR: flag / turbulence channels are not part of the multi-pass hot path")
+    exit(1)
+if useVorticities and not useVelocities:
+    print("ERROR: useVorticities 1 computes its channels from the velocity channels: useVelocities 1")
     exit(1)
 if transposeAxis not in (0, 1, 2, 3):
     print("ERROR: transposeAxis %d (0..3)" % transposeAxis)
@@ -112,7 +122,8 @@ for k, n in enumerate(nets):
                start_fms=n["start_fms"], max_fms=n["max_fms"], add_adj=n["add_adj"] and k == 0,
                first_nn_arch=bool(firstNNArch) and k == 0, use_res_net=n["use_res_net"], pixel_norm=pixel_norm,
                batch_norm=batch_norm, upsample_mode=upsampleMode, add_bicubic=bool(addBicubicUpsample),
-               pixel_shuffle=bool(usePixelShuffle) and k == 0)     # growBlockGen applies it in the first network only
+               pixel_shuffle=bool(usePixelShuffle) and k == 0,     # growBlockGen applies it in the first network only
+               vorticity=bool(useVorticities))
     try:
         params = checkpoint.load(path)
         print("Model %d restored from %s." % (k + 1, path))

@@ -553,6 +553,15 @@ int mpg_tile_orient(mpg_stream_t stream, const float* src, int zs, int ys, int x
                     const float* chan_sign, float* dst);
 int mpg_semilagr_positions(mpg_stream_t stream, const float* vel, const float* dt, int n_batch, int h, int w, int n_out,
                            float* pos);
+/* The vorticity input channels of useVorticities (addVorticity, GAN/multipassGAN-8x.py:1440-1446, 2D branch as written;
+ * called per batch and per temporal batch at -8x.py:1482-1490,1508-1511 and -4x.py:491-499,1026-1029).
+ * x [n,h,w,c] fp32 -> y [n,h,w,c+3] fp32, not overlapping:  y[..., :c] = x;  y[..., c] = y[..., c+1] = 0;
+ *   y[i,j,c+2] = 0.5f * ((x[i+1,j,2] - x[i-1,j,2]) - (x[i,j+1,1] - x[i,j-1,1]))  for 1 <= i <= h-2, 1 <= j <= w-2
+ * (i the row, j the column), 0 elsewhere -- all of it when h < 3 or w < 3.  Not the textbook curl; bit-defined (no
+ * contraction possible).  One read of x, one write of y, 64-bit offsets.  MPG_ERR_ARG: c < 4, h or w < 1, n < 0, null
+ * pointers, more than 2^32 - 1 pixels; n == 0 (with a valid h, w, c) succeeds, launches nothing and does not look at the
+ * pointers. */
+int mpg_vorticity_append(mpg_stream_t stream, const float* x, int n, int h, int w, int c, float* y);
 /* ------------------------------------------------------------------------
  * Slice mode of the training-set loader on a device-resident source (tools_wscale/fluiddataloader.py:387-544; SURVEY 8f
  * rank 2).  File handling and every random draw stay on the host (multi-pass-gan_amd/fluiddataloader_device.py).

@@ -176,6 +176,7 @@ PROTOTYPES = {
     "mpg_tile_orient": (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
                             ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_float), _P]),
     "mpg_semilagr_positions": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "mpg_vorticity_append": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     # slice mode of the training-set loader
     "mpg_slice_zoom_means": (_I, [_P, _P, ctypes.POINTER(_I), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _P, _P, _Z]),
     "mpg_slice_zoom_gather": (_I, [_P, _P, ctypes.POINTER(_I), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _I,

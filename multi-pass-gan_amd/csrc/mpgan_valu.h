@@ -1,5 +1,5 @@
 // What the vector-ALU translation units (mpgan_elem.hip, mpgan_tiles.hip, mpgan_bn.hip, mpgan_train_conv.hip,
-// mpgan_train_elem.hip, mpgan_advect.hip, mpgan_optim.hip, mpgan_tempo.hip, mpgan_loader.hip, mpgan_preview.hip) share: the block size and the one-thread-per-element grid,
+// mpgan_train_elem.hip, mpgan_advect.hip, mpgan_optim.hip, mpgan_tempo.hip, mpgan_loader.hip, mpgan_preview.hip, mpgan_vorticity.hip) share: the block size and the one-thread-per-element grid,
 // V-wide loads and stores, the block abs-max, and the three pieces the reproducible sums rest on -- the split of a pixel
 // range over blocks, the ordered sum of the blocks' results and the fixed tree over a block's threads.
 #pragma once

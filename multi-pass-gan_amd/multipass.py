@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import graph as G
-from . import arch, ops
+from . import arch, ops, vorticity
 from .session import Session, VariableStore
 
 CUTOFF = 0.0005     # multipassGAN-4x.py:1156, multipassGAN-out.py:614
@@ -80,7 +80,9 @@ def slice_range(total, comm):
 class Generator(object):
     """One generator network: private graph + session.  Call with device tensors
     x [N,h,w,C] (and y [N,H,W] for the later 8x generators); returns [N,H,W].
-    gen_resnet with upsampling_mode 0 takes planes x [N, high, low, C]: its first layer repeats the columns only."""
+    gen_resnet with upsampling_mode 0 takes planes x [N, high, low, C]: its first layer repeats the columns only.
+    cfg["vorticity"] (useVorticities): the network takes three more input channels than cfg["channels"] (plus the two
+    add_adj ones) says, behind all others; the pass functions compute them (_with_vorticity)."""
 
     def __init__(self, kind, cfg, params=None, prec=None, device="cuda:0", seed=777, prec_map=None):
         prec = ops.INFERENCE_PREC if prec is None else prec
@@ -91,17 +93,22 @@ class Generator(object):
         try:
             c = self.cfg
             low, up, nch = c["tile_low"], c["up_res"], c["channels"]
+            vort = vorticity.CHANNELS if c.get("vorticity") else 0
+            if vort and nch < 4:
+                raise ValueError("vorticity channels are computed from the velocity channels 1 and 2: channels %d < 4" % nch)
             self.high = low * up
             self.y = None
             if kind == "gen_resnet":
                 mode = c.get("upsampling_mode", 2)
                 rows = low if mode == 2 else self.high
                 cols = low if mode in (2, 0) else self.high
+                nch += vort                                  # 4x.py:344
                 self.x = G.placeholder([None, rows * cols * nch], name="x")
                 self.sampler = arch.gen_resnet(self.x, low, up, nch, mode, use_batch_norm=c.get("batch_norm", True))
             elif kind == "growing_gen":
                 first = c.get("first_gen", True)
-                n_in = nch + (2 if c.get("add_adj", False) else 0)
+                n_in = nch + (2 if c.get("add_adj", False) else 0) + vort     # 8x.py:350, out.py:148
+                nch += vort
                 self.x = G.placeholder([None, low * low * n_in], name="x")
                 src = self.x
                 if not first:
@@ -165,6 +172,19 @@ _NESTED = [False]          # set while two_pass_4x_batch runs whole volumes on l
 
 def set_pass_lanes(k):
     PASS_LANES[0] = max(1, int(k))
+
+
+def _with_vorticity(gen, xs):
+    """the slice batch [S, h, w, C] as a network with cfg["vorticity"] takes it: the three vorticity channels of every
+    slice behind its other channels (vorticity.append: the HIP kernel on device tensors).  Called on the batch exactly
+    as the generator would otherwise have received it -- after the zoom, the velocity scale, the transposes with their
+    channel exchange and add_adjacent -- so that inference feeds what getinput feeds in training."""
+    return vorticity.append(xs) if _wants_vorticity(gen) else xs
+
+
+def _wants_vorticity(gen):
+    """cfg["vorticity"] of a Generator; a callable without a cfg (the oracle stand-ins of the host rehearsals) has none"""
+    return bool((getattr(gen, "cfg", None) or {}).get("vorticity"))
 
 
 def _run_pass(gen, xs, ys, lo, hi, batch, out=None):
@@ -234,6 +254,8 @@ def _pass1_4x(gen1, low, up_res, batch, comm, backend, vel_scale, a2a=False):
         low1 = backend.channel_gather(low, None, list(range(nch)), [1.0] + [vel_scale] * 3 + [1.0] * (nch - 4))
     xs = backend.axis_zoom_linear(low1, 0, up_res)                   # [s, sim, sim, C]
     lo, hi = slice_range(s, comm)
+    if _wants_vorticity(gen1):
+        xs, lo, hi = _with_vorticity(gen1, xs[lo:hi]), 0, hi - lo
     out1 = _run_pass(gen1, xs, None, lo, hi, batch)                  # [hi-lo, s, s] = (z, y, x)
     out1 = backend.cutoff(out1, CUTOFF)                              # 4x.py:1156-1157
     return _start_hand_over(comm, out1, s, (2, 0, 1), a2a)
@@ -255,7 +277,7 @@ def _pass2_4x(gen2, low, hand, up_res, batch, comm, backend, vel_scale):
         xin = backend.channel_gather(ys.reshape(hi - lo, s, s, 1), velx, [0, 1, 2, 3])
     else:
         xin = ys.reshape(hi - lo, s, s, 1)
-    out2 = _run_pass(gen2, xin, None, 0, hi - lo, batch)             # [x-range][z][y]
+    out2 = _run_pass(gen2, _with_vorticity(gen2, xin), None, 0, hi - lo, batch)   # [x-range][z][y]
     return _start_gather(comm, out2, s), v1
 
 
@@ -278,6 +300,8 @@ def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend
         xin = backend.volume_transpose(backend.channel_gather(prev.reshape(s, s, s, 1), vel, [0, 1, 2, 3]), perm, chan_map=cmap)
     else:
         xin = backend.volume_transpose(prev.reshape(s, s, s), perm).reshape(s, s, s, 1)
+    if _wants_vorticity(gen):
+        xin, lo, hi = _with_vorticity(gen, xin[lo:hi]), 0, hi - lo
     out = _run_pass(gen, xin, None, lo, hi, batch)
     vol = comm.all_gather_slabs(out, s)
     if previews is not None:
@@ -309,7 +333,7 @@ def plane_pass_4x(gen1, low, up_res=4, batch=8, comm=None, backend=ops, vel_scal
     low1 = low
     if nch > 1 and vel_scale != 1.0:
         low1 = backend.channel_gather(low, None, list(range(nch)), [1.0] + [vel_scale] * 3 + [1.0] * (nch - 4))
-    out = _run_pass(gen1, low1, None, 0, low.shape[0], batch)        # [z_low, Y, X]
+    out = _run_pass(gen1, _with_vorticity(gen1, low1), None, 0, low.shape[0], batch)   # [z_low, Y, X]
     return backend.cutoff(out, CUTOFF) if apply_cutoff else out
 
 
@@ -325,6 +349,9 @@ def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops,
     volume (density_low_1x1x1) is what the reference stores, not a [z, y, x] one.  previews: a preview.PreviewSink
     that receives the volume where the reference calls save_img_3d (:1146), before the cutoff."""
     _preview_comm(_single_process(comm, "upsample_pass_4x"), previews)
+    if _wants_vorticity(gen0):
+        raise ValueError("upsample_pass_4x (upsamplingMode 0) has no vorticity channels: no training path produces such a "
+                         "network (its planes [x][y][z_low] are not the slices the stencil is defined on)")
     nch = low.shape[3]
     zl = low.shape[0]
     s = zl * up_res
@@ -490,7 +517,9 @@ def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops,
     xs = slice_batch_8x(low, up_res, 1, transpose_axis, backend)
     if gens[0].cfg.get("add_adj", False):
         xs_r = backend.add_adjacent(xs, lo, hi - lo)
-        out = _run_pass(gens[0], xs_r, None, 0, hi - lo, batches[0])
+        out = _run_pass(gens[0], _with_vorticity(gens[0], xs_r), None, 0, hi - lo, batches[0])
+    elif _wants_vorticity(gens[0]):
+        out = _run_pass(gens[0], _with_vorticity(gens[0], xs[lo:hi]), None, 0, hi - lo, batches[0])
     else:
         out = _run_pass(gens[0], xs, None, lo, hi, batches[0])
     if previews is not None:
@@ -499,14 +528,14 @@ def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops,
         # pass 2 (463-523): conditioned on planes of dim_output.transpose(2,1,0) (:459)
         ys, _ = _hand_over(comm, out, s, (2, 1, 0), a2a, backend)
         xl = slice_batch_8x(low, up_res, 2, transpose_axis, backend)
-        out = _run_pass(gens[1], xl[lo:hi], ys, 0, hi - lo, batches[1])
+        out = _run_pass(gens[1], _with_vorticity(gens[1], xl[lo:hi]), ys, 0, hi - lo, batches[1])   # on the low-res slice
         if previews is not None:
             previews.projection("2nd", out, (1, 2, 0))               # :521-523
     if len(gens) > 2:
         # pass 3 (525-585): conditioned on the previous result .transpose(1,2,0) (:521)
         ys, _ = _hand_over(comm, out, s, (1, 2, 0), a2a, backend)
         xl = slice_batch_8x(low, up_res, 3, transpose_axis, backend)
-        out = _run_pass(gens[2], xl[lo:hi], ys, 0, hi - lo, batches[2])
+        out = _run_pass(gens[2], _with_vorticity(gens[2], xl[lo:hi]), ys, 0, hi - lo, batches[2])
         if previews is not None:
             previews.projection("3rd", out, (0, 1, 2))               # :583-585
     vol = comm.all_gather_slabs(out, s)
@@ -552,7 +581,10 @@ def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, com
         if perm is not None:
             ys = backend.volume_transpose(ys, perm)                                  # :1650,1657,1666
     if gen.cfg.get("add_adj", False):
-        out = _run_pass(gen, backend.add_adjacent(xs, lo, hi - lo), ys[lo:hi] if ys is not None else None, 0, hi - lo, batch)
+        out = _run_pass(gen, _with_vorticity(gen, backend.add_adjacent(xs, lo, hi - lo)), ys[lo:hi] if ys is not None else None,
+                        0, hi - lo, batch)
+    elif _wants_vorticity(gen):
+        out = _run_pass(gen, _with_vorticity(gen, xs[lo:hi]), ys[lo:hi] if ys is not None else None, 0, hi - lo, batch)
     else:
         out = _run_pass(gen, xs, ys, lo, hi, batch)
     vol = comm.all_gather_slabs(out, s)

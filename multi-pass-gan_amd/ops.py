@@ -691,6 +691,21 @@ def channel_gather(a, b, cmap, scales=None, scales2=None):
     return out
 
 
+def vorticity_append(x):
+    """[..., h, w, C] -> [..., h, w, C + 3]: the input next to the three vorticity channels of useVorticities
+    (mpg_vorticity_append: addVorticity of multipassGAN-8x.py:1440-1446, 2D branch as written).  Any leading dimensions,
+    e.g. [B, 1, h, w, C]; every [h, w] slice is a stencil of its own."""
+    lib = _lib.load()
+    x = _dev(x, "x")
+    if x.dim() < 3:
+        raise _lib.MpgError("vorticity_append: x %s has no [h, w, C] at its end" % (tuple(x.shape),))
+    h, w, c = (int(d) for d in x.shape[-3:])
+    n = x.numel() // max(h * w * c, 1)
+    out = torch.empty(tuple(x.shape[:-1]) + (c + 3,), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mpg_vorticity_append(_stream(), _ptr(x), n, h, w, c, _ptr(out)), "mpg_vorticity_append")
+    return out
+
+
 def cutoff(v, thr=0.0005, out=None):
     """v[v < thr] = 0 (multipassGAN-4x.py:1156-1157)."""
     lib = _lib.load()

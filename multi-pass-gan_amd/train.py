@@ -1139,19 +1139,23 @@ class _HeldOutMixin(object):
         if not 0 <= int(stage) < levels:
             raise _lib.MpgError("evaluate: growing stage %d of %d" % (stage, levels))
 
-    def sample_frame_image(self, tiCr, index, out_dir, image_no=0, sim_size_high=None, percentage=None):
+    def sample_frame_image(self, tiCr, index, out_dir, image_no=0, sim_size_high=None, percentage=None, use_vorticity=False):
         """generateTestImage: the tiles of frame `index` (tiCr.getFrameTiles; index = (sim_no - fromSim) * frame_max +
         frame_no) through the sampler one tile at a time with `train: False`, the generator outputs assembled into the
         (sim_size_high / tileSizeHigh)^2 mosaic on the device (mpg_tiles_to_gray8) and written as
-        out_dir/img_%04d.png.  Returns the path."""
-        from . import heldout
+        out_dir/img_%04d.png.  use_vorticity: the low-res tiles get their three vorticity channels first (useVorticities:
+        the network was built three channels wider than the tile creator's layout).  Returns the path."""
+        from . import heldout, vorticity
         low, high = tiCr.getFrameTiles(index)
         th = self.tileSizeHigh
         side = (sim_size_high // th) if sim_size_high else int(round(math.sqrt(len(low))))
         if side * side != len(low):
             raise _lib.MpgError("sample_frame_image: %d tiles do not fill a %d x %d mosaic" % (len(low), side, side))
         dev = self.sess.device
-        lows = torch.as_tensor(np.ascontiguousarray(low, dtype=np.float32)).to(dev).reshape(len(low), -1)
+        lows = torch.as_tensor(np.ascontiguousarray(low, dtype=np.float32)).to(dev)
+        if use_vorticity:
+            lows = vorticity.append(lows)
+        lows = lows.reshape(len(low), -1)
         highs = torch.as_tensor(np.ascontiguousarray(high, dtype=np.float32)).to(dev).reshape(len(high), -1)
         tiles = []
         with self.sess.evaluation():
@@ -1436,7 +1440,8 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         if self.gdrop and not use_LSGAN:
             raise _lib.MpgError("gDrop 1 needs use_LSGAN 1: the reference feeds the noise strengths only under use_LSGAN "
                                 "(multipassGAN-8x.py:1993-2014)")
-        if cfg.useVelInTDisc and not (use_tempo and adv_flag and cfg.n_inputChannels == 4):
+        # 4 channels (d, vx, vy, vz) or 7: the same with the three vorticity channels behind them (useVorticities)
+        if cfg.useVelInTDisc and not (use_tempo and adv_flag and cfg.n_inputChannels in (4, 7)):
             raise _lib.MpgError("useVelInTDisc 1 needs the temporal critic, adv_flag 1 and a 4-channel low-res tile whose "
                                 "channels 1..3 are the velocity (multipassGAN-8x.py:1185,1204-1208); got use_tempo %r, "
                                 "adv_flag %r, %d channels" % (use_tempo, adv_flag, cfg.n_inputChannels))
@@ -1469,7 +1474,7 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         # 0: tensorResample on positions computed by the tile creator; 1 / 2: GAN.advect on the low-res velocity channels
         # of x_t, semi-Lagrangian / MacCormack (:1193-1199,1221-1225)
         self.adv_mode = int(adv_mode)
-        if use_tempo and adv_flag and self.adv_mode and cfg.n_inputChannels != 4:
+        if use_tempo and adv_flag and self.adv_mode and cfg.n_inputChannels not in (4, 7):
             raise _lib.MpgError("adv_mode %d reads the velocity from channels 1..3 of a 4-channel low-res tile (:1187), "
                                 "got %d channels" % (self.adv_mode, cfg.n_inputChannels))
         if use_tempo:
@@ -1601,7 +1606,7 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
                 k = cur // pc
                 v = v[:, ::k, ::k, :].contiguous()
             if pos is None:
-                vel_t = xts.reshape(-1, tl, tl, 4)[..., 1:4].contiguous()
+                vel_t = xts.reshape(-1, tl, tl, self.cfg.n_inputChannels)[..., 1:4].contiguous()
                 n = v.shape[0]                              # startBz = (batch // 3) * 3 = the rows of a tempo batch
                 v = train_ops.advect(v, vel_t, torch.zeros_like(v), 0.5, self.adv_mode, 1.0, start_bz=n)
             else:
@@ -1613,7 +1618,8 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         if self.cfg.useVelInTDisc:
             tl = self.cfg.tileSizeLow
             scale = float(2 ** int(math.ceil(percentage)))                      # upresFac (:1178)
-            return TempoVelPackFn.apply(v.contiguous(), xts.detach().reshape(-1, tl, tl, 4), scale)
+            x4 = xts.detach().reshape(-1, tl, tl, self.cfg.n_inputChannels)[..., :4].contiguous()
+            return TempoVelPackFn.apply(v.contiguous(), x4, scale)
         return v.reshape(-1, self.n_t, self.cfg.n_output).permute(0, 2, 1).reshape(-1, self.cfg.n_output * self.n_t)
 
     def _tempo_forward(self, batch_xts, batch_yts, batch_y_pos=None, percentage=3.0, gdrop_str_t=0.0):
