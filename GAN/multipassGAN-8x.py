@@ -25,8 +25,8 @@ and feeds nothing); (b) ``out 1`` computes the channels on the low-res slice bat
 ``useVelInTDisc`` read the velocity as channels 1..3 of the 7-channel tile (the reference's 4-channel reshape, :1185,
 fails there).
 
-Not rebuilt: upsamplingMode 0 (the linear-interpolation variant no example run uses), flag / k-eps
-inputs, PNG test images, TensorBoard.  ``lossScaling 1`` runs the dynamic loss scaling of :490-541 and every
+Not rebuilt: training with upsamplingMode 0 (``out 1`` runs it, see output_main; ``out 0`` says so and stops), flag /
+k-eps inputs, PNG test images, TensorBoard.  ``lossScaling 1`` runs the dynamic loss scaling of :490-541 and every
 stage uses its own optimisers over its own variable subset (:1305-1362) -- train.StagedAdam.
 """
 import math
@@ -91,16 +91,34 @@ def output_main():
       upsamplingMode 2, upsampledData 0 : first network          -> density_low_t%04d_2x2_%04d.uni   (t = load_model_test)
       upsamplingMode 1, upsampledData 1 : density_low_t<outNNTestNo>_2x2 in -> density_low_t%04d_1x1_%04d.uni
       upsamplingMode 3, upsampledData 1 : density_low_t<outNNTestNo>_1x1 in -> density_low_0x0_%04d.uni
-    with the slicing axis given by transposeAxis (0..3) and the <5e-4 cutoff on every written volume."""
+    with the slicing axis given by transposeAxis (0..3) and the <5e-4 cutoff on every written volume; and the pair in
+    which nothing is zoomed along z (:134,235-236,1614-1639,1711-1716,1763-1776):
+      upsamplingMode 2, upsampledData 0, upsampleFirst 0 : first network on the simSize z slices
+                                                           -> density_low_t%04d_2x2x1_%04d.uni (dimZ = simSize, :1763-1764)
+      upsamplingMode 0, upsampledData 1 : density_low_t<outNNTestNo>_2x2x1 in, planes (y, z_low) along x, the network
+                                          upsamples z itself -> density_low_t%04d_1x1x1_%04d.uni
+    (multipass.plane_pass_8x / upsample_pass_8x, whose docstrings name the two places where the reference cannot run as
+    written).  upsampleFirst 0 slices along z (transposeAxis 0); upsamplingMode 0 needs useVelocities 1 (the channel swap
+    of :1637-1639 and the residual's channel 4) and has no vorticity channels, like the 4x driver."""
     from mpgan_amd import multipass, ops, uniio
     mode, upsampled = int(P["upsamplingMode"]), int(P["upsampledData"])
-    if (mode, upsampled) not in ((2, 0), (1, 1), (3, 1)) or int(P["dataDim"]) != 2 or not int(P["upsampleFirst"]):
-        fail("output mode: upsamplingMode 2 (upsampledData 0) or 1 / 3 (upsampledData 1), dataDim 2, upsampleFirst 1")
+    up_first = int(P["upsampleFirst"]) > 0
+    if (mode, upsampled) not in ((2, 0), (1, 1), (3, 1), (0, 1)) or int(P["dataDim"]) != 2:
+        fail("output mode: upsamplingMode 2 (upsampledData 0) or 0 / 1 / 3 (upsampledData 1), dataDim 2")
+    if not up_first and mode != 2:
+        fail("upsampleFirst 0 belongs to the first network (upsamplingMode 2): the other modes read what it wrote")
     if int(P["useFlags"]) or int(P["useK_Eps_Turb"]):
         fail("flag / k-eps inputs are not supported")
     ta = int(P["transposeAxis"])
     if ta not in (0, 1, 2, 3):
         fail("transposeAxis %d (0..3)" % ta)
+    if not up_first and ta != 0:
+        fail("upsampleFirst 0 runs the network on the z slices as they are: transposeAxis 0")
+    if mode == 0 and useVorticities:
+        fail("upsamplingMode 0 has no vorticity channels (no training path produces such a network)")
+    if mode == 0 and not int(P["useVelocities"]):
+        fail("upsamplingMode 0 swaps and scales the velocity channels of its planes (:1636-1639) and takes its residual "
+             "from channel 4 (:721): useVelocities 1")
     # extensions: uniIndex 1 = the written volumes record their unit sizes (device codecs), which lets deviceRead 1 = the
     # previous network's volume of each frame is read inside the frame loop and inflated on the GPU (uniio.readUniToDevice)
     uni_index, device_read = int(P["uniIndex"]), int(P["deviceRead"])
@@ -122,13 +140,14 @@ def output_main():
     x_3d, _, _ = fl.get()
     x_3d[:, :, :, :, 1:4] = float(P["velScale"]) * x_3d[:, :, :, :, 1:4]                     # :361
     x_2 = None
-    prev_name = ("density_low_t%04d_2x2" if mode == 1 else "density_low_t%04d_1x1") % int(P["outNNTestNo"]) + "_%04d.uni"
+    prev_name = {1: "density_low_t%04d_2x2", 0: "density_low_t%04d_2x2x1"}.get(mode, "density_low_t%04d_1x1") % int(
+        P["outNNTestNo"]) + "_%04d.uni"                                                       # :231-238
     if upsampled and not device_read:
         fl2 = FDL.FluidDataLoader(print_info=0, base_path=sims, numpy_seed=int(P["randSeed"]), filename=prev_name,
                                   filename_index_min=f0, oldNamingScheme=False, filename_index_max=f1, indices=[from_sim],
                                   data_fraction=1.0, multi_file_list=["density"])
         x_2, _, _ = fl2.get()
-    cfg = dict(tile_low=sim, up_res=up, channels=n_ch, first_gen=first, filter_size=int(P["filterSize"]),
+    cfg = dict(tile_low=sim, up_res=up, channels=n_ch, first_gen=first, upsampling_mode=mode, filter_size=int(P["filterSize"]),
                start_fms=int(P["startFms"]), max_fms=int(P["maxFms"]), add_adj=int(P["add_adj_idcs"]) > 0 and first,
                first_nn_arch=int(P["firstNNArch"]) > 0 and first, use_res_net=int(P["use_res_net"]) > 0,
                pixel_norm=int(P["pixelNorm"]) > 0, batch_norm=int(P["batchNorm"]) > 0, upsample_mode=int(P["upsampleMode"]),
@@ -145,8 +164,9 @@ def output_main():
         print("no checkpoint, seeded synthetic weights (synthWeights 1)")
     gen = multipass.Generator("growing_gen", cfg, params, prec=ops.parse_prec(P["prec"]), device="cuda:0",
                               seed=int(P["randSeed"]))
-    out_name = {2: "density_low_t%04d_2x2" % test_no + "_%04d.uni", 1: "density_low_t%04d_1x1" % test_no + "_%04d.uni",
-                3: "density_low_0x0_%04d.uni"}[mode]
+    out_name = {2: "density_low_t%04d_2x2" % test_no + ("" if up_first else "x1") + "_%04d.uni",
+                1: "density_low_t%04d_1x1" % test_no + "_%04d.uni", 0: "density_low_t%04d_1x1x1" % test_no + "_%04d.uni",
+                3: "density_low_0x0_%04d.uni"}[mode]                                          # :1768-1778
     print('*****OUTPUT ONLY*****')
     probe = sims + "sim_%04d/density_low_%04d.uni" % (from_sim, 0)
     head_0, _ = uniio.readUni(probe if os.path.exists(probe) else sims + "sim_%04d/density_low_%04d.uni" % (from_sim, f0))
@@ -166,7 +186,8 @@ def output_main():
         else:
             prev = None if x_2 is None else torch.as_tensor(np.ascontiguousarray(x_2[layerno - f0][..., 0])).to("cuda:0")
         sink = preview.PreviewSink(test_path, layerno, int(P["tileSize"]) * up) if previews else None
-        vol = multipass.single_pass_8x(gen, low, prev, up, ta, batch=2, apply_cutoff=gen_uni, previews=sink)
+        vol = multipass.single_pass_8x(gen, low, prev, up, ta, batch=2, apply_cutoff=gen_uni, previews=sink,
+                                       upsample_first=up_first)
         torch.cuda.synchronize()
         if sink is not None:
             pictures += len(sink.written)
@@ -174,6 +195,8 @@ def output_main():
         if gen_uni:
             head = dict(head_0)
             head['dimX'] = head['dimY'] = head['dimZ'] = s
+            if not up_first:
+                head['dimZ'] = sim                                                           # :1763-1764
             uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol,
                                      codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"),
                                      unit_index=bool(uni_index))
@@ -186,6 +209,9 @@ if int(P["out"]) > 0:
     output_main()
     exit(0)
 upsampling_mode, upsampled_data = int(P["upsamplingMode"]), int(P["upsampledData"])
+if upsampling_mode == 0:
+    fail("training upsamplingMode 0 is not built (the [tileSizeHigh, tileSizeLow] tiles of :298,378-382 and the faded "
+         "heads of :729-737); the mode runs in output mode only: out 1 upsamplingMode 0 upsampledData 1")
 if (upsampling_mode, upsampled_data) not in ((2, 0), (1, 1), (3, 1)) or int(P["dataDim"]) != 2:
     fail("training is implemented for the first network (upsamplingMode 2, upsampledData 0) and the second / third "
          "one (upsamplingMode 1 / 3, upsampledData 1), dataDim 2")

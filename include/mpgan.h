@@ -223,6 +223,13 @@ int mpg_resize_bilinear(mpg_stream_t stream, const float* x, int n, int h, int w
  * (avg_depool(mode=2), multipassGAN-out.py:330) */
 int mpg_resize_bicubic(mpg_stream_t stream, const float* x, int n, int h, int w, int c,
                        float* y, int oh, int ow);
+/* The residual of the upsampling_mode 0 growing generator (multipassGAN-8x.py:720-721) in one pass:
+ * out[n,h,wl*f,1] = dens[n,h,wl*f,1] + resize_images(src[n,h,wl,c][..., c_src], [h, wl*f], method=2).  The rows are kept, so
+ * the row weights of mpg_resize_bicubic are exactly (0, 1, 0, 0) and four column taps remain per output pixel, with that
+ * entry's coordinate, table offset and weights.  f: a power of two up to 64.  out is a buffer of its own.  16-byte accesses
+ * to dens / out when wl * f is a multiple of 4 and both are 16-byte aligned, scalar ones otherwise; src needs no alignment. */
+int mpg_bicubic_cols_add(mpg_stream_t stream, const float* src, int n, int h, int wl, int c, int c_src, int f,
+                         const float* dens, float* out);
 /* tf.nn.max_pool VALID, k x k window, stride s (GAN.max_pool, GAN.py:152-159).  arg (may be NULL; one byte per output)
  * receives the window position dy * k + dx of the first maximum in scan order; mpg_max_pool_bwd sends dy there
  * (dx [n,h,w,c] is overwritten). */

@@ -119,6 +119,7 @@ PROTOTYPES = {
     "mpg_resize_nearest": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
     "mpg_resize_bilinear": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
     "mpg_resize_bicubic": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
+    "mpg_bicubic_cols_add": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mpg_avg_pool2": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "mpg_max_pool": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mpg_max_pool_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

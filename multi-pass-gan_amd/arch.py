@@ -204,14 +204,27 @@ class Cfg8x(object):
         self.bn_decay = bn_decay
         self.usePixelShuffle = bool(usePixelShuffle)     # only the first network reads it (growBlockGen, -out.py:239-247)
         self.gDrop = bool(gDrop)                         # use_gdrop: Gaussian noise on the critics' conv inputs (-8x.py:155,601-603)
-        if upsampling_mode not in (1, 2, 3):
-            raise NotImplementedError("upsampling_mode %d (only 1, 2, 3 are used by the example runs)" % upsampling_mode)
-        self.n_input = tileSizeLow ** 2 * n_inputChannels            # -8x.py:402-416 (modes 1, 2, 3)
+        if upsampling_mode not in (0, 1, 2, 3):
+            raise NotImplementedError("upsampling_mode %d (0..3)" % upsampling_mode)
+        if upsampling_mode == 0:
+            # planes [tileSizeHigh, tileSizeLow] of the previous pass next to the low-res channels (-8x.py:404-405,413-414)
+            if addBicubicUpsample and n_inputChannels + 1 < 5:
+                raise ValueError("upsampling_mode 0 with addBicubicUpsample takes its residual from channel 4 of the "
+                                 "[tileSizeHigh, tileSizeLow, n_inputChannels + 1] input (-8x.py:721): n_inputChannels + 1 "
+                                 "= %d < 5" % (n_inputChannels + 1))
+            self.n_input = self.tileSizeHigh * tileSizeLow * (n_inputChannels + 1)
+        else:
+            self.n_input = tileSizeLow ** 2 * n_inputChannels        # -8x.py:402-416 (modes 1, 2, 3)
         self.n_output = self.tileSizeHigh ** 2
 
     @property
     def first_gen(self):
         return self.upsampling_mode == 2
+
+    @property
+    def axis_gen(self):
+        """upsampling_mode 0: the network that upsamples the one remaining axis itself"""
+        return self.upsampling_mode == 0
 
 
 def second_gen_input(x, y, tileSizeLow, tileSizeHigh, n_inputChannels):
@@ -244,14 +257,28 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
                 output=None):
     """The 8x generator.  output=True (inference, -out.py:286-338): only the last level's density head.
     output=False (training, -8x.py:677-744): a head per level, faded in with lerp(old, new, percentage - (j-1)).
-    _in: [N, h*w*C] flat or the 4D tensor second_gen_input / later_network_input built."""
+    _in: [N, h*w*C] flat or the 4D tensor second_gen_input / later_network_input built.
+
+    cfg.upsampling_mode 0 (inference form only; -8x.py:634-635,681-682,720-721): the input is
+    [-1, tileSizeHigh, tileSizeLow, n_inputChannels + 1] -- planes of the previous pass next to the low-res channels --
+    and every block starts with gan.max_depool(height_factor=1, width_factor=2), so the three blocks grow the columns
+    from tileSizeLow to tileSizeHigh and leave the rows alone.  With addBicubicUpsample the residual is the bicubic
+    resize to [tileSizeHigh, tileSizeLow * 2^j] of channel index 4 of the input, exactly as the reference writes it
+    (:721) -- NOT channel 0, the previous pass, which the other modes add; hence n_inputChannels + 1 >= 5 (Cfg8x
+    refuses less).  The training form needs GAN.avg_depool(scale=[1, 2], mode=1) for the faded heads (:730) and is not
+    built."""
     c = cfg
     output = (percentage is None) if output is None else output
+    if c.axis_gen and not output:
+        raise NotImplementedError("growing_gen: training upsampling_mode 0 is not built (the faded heads of "
+                                  "-8x.py:729-737 and their data path); only the inference form (output=True) is")
     levels = log2_int(c.upRes) if currentUpres is None else currentUpres
     stem, blocks = growing_gen_table(c.start_fms, c.max_fms, levels, c.first_nn_arch, c.use_res_net)
     with tf.variable_scope("generator", reuse=reuse):
         if c.first_gen:
             x_in = tf.reshape(_in, shape=[-1, c.tileSizeLow, c.tileSizeLow, c.n_inputChannels])
+        elif c.axis_gen:
+            x_in = tf.reshape(_in, shape=[-1, c.tileSizeHigh, c.tileSizeLow, c.n_inputChannels + 1])
         else:
             x_in = tf.reshape(_in, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, c.n_inputChannels + 1])
         gan = GAN(x_in, bn_decay=c.bn_decay if not output else 0.0)
@@ -270,12 +297,17 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
                     x = gan.pixel_shuffle(x, upres=2, stage="%d" % up)
                 elif c.first_gen:
                     x = gan.avg_depool(mode=c.upsampleMode)      # acts on gan.layer (-out.py:243)
+                elif c.axis_gen:
+                    x = gan.max_depool(height_factor=1, width_factor=2)      # acts on gan.layer too (-8x.py:635, GAN.py:517)
                 x = em.units(x, units, use_batch_norm)
                 if not output or last:
                     dens = _density_head(x, up, reuse, train, 0.0)
             if c.addBicubicUpsample and (not output or last):    # residual learning (-out.py:327-332, -8x.py:718-725)
-                base = tf.slice_channels(x_in, 0, 1)
-                dens = dens + (GAN(base).avg_depool(mode=2, scale=[up]) if c.first_gen else base)
+                if c.axis_gen:                                   # channel 4, as written (-8x.py:721)
+                    dens = dens + tf.resize_images(tf.slice_channels(x_in, 4, 1), [c.tileSizeHigh, c.tileSizeLow * up], 2)
+                else:
+                    base = tf.slice_channels(x_in, 0, 1)
+                    dens = dens + (GAN(base).avg_depool(mode=2, scale=[up]) if c.first_gen else base)
             if not output:
                 size = c.tileSizeLow * up if c.first_gen else c.tileSizeHigh
                 if c.first_gen:
@@ -283,8 +315,8 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
                 old = tf.reshape(tf.lerp(old, dens, percentage - (j - 1)), shape=[-1, size, size, 1])
             elif last:
                 old = dens
-        size = int(old.get_shape()[1])
-        return tf.reshape(old, shape=[-1, size * size])
+        rows, cols = int(old.get_shape()[1]), int(old.get_shape()[2])
+        return tf.reshape(old, shape=[-1, rows * cols])
 
 
 def _critic(x_in, p, percentage, cfg, reuse, use_batch_norm, train, levels, mb_group, gstr=None):

@@ -81,6 +81,8 @@ class Generator(object):
     """One generator network: private graph + session.  Call with device tensors
     x [N,h,w,C] (and y [N,H,W] for the later 8x generators); returns [N,H,W].
     gen_resnet with upsampling_mode 0 takes planes x [N, high, low, C]: its first layer repeats the columns only.
+    growing_gen with cfg["upsampling_mode"] 0 takes planes x [N, high, low, C + 1] (previous pass first) and no y: every
+    block repeats the columns once (arch.growing_gen).
     cfg["vorticity"] (useVorticities): the network takes three more input channels than cfg["channels"] (plus the two
     add_adj ones) says, behind all others; the pass functions compute them (_with_vorticity)."""
 
@@ -107,15 +109,23 @@ class Generator(object):
                 self.sampler = arch.gen_resnet(self.x, low, up, nch, mode, use_batch_norm=c.get("batch_norm", True))
             elif kind == "growing_gen":
                 first = c.get("first_gen", True)
+                mode = c.get("upsampling_mode", 2 if first else 1)
+                first = mode == 2
+                if mode == 0 and vort:
+                    raise ValueError("growing_gen with upsampling_mode 0 has no vorticity channels: no training path "
+                                     "produces such a network")
                 n_in = nch + (2 if c.get("add_adj", False) else 0) + vort     # 8x.py:350, out.py:148
                 nch += vort
-                self.x = G.placeholder([None, low * low * n_in], name="x")
+                if mode == 0:          # planes [high, low] of (previous pass, low-res channels): 8x.py:404-405,413-414
+                    self.x = G.placeholder([None, self.high * low * (nch + 1)], name="x")
+                else:
+                    self.x = G.placeholder([None, low * low * n_in], name="x")
                 src = self.x
-                if not first:
+                if mode in (1, 3):
                     self.y = G.placeholder([None, None], name="y")
                     src = arch.second_gen_input(self.x, self.y, low, self.high, nch)
                 acfg = arch.Cfg8x(tileSizeLow=low, upRes=up, n_inputChannels=n_in if first else nch,
-                                  upsampling_mode=2 if first else 1, upsampleMode=c.get("upsample_mode", 1),
+                                  upsampling_mode=mode if mode in (0, 2) else 1, upsampleMode=c.get("upsample_mode", 1),
                                   filterSize=c["filter_size"], start_fms=c["start_fms"], max_fms=c["max_fms"],
                                   first_nn_arch=c.get("first_nn_arch", False), use_res_net=c.get("use_res_net", True),
                                   pixel_norm=c.get("pixel_norm", True), addBicubicUpsample=c.get("add_bicubic", True),
@@ -559,18 +569,106 @@ _SINGLE_PASS = {0: (None, None, (0, 1, 2)), 1: ((1, 0, 2), _SWAP_YZ, (1, 0, 2)),
 _ZOOM_AXIS = {0: 0, 1: 1, 2: 2, 3: 2}
 
 
+def _axis_restore(vol, transpose_axis, apply_cutoff, backend):
+    """the transposes the reference applies to its slice stack before it writes it (8x.py:1720-1725), with the cutoff"""
+    back = _SINGLE_PASS[transpose_axis][2]
+    if back == (0, 1, 2):
+        return backend.cutoff(vol, CUTOFF) if apply_cutoff else vol
+    return backend.volume_transpose(vol, back, cutoff=CUTOFF if apply_cutoff else 0.0)
+
+
+def plane_pass_8x(gen1, low, up_res=8, batch=2, comm=None, backend=ops, apply_cutoff=True, previews=None):
+    """upsamplingMode 2 with upsampleFirst 0 (8x.py:1617,1633,1714,1763-1764,1772): the first network runs over the
+    simSize z slices of the low-res array as they are, nothing is zoomed.  low: [z_low, y, x, C] with the velocities
+    already scaled by velScale (:361); returns [z_low, Y, X] (density_low_t%04d_2x2x1).  Slices along z only: the
+    reference's transposeAxis branches (:1644-1666, 1720-1725) would leave a volume whose header no reader of the 2x2x1
+    file expects, and upsample_pass_8x takes [z_low, Y, X]."""
+    _preview_comm(_single_process(comm, "plane_pass_8x"), previews)
+    zl = low.shape[0]
+    if (getattr(gen1, "cfg", None) or {}).get("add_adj", False):
+        xs = backend.add_adjacent(low, 0, zl)                        # :1671-1685
+    else:
+        xs = low
+    out = _run_pass(gen1, _with_vorticity(gen1, xs), None, 0, zl, batch)      # [z_low, Y, X]
+    if previews is not None:
+        previews.projection(None, out, (0, 1, 2))                    # :1718
+    return backend.cutoff(out, CUTOFF) if apply_cutoff else out
+
+
+def upsample_pass_8x(gen0, low, prev, up_res=8, transpose_axis=0, batch=2, comm=None, backend=ops, apply_cutoff=True,
+                     previews=None):
+    """upsamplingMode 0 (8x.py:1615,1635-1639,1716-1725,1776): the second network upsamples z itself.  prev: the
+    [z_low, Y, X] volume of plane_pass_8x; gen0: Generator("growing_gen", upsampling_mode=0); low: [z_low, y, x, C >= 4]
+    with the velocities already scaled by velScale (:361).
+    As written: ALL channels of the low-res array, the density too, are zoomed along y and x (:1615); concatenated
+    behind prev (:1635); planes [x][y][z_low] (transpose(2, 1, 0, 3)); channels 1 and 2 -- the zoomed density and vx --
+    times upRes (:1636); channels 1 and 3 swapped (:1637-1639): (prev, vy, vx * upRes, d * upRes, vz, ...).  Channel 4,
+    which the network's residual reads (arch.growing_gen), is vz.
+    Two deviations, where the reference cannot run as written: it reshapes the planes to n_inputChannels channels
+    (:1635) although they hold n_inputChannels + 1 and n_input counts that many (:413-414) -- here they keep their
+    channels; and it feeds `y: batch_ys_in` (:1697), a name that mode 0 never assigns and a placeholder the sampler does
+    not read (:1072-1073) -- here nothing is fed.  Fewer than four low-res channels fail at the swap of :1638 there and
+    are refused here.
+    The output stack [x][y][z] goes through the transposeAxis restore of :1720-1725 as written: with transposeAxis 0,
+    the default, the stored volume (density_low_t%04d_1x1x1) keeps the axes (x, y, z); transposeAxis 2 makes it
+    [z, y, x].  previews: a preview.PreviewSink that receives the stack where the reference calls save_img_3d (:1718)."""
+    _preview_comm(_single_process(comm, "upsample_pass_8x"), previews)
+    if _wants_vorticity(gen0):
+        raise ValueError("upsample_pass_8x (upsamplingMode 0) has no vorticity channels: no training path produces such a "
+                         "network (its planes [x][y][z_low] are not the slices the stencil is defined on)")
+    zl, nch = low.shape[0], low.shape[3]
+    s = zl * up_res
+    if nch < 4:
+        raise ValueError("upsample_pass_8x: %d low-res channels; the channel swap of multipassGAN-8x.py:1637-1639 needs the "
+                         "density and three velocity components (useVelocities 1)" % nch)
+    if tuple(prev.shape) != (zl, s, s):
+        raise ValueError("upsample_pass_8x: previous volume %s, expected %s" % (tuple(prev.shape), (zl, s, s)))
+    tile = low
+    for ax in (1, 2):
+        tile = backend.axis_zoom_linear(tile, ax, up_res)            # [z_low, Y, X, C]
+    up = float(up_res)
+    xin = backend.channel_gather(prev.reshape(zl, s, s, 1), tile, [0, 3, 2, 1] + list(range(4, nch + 1)),
+                                 [1.0, 1.0, up, up] + [1.0] * (nch - 3))
+    xin = backend.volume_transpose(xin, (2, 1, 0))                   # [x][y][z_low][C + 1]
+    out = _run_pass(gen0, xin, None, 0, s, batch)                    # [x][y][z]
+    if previews is not None:
+        previews.projection(None, out, (0, 1, 2))                    # :1718
+    return _axis_restore(out, transpose_axis, apply_cutoff, backend)
+
+
+def two_pass_8x_axis(gen1, gen0, low, up_res=8, batches=(2, 2), transpose_axis=0, comm=None, backend=ops):
+    """plane_pass_8x then upsample_pass_8x in one process, the volumes staying in HBM: the 8x pipeline in which nothing
+    is zoomed along z (sim + sim * upRes generator slices, the second network on planes of sim * upRes x sim pixels).
+    Returns (final volume as upsample_pass_8x leaves it, pass-1 volume [z_low, Y, X]), both with the cutoff of the files
+    the reference writes."""
+    _single_process(comm, "two_pass_8x_axis")
+    v1 = plane_pass_8x(gen1, low, up_res, batches[0], None, backend)
+    return upsample_pass_8x(gen0, low, v1, up_res, transpose_axis, batches[1], None, backend), v1
+
+
 def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, comm=None, backend=ops, apply_cutoff=True,
-                   previews=None):
+                   previews=None, upsample_first=True):
     """One `multipassGAN-8x.py out 1` invocation.  low: device [z,y,x,C]; prev: None for the first network
     (upsamplingMode 2) or the previous network's [z,y,x] volume as stored in its .uni file (modes 1 / 3).
     Returns the volume the reference writes: [z,y,x] with the <5e-4 cutoff (:1720-1725, 1766-1767).  previews: a
     preview.PreviewSink that receives the slice stack where the reference calls save_img_3d (:1709-1718), before the
-    axis restore and the cutoff."""
+    axis restore and the cutoff.
+    upsample_first=False (upsampleFirst 0, first network only): plane_pass_8x.  A generator built with
+    cfg["upsampling_mode"] 0 takes the [z_low, Y, X] volume of that pass as prev: upsample_pass_8x."""
+    if (getattr(gen, "cfg", None) or {}).get("upsampling_mode") == 0:
+        if prev is None:
+            raise ValueError("single_pass_8x: upsamplingMode 0 refines the volume of the upsampleFirst 0 pass (prev)")
+        return upsample_pass_8x(gen, low, prev, up_res, transpose_axis, batch, comm, backend, apply_cutoff, previews)
+    if not upsample_first:
+        if prev is not None or transpose_axis != 0:
+            raise ValueError("single_pass_8x: upsampleFirst 0 belongs to the first network (no previous volume) and "
+                             "slices along z (transposeAxis 0)")
+        return plane_pass_8x(gen, low, up_res, batch, comm, backend, apply_cutoff, previews)
     comm = _preview_comm(comm, previews)
     sim, nch = low.shape[0], low.shape[3]
     s = sim * up_res
     lo, hi = slice_range(s, comm)
-    perm, cmap, back = _SINGLE_PASS[transpose_axis]
+    perm, cmap, _ = _SINGLE_PASS[transpose_axis]
     xs = backend.axis_zoom_linear(low, _ZOOM_AXIS[transpose_axis], up_res)           # :1606-1613, 1624-1631
     if perm is not None:
         xs = backend.volume_transpose(xs, perm, chan_map=cmap if nch >= 4 else None)  # :1644-1664
@@ -590,7 +688,4 @@ def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, com
     vol = comm.all_gather_slabs(out, s)
     if previews is not None:
         previews.projection(None, vol, (0, 1, 2))                    # 8x.py:1718
-    thr = CUTOFF if apply_cutoff else 0.0
-    if back == (0, 1, 2):
-        return backend.cutoff(vol, CUTOFF) if apply_cutoff else vol
-    return backend.volume_transpose(vol, back, cutoff=thr)
+    return _axis_restore(vol, transpose_axis, apply_cutoff, backend)

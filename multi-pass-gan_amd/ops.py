@@ -549,6 +549,33 @@ def resize_images(x, oh, ow, method):
     raise _lib.MpgError("resize method %r not supported" % (method,))
 
 
+def bicubic_cols_add_ok(src_shape, c_src, f):
+    """does mpg_bicubic_cols_add take channel c_src of a [n, h, wl, c] tensor at column factor f?  (the planner asks before
+    it emits the kernel; what it refuses runs as slice, resize_bicubic and add)"""
+    return (len(src_shape) == 4 and 0 <= c_src < src_shape[3] and 1 <= f <= 64 and f & (f - 1) == 0
+            and src_shape[2] * f < 2 ** 31)
+
+
+def bicubic_cols_add(src, c_src, f, dens, out=None):
+    """dens [n,h,wl*f,1] + the bicubic resize of src[n,h,wl,c][..., c_src] along the columns by f (mpg_bicubic_cols_add: the
+    residual of the upsampling_mode 0 growing generator, multipassGAN-8x.py:720-721).  out: where the result goes (fp32,
+    contiguous, as many elements as dens, not dens itself), else a new tensor."""
+    lib = _lib.load()
+    src, dens = _dev(src, "src"), _dev(dens, "dens")
+    if src.dim() != 4:
+        raise _lib.MpgError("bicubic_cols_add: expected NHWC src, got %s" % (tuple(src.shape),))
+    n, h, wl, c = src.shape
+    if dens.numel() != n * h * wl * f:
+        raise _lib.MpgError("bicubic_cols_add: dens %s is not [%d,%d,%d,1]" % (tuple(dens.shape), n, h, wl * f))
+    if out is None:
+        out = torch.empty((n, h, wl * f, 1), dtype=torch.float32, device=src.device)
+    elif _dev(out, "out").numel() != dens.numel():
+        raise _lib.MpgError("bicubic_cols_add: out %s does not match dens %s" % (tuple(out.shape), tuple(dens.shape)))
+    _lib.check(lib.mpg_bicubic_cols_add(_stream(), _ptr(src), n, h, wl, c, int(c_src), int(f), _ptr(dens), _ptr(out)),
+               "mpg_bicubic_cols_add")
+    return out.view(n, h, wl * f, 1)
+
+
 def max_pool(x, k=2, s=2, want_arg=False):
     """tf.nn.max_pool(x, k, s, VALID) (GAN.py:152-159); with want_arg also the uint8 window positions of the maxima"""
     lib = _lib.load()

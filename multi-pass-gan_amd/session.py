@@ -14,7 +14,9 @@ Fusion rules (all arithmetic stays in the kernels of libmpgan_hip.so):
     GAN.py:554-560), is one ``mpg_conv2d_fused_d2s`` launch per 128 outputs writing the shuffled tensor;
   * a fused convolution of more than 128 outputs (the 256-wide first level of the 8x generators at the driver's
     defaults) is one step of ``mpg_conv2d_fused_window`` launches into the same tensors, its pixel norm one
-    ``mpg_pixel_norm_g8`` pass behind them (``ops.conv2d_fused_wide``).
+    ``mpg_pixel_norm_g8`` pass behind them (``ops.conv2d_fused_wide``);
+  * ``chain + resize_images(slice(x, c, 1), bicubic)`` with the rows kept (the residual of the upsampling_mode 0 growing
+    generator, multipassGAN-8x.py:720-721) is the convolution launch and one ``mpg_bicubic_cols_add`` behind it.
 The matchers only recognise these patterns; ``Session._fused_step`` makes the step of every one of them.
 Everything else falls back to one kernel per node.
 """
@@ -486,6 +488,8 @@ class Session(object):
         cur = n
         # chain + tensor  (only valid as the last op: the epilogue adds after act / pixel norm)
         if cur.op == "add" and self._match_lin(cur, single_use) is None:
+            if self._cols_residual(cur) is not None:      # dens + column bicubic: its own kernel behind the convolution
+                return None
             for side in (0, 1):
                 cand, other = cur.inputs[side], cur.inputs[1 - side]
                 if single_use(cand) and self._match_chain(cand, single_use) is not None:
@@ -691,6 +695,9 @@ class Session(object):
             cnt = n.attrs["count"]
             return _Step(n, [n.inputs[0]], lambda env, i=n.inputs[0]: self._f32(env, i).reshape(self._f32(env, i).shape[0], -1)[:, :cnt].contiguous())
         if op == "add":
+            res = self._cols_residual(n)
+            if res is not None:
+                return self._cols_residual_step(n, *res)
             a, b = n.inputs
             return _Step(n, [a, b], lambda env: ops.add_act(self._f32(env, a), self._f32(env, b)))
         if op == "act":
@@ -750,6 +757,40 @@ class Session(object):
             if direct is not None:
                 return direct
         raise G.GraphError("no HIP lowering for node %r (inputs %r)" % (n, n.inputs))
+
+    # ---- the residual of the upsampling_mode 0 growing generator ---------------------------------------------------
+    @staticmethod
+    def _cols_residual(n):
+        """n = dens + resize_images(slice(src, c_src, 1), [h, wl * f], bicubic) with the rows kept, one density channel and
+        a factor mpg_bicubic_cols_add takes (arch.growing_gen, multipassGAN-8x.py:720-721) -> (dens, src, c_src, f), else
+        None: anything else stays the unfused composition (slice, mpg_resize_bicubic, add)"""
+        if n.op != "add":
+            return None
+        for side in (0, 1):
+            rs, dens = n.inputs[side], n.inputs[1 - side]
+            if rs.op != "resize" or rs.attrs["method"] != 2 or rs.inputs[0].op != "slice":
+                continue
+            sl = rs.inputs[0]
+            src = sl.inputs[0]
+            if sl.attrs["size"] != 1 or len(src.shape) != 4 or rs.attrs["oh"] != src.shape[1] or rs.attrs["ow"] % src.shape[2]:
+                continue
+            f = rs.attrs["ow"] // src.shape[2]
+            if tuple(dens.shape[1:]) != (rs.attrs["oh"], rs.attrs["ow"], 1) or not ops.bicubic_cols_add_ok(
+                    (1,) + tuple(src.shape[1:]), sl.attrs["begin"], f):
+                continue
+            return dens, src, sl.attrs["begin"], f
+        return None
+
+    def _cols_residual_step(self, n, dens, src, c_src, f):
+        """one mpg_bicubic_cols_add launch: reads the convolution's density and the low plane, writes the sum (into the
+        buffer run_device was given when n is what it fetches)"""
+        def run(env):
+            out = env.get("__out__")
+            return ops.bicubic_cols_add(self._f32(env, src), c_src, f, self._f32(env, dens),
+                                        out=out if out is None else out.view(-1, *n.shape[1:]))
+
+        info = {"kind": "bicubic_cols_add", "src": src.name, "c_src": c_src, "factor": f, "dens": dens.name}
+        return _Step(n, [dens, src], run, info)
 
     def _match_direct(self, n, single_use):
         """[act](bn?(bias_add?(conv2d | matmul | conv2d_transpose))) outside the fused step: strided convolutions, more

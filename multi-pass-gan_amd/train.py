@@ -1425,6 +1425,10 @@ class Trainer8x(_SlotStateMixin, _HeldOutMixin):
         from . import arch
         from .session import VariableStore
         self.cfg = cfg
+        if cfg.upsampling_mode == 0:
+            raise NotImplementedError("Trainer8x: training upsampling_mode 0 is not built (the faded heads need "
+                                      "GAN.avg_depool(scale=[1, 2], mode=1), multipassGAN-8x.py:729-737, and the "
+                                      "[tileSizeHigh, tileSizeLow] tiles of :298,378-382); the mode runs in inference only")
         self.k, self.k2, self.weight_dld = lambda_l1, lambda2, weight_dld
         self.use_wgan_gp, self.use_LSGAN = use_wgan_gp, use_LSGAN
         # `batchNorm 1` / `use_mb_stddev 1` (multipassGAN-8x.py:85,149,847,907; both 0 in the reference runs) with the WGAN-GP
