@@ -5,16 +5,12 @@ using namespace mpg::conv;
 
 namespace {
 
-// extra bytes of dynamic LDS asked for by every conv_small_kernel launch (occupancy experiments)
-#ifndef MPG_SM_PAD
-#define MPG_SM_PAD 0
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // conv_small_kernel: fused convolution for layers with <= 8 input and <= 8 output channels per
-// segment.  One thread per output pixel holds the 8 output channels; every tap is one 16-byte
-// read per plane of the single G8 channel group (hi + lo -> fp32), the weights are wave-uniform
-// scalar loads.  HBM / L1 bound, fp32 arithmetic on fp32-grade activations.
+// segment.  One thread holds the output channels of a column of SM_RPT output pixels.  Per segment
+// the block converts its halo tile (hi + lo -> fp32) and the segment's dense weight table into LDS
+// once; every filter column then costs SM_RPT + kh - 1 pixel reads from LDS per thread, and the
+// weights are LDS broadcasts.  fp32 arithmetic on fp32-grade activations.
 // ---------------------------------------------------------------------------------------------
 struct SmallSeg {
     const char* x;
@@ -34,42 +30,42 @@ struct SmallArgs {
     char* y_g8;
 };
 
-__device__ __forceinline__ void g8_load8(const char* src, size_t plane_bytes, float (&v)[8]) {
-    const half8 hi = *reinterpret_cast<const half8*>(src);
-    const half8 lo = *reinterpret_cast<const half8*>(src + plane_bytes);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)hi[j] + (float)lo[j];
-}
-
 // block = 64 x 16 output pixels; a thread owns a COLUMN of four of them (rows 4 yg .. 4 yg + 3 at column lx), so that
-// consecutive lanes read consecutive 16-byte LDS words (no bank conflicts) and the rows a thread reads for one filter
+// consecutive lanes read consecutive LDS words (no bank conflicts) and the rows a thread reads for one filter
 // column serve all of its pixels: (4 + kh - 1) pixel reads per kx instead of 4 kh, and every tap's weight block --
-// LDS broadcasts of the dense [tap][CINB][COUT] table -- feeds four pixels.  Per segment the halo tile is converted to
-// fp32 ONCE into LDS as planes of four channels ([plane][row][col] float4, zero outside the image).
+// LDS broadcasts of the dense [tap][CS][COUT] table -- feeds four pixels.  Per segment the halo tile is converted to
+// fp32 ONCE into LDS, zero outside the image, CS = the segment's channels rounded up to 1, 2, 4 or 8 per pixel:
+// [row][col] of float, float2 or float4, and two such planes of float4 for 8 channels.
 #ifndef MPG_SM_RPT
 #define MPG_SM_RPT 4
 #endif
 constexpr int SM_TW = 64, SM_RPT = MPG_SM_RPT, SM_TH = 4 * SM_RPT, SM_KMAX = 7;
-#ifndef MPG_DIAG_SMALL
-#define MPG_DIAG_SMALL 0
-#endif
-#ifndef MPG_SMALL_INV
-#define MPG_SMALL_INV 0
-#endif
-#if MPG_DIAG_SMALL
-__device__ unsigned g_small_diag[2];
-#endif
+// Every global load of a block -- halo tile and weight tables -- is issued before the first of them is waited for, in
+// loops whose trip counts are known to the compiler: the passes of 256 threads over the largest tile and table.
+constexpr int passes(int n) { return (n + 255) / 256; }
+constexpr int SM_TILE_PASSES = passes((SM_TW + SM_KMAX - 1) * (SM_TH + SM_KMAX - 1));
+constexpr int SM_PAIR_PASSES = passes((SM_TW + 2 * (SM_KMAX - 1)) * (SM_TH + 2 * (SM_KMAX - 1)));   // input tile of two filters
+constexpr int SM_TAPS = SM_KMAX * SM_KMAX;
+// tables and tiles start on 16 bytes in LDS
+__host__ __device__ constexpr int up4(int n) { return (n + 3) & ~3; }
+// channels rounded up to 1, 2, 4, 8
+__host__ __device__ constexpr int chan_bound(int c) { return c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8; }
 
-// The <= 8 bias values of a small layer, read once per thread in front of every loop (uniform addresses; index clamped
-// to the last channel instead of a branch per value: nothing at or beyond bias + cout is read, and channels beyond cout
-// are never used).  Zeros without a bias.
+// A value that every thread of the launch reads and that was written before the launch: a scalar load.  Such a load is
+// no vector-memory operation, so a register that waits for it does not stand between the tile loads further down.
+__device__ __forceinline__ float uniform_load(const float* p) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) float*>(reinterpret_cast<uintptr_t>(p));
+}
+// The <= 8 bias values of a small layer, read once per wave in front of every loop (index clamped to the last channel
+// instead of a branch per value: nothing at or beyond bias + cout is read, and channels beyond cout are never used).
+// Zeros without a bias.
 template <int C>
 __device__ __forceinline__ void small_bias(const float* bias, int cout, float (&bq)[C]) {
 #pragma unroll
     for (int q = 0; q < C; ++q) bq[q] = 0.f;
     if (bias != nullptr) {
 #pragma unroll
-        for (int q = 0; q < C; ++q) bq[q] = bias[q < cout ? q : cout - 1];
+        for (int q = 0; q < C; ++q) bq[q] = uniform_load(bias + (q < cout ? q : cout - 1));
     }
 }
 // run f(std::integral_constant<int, act>): one uniform switch around code that holds a single activation
@@ -82,25 +78,235 @@ __device__ __forceinline__ void with_act(int act, F&& f) {
         default: f(std::integral_constant<int, MPG_ACT_NONE>{}); break;
     }
 }
+// run f(std::integral_constant<int, chan_bound(cin)>) for cin <= CMAX (1, 2, 4 or 8): one uniform switch per segment
+template <int CMAX, class F>
+__device__ __forceinline__ void with_chan_bound(int cin, F&& f) {
+    if (CMAX >= 8 && cin > 4) f(std::integral_constant<int, CMAX >= 8 ? 8 : CMAX>{});
+    else if (CMAX >= 4 && cin > 2) f(std::integral_constant<int, CMAX >= 4 ? 4 : CMAX>{});
+    else if (CMAX >= 2 && cin > 1) f(std::integral_constant<int, CMAX >= 2 ? 2 : CMAX>{});
+    else f(std::integral_constant<int, 1>{});
+}
 
-// COUT / CINB: output channels / input channels per segment rounded up to 1, 2, 4, 8 (compile-time loop bounds: the
-// weight table holds zeros beyond cin and cout, a G8 group holds zeros beyond its channels)
+// ---- weight tables: [tap][8][8] in memory -> dense [tap][CI][CO] in LDS ----
+template <int CI, int CO>
+struct TableLoads {
+    static constexpr int NPASS = passes(SM_TAPS * CI * CO);
+    float v[NPASS];
+};
+template <int CI, int CO>
+__device__ __forceinline__ float table_word(const float* w, int p) {
+    const int co = p % CO, ci = (p / CO) % CI, tap = p / (CO * CI);
+    return w[tap * 64 + ci * 8 + co];
+}
+template <int CI, int CO>
+__device__ __forceinline__ void table_issue(TableLoads<CI, CO>& t, const float* w, int n, int tid) {
+#pragma unroll
+    for (int i = 0; i < TableLoads<CI, CO>::NPASS; ++i) {
+        const int p = tid + 256 * i;
+        t.v[i] = 0.f;
+        if (p < n) t.v[i] = table_word<CI, CO>(w, p);
+    }
+}
+// MORE: the table may have more than SM_TAPS taps (the shortcut of a pair may be as large as both of its filters together)
+template <bool MORE, int CI, int CO>
+__device__ __forceinline__ void table_store(const TableLoads<CI, CO>& t, const float* w, float* wl, int n, int tid) {
+#pragma unroll
+    for (int i = 0; i < TableLoads<CI, CO>::NPASS; ++i) {
+        const int p = tid + 256 * i;
+        if (p < n) wl[p] = t.v[i];
+    }
+    if constexpr (MORE)
+        for (int p = tid + 256 * TableLoads<CI, CO>::NPASS; p < n; p += 256) wl[p] = table_word<CI, CO>(w, p);
+}
+
+// ---- halo tiles: G8 in memory -> fp32 in LDS ----
+// The words of a thread's pixels p = tid + 256 i of a tile: the first LC channels of the hi and of the lo plane.
+template <int LC, int NPASS>
+struct TileLoads {
+    typedef _Float16 hv __attribute__((ext_vector_type(LC)));
+    hv hi[NPASS], lo[NPASS];
+    unsigned inside;      // bit i: pixel i lies in the image (every other pixel of the tile is zero)
+};
+// tile of tw columns and npx pixels whose first pixel is (ty0, tx0) of the h x w image; the source is the image
+// shrunk by (upy, up) bits, ws pixels wide.  A pixel outside the image loads the nearest one inside (so every address
+// is one of the tensor) and is replaced by zero in tile_store; pixels at and beyond npx load nothing.
+template <int LC, int NPASS>
+__device__ __forceinline__ void tile_issue(TileLoads<LC, NPASS>& t, const char* base, size_t plane_bytes, int ws, int up, int upy,
+                                           int h, int w, int ty0, int tx0, int tw, int npx, int tid) {
+    typedef typename TileLoads<LC, NPASS>::hv hv;
+    const int qs = 256 / tw, rs = 256 - qs * tw;     // 256 pixels further: qs rows and rs columns
+    int hy = tid / tw, hx = tid - hy * tw;
+    t.inside = 0;
+#pragma unroll
+    for (int i = 0; i < NPASS; ++i) {
+        const int yy = ty0 + hy, xx = tx0 + hx;
+        const bool live = tid + 256 * i < npx;
+        if (live && yy >= 0 && yy < h && xx >= 0 && xx < w) t.inside |= 1u << i;
+        const int yc = min(max(yy, 0), h - 1), xc = min(max(xx, 0), w - 1);
+        const char* src = base + ((size_t)(yc >> upy) * ws + (xc >> up)) * 16;
+        t.hi[i] = hv{};
+        t.lo[i] = hv{};
+        if (live) {
+            t.hi[i] = *reinterpret_cast<const hv*>(src);
+            t.lo[i] = *reinterpret_cast<const hv*>(src + plane_bytes);
+        }
+        hx += rs;
+        hy += qs;
+        if (hx >= tw) { hx -= tw; ++hy; }
+    }
+}
+// hi + lo -> fp32, CS channels per pixel (CS <= LC) into the tile of plane_px pixels per plane
+template <int CS, int LC, int NPASS>
+__device__ __forceinline__ void tile_store(const TileLoads<LC, NPASS>& t, float* tile, int plane_px, int npx, int tid) {
+    static_assert(CS <= LC, "a tile pixel holds no more channels than were loaded");
+#pragma unroll
+    for (int i = 0; i < NPASS; ++i) {
+        const int p = tid + 256 * i;
+        if (p < npx) {
+            const bool in = (t.inside >> i) & 1;
+            float v[CS];
+#pragma unroll
+            for (int j = 0; j < CS; ++j) v[j] = in ? (float)t.hi[i][j] + (float)t.lo[i][j] : 0.f;
+            if constexpr (CS == 1) tile[p] = v[0];
+            if constexpr (CS == 2) reinterpret_cast<float2*>(tile)[p] = make_float2(v[0], v[1]);
+            if constexpr (CS >= 4) reinterpret_cast<float4*>(tile)[p] = make_float4(v[0], v[1], v[2], v[3]);
+            if constexpr (CS == 8) reinterpret_cast<float4*>(tile)[plane_px + p] = make_float4(v[4], v[5], v[6], v[7]);
+        }
+    }
+}
+// the CS channels of tile pixel idx
+template <int CS>
+__device__ __forceinline__ void tile_pixel(const float* tile, int plane_px, int idx, float (&r)[CS]) {
+    if constexpr (CS == 1) r[0] = tile[idx];
+    if constexpr (CS == 2) {
+        const float2 p = reinterpret_cast<const float2*>(tile)[idx];
+        r[0] = p.x; r[1] = p.y;
+    }
+    if constexpr (CS >= 4) {
+        const float4 p = reinterpret_cast<const float4*>(tile)[idx];
+        r[0] = p.x; r[1] = p.y; r[2] = p.z; r[3] = p.w;
+    }
+    if constexpr (CS == 8) {
+        const float4 p = reinterpret_cast<const float4*>(tile)[plane_px + idx];
+        r[4] = p.x; r[5] = p.y; r[6] = p.z; r[7] = p.w;
+    }
+}
+// CS channels of a pixel into the tile (the middle tile of a pair)
+template <int CS>
+__device__ __forceinline__ void tile_put(float* tile, int plane_px, int idx, const float (&v)[8]) {
+    if constexpr (CS == 1) tile[idx] = v[0];
+    if constexpr (CS == 2) reinterpret_cast<float2*>(tile)[idx] = make_float2(v[0], v[1]);
+    if constexpr (CS >= 4) reinterpret_cast<float4*>(tile)[idx] = make_float4(v[0], v[1], v[2], v[3]);
+    if constexpr (CS == 8) reinterpret_cast<float4*>(tile)[plane_px + idx] = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// Sums of one filter over a column of SM_RPT pixels: the thread's first row of the tile is `row0`, its column `col`
+// (both in tile coordinates of the first tap); wl = [tap][CS][COUTB].  KH, KW > 0: the filter's size, known to the
+// compiler (no branch in the sums); KH == 0: kh x kw <= SM_KMAX x SM_KMAX, decided while running.  Either way an output
+// is the same chain of fmaf: kx outer, then ky, then ci.
+template <int CS, int COUTB, int KH, int KW>
+__device__ __forceinline__ void small_column(const float* tile, int tw, int plane_px, int row0, int col, const float* wl,
+                                             int kh_run, int kw_run, float (&acc)[SM_RPT][COUTB]) {
+    constexpr int KHM = KH > 0 ? KH : SM_KMAX, NW = CS * COUTB;
+    const int kh = KH > 0 ? KH : kh_run, kw = KW > 0 ? KW : kw_run;
+    // a filter column of a small block is unrolled into the next, so that its pixel reads run under these sums
+    constexpr int UNROLL_KX = KW > 0 && NW <= 16 ? KW : 1;
+#pragma unroll UNROLL_KX
+    for (int kx = 0; kx < kw; ++kx) {
+        // the rows this thread's pixels see through filter column kx
+        float rows[SM_RPT + KHM - 1][CS];
+#pragma unroll
+        for (int r = 0; r < SM_RPT + KHM - 1; ++r)
+            if (KH > 0 || r < SM_RPT + kh - 1) tile_pixel<CS>(tile, plane_px, (row0 + r) * tw + col + kx, rows[r]);
+#pragma unroll
+        for (int ky = 0; ky < KHM; ++ky) {
+            if (KH > 0 || ky < kh) {
+                // the tap's [CS][COUTB] block: up to 16 weights at once in the widest reads their number allows (one
+                // ds_read_b128 is two input channels of a 2-channel output), a larger block one input channel at a time
+                const float* wt = wl + (ky * kw + kx) * NW;
+                constexpr int WG = NW <= 16 ? NW : COUTB;
+                constexpr int WQ = WG % 4 == 0 ? 4 : WG % 2 == 0 ? 2 : 1;
+#pragma unroll
+                for (int g0 = 0; g0 < NW; g0 += WG) {
+                    float wv[WG];
+#pragma unroll
+                    for (int q = 0; q < WG / WQ; ++q) {
+                        if constexpr (WQ == 4) {
+                            const float4 w4 = *reinterpret_cast<const float4*>(wt + g0 + 4 * q);
+                            wv[4 * q] = w4.x; wv[4 * q + 1] = w4.y; wv[4 * q + 2] = w4.z; wv[4 * q + 3] = w4.w;
+                        } else if constexpr (WQ == 2) {
+                            const float2 w2 = *reinterpret_cast<const float2*>(wt + g0 + 2 * q);
+                            wv[2 * q] = w2.x; wv[2 * q + 1] = w2.y;
+                        } else {
+                            wv[q] = wt[g0 + q];
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < WG / COUTB; ++c)
+#pragma unroll
+                        for (int j = 0; j < SM_RPT; ++j)
+#pragma unroll
+                            for (int co = 0; co < COUTB; ++co)
+                                acc[j][co] = fmaf(rows[j + ky][g0 / COUTB + c], wv[c * COUTB + co], acc[j][co]);
+                }
+            }
+        }
+    }
+}
+// the filter sizes of both generators' small layers are instantiated, every other size takes the run-time form
+template <int CS, int COUTB>
+__device__ __forceinline__ void small_filter(const float* tile, int tw, int plane_px, int row0, int col, const float* wl, int kh, int kw,
+                                             float (&acc)[SM_RPT][COUTB]) {
+    // (not for 8 -> 8 channels: with 64 weights per tap the instantiated sizes would cost a wave per SIMD in registers)
+    constexpr bool SIZES = CS * COUTB < 64;
+    if (SIZES && kh == 5 && kw == 5) small_column<CS, COUTB, SIZES ? 5 : 0, SIZES ? 5 : 0>(tile, tw, plane_px, row0, col, wl, kh, kw, acc);
+    else if (SIZES && kh == 1 && kw == 1) small_column<CS, COUTB, SIZES ? 1 : 0, SIZES ? 1 : 0>(tile, tw, plane_px, row0, col, wl, kh, kw, acc);
+    else small_column<CS, COUTB, 0, 0>(tile, tw, plane_px, row0, col, wl, kh, kw, acc);
+}
+
+// the thread's SM_RPT pixels of column x (rows y0 ..): fp32 NHWC and / or G8
+__device__ __forceinline__ void small_store(const float (&o)[SM_RPT][8], float* y, char* y_g8, int b, int h, int w, int cout, int y0, int x) {
+    const size_t plane_px = (size_t)h * w;
+#pragma unroll
+    for (int j = 0; j < SM_RPT; ++j) {
+        const int yy = y0 + j;
+        if (yy >= h) break;
+        const size_t pix = (size_t)yy * w + x;
+        if (y != nullptr) {
+            float* dst = y + ((size_t)b * plane_px + pix) * cout;
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (q < cout) dst[q] = o[j][q];
+        }
+        if (y_g8 != nullptr) {
+            half8 hi, lo;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                hi[q] = (_Float16)o[j][q];
+                lo[q] = (_Float16)(o[j][q] - (float)hi[q]);
+            }
+            char* dst = y_g8 + ((size_t)b * 2 * plane_px + pix) * 16;
+            *reinterpret_cast<half8*>(dst) = hi;
+            *reinterpret_cast<half8*>(dst + plane_px * 16) = lo;
+        }
+    }
+}
+
+// COUT: output channels rounded up to 1, 2, 4, 8; CINB: the same of the launch's widest segment, which sizes the LDS.
+// A segment works on its own channels rounded up (CS): the weight table holds zeros beyond cin and cout and a G8 group
+// holds zeros beyond its channels, so the terms left out of a narrow segment are fmaf(0, 0, acc) = acc (acc starts at
+// +0 and a sum of products that reaches zero from +0 is +0 in round-to-nearest, never -0).
 template <int COUT, int CINB>
 __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
-    constexpr int PL = (CINB + 3) / 4;                 // planes of four channels
-    constexpr int CP = CINB < 4 ? CINB : 4;            // channels used of a plane
-    float4* tile = reinterpret_cast<float4*>(small_lds);
+    float* tile = small_lds;
     float* wl = small_lds + a.tile_floats;
     const int tid = threadIdx.x;
     const int lx = tid % SM_TW, yg = tid / SM_TW;
     const int x0 = blockIdx.x * SM_TW, y0 = blockIdx.y * SM_TH, b = blockIdx.z;
-#if MPG_SMALL_INV
-    asm volatile("buffer_inv sc0 sc1" ::: "memory");
-#endif
     float bq[COUT];
     small_bias(a.bias, a.cout, bq);
-    const float amax = a.in_amax != nullptr ? *a.in_amax : 0.f;     // pow2_scale(0) == 1
+    const float amax = a.in_amax != nullptr ? uniform_load(a.in_amax) : 0.f;     // pow2_scale(0) == 1
     float acc[SM_RPT][COUT];
 #pragma unroll
     for (int j = 0; j < SM_RPT; ++j)
@@ -108,107 +314,27 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
         for (int co = 0; co < COUT; ++co) acc[j][co] = 0.f;
     for (int s = 0; s < a.nseg; ++s) {
         const SmallSeg& g = a.seg[s];
-        const size_t plane_bytes = (size_t)g.hs * g.ws * 16;
-        const char* base = g.x + ((size_t)b * g.cg_total + g.g_off) * 2 * plane_bytes;
-        const int tw = SM_TW + g.kw - 1, th = SM_TH + g.kh - 1;
-        if (s > 0) __syncthreads();
-        for (int p = tid; p < g.kh * g.kw * CINB * COUT; p += 256) {
-            const int co = p % COUT, ci = (p / COUT) % CINB, tap = p / (COUT * CINB);
-            wl[p] = g.w[tap * 64 + ci * 8 + co];
-        }
-        for (int p = tid; p < tw * th; p += 256) {
-            const int hy = p / tw, hx = p - hy * tw;
-            const int yy = y0 - g.pt + hy, xx = x0 - g.pl + hx;
-            float v[8];
-            if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) {
-                g8_load8(base + ((size_t)(yy >> g.upy) * g.ws + (xx >> g.up)) * 16, plane_bytes, v);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = 0.f;
-            }
-            tile[p] = make_float4(v[0], v[1], v[2], v[3]);
-            if (PL > 1) tile[th * tw + p] = make_float4(v[4], v[5], v[6], v[7]);
-        }
-        __syncthreads();
-        const int kh = g.kh;
-        for (int kx = 0; kx < g.kw; ++kx) {
-            // the rows this thread's four pixels see through filter column kx
-            float rows[SM_RPT + SM_KMAX - 1][CINB];
-#pragma unroll
-            for (int r = 0; r < SM_RPT + SM_KMAX - 1; ++r) {
-                if (r < SM_RPT + kh - 1) {
-                    const float4* src = tile + (yg * SM_RPT + r) * tw + lx + kx;
-                    const float4 p0 = src[0];
-                    rows[r][0] = p0.x;
-                    if constexpr (CP > 1) rows[r][1] = p0.y;
-                    if constexpr (CP > 2) { rows[r][2] = p0.z; rows[r][3] = p0.w; }
-                    if constexpr (PL > 1) {
-                        const float4 p1 = src[th * tw];
-                        rows[r][4] = p1.x; rows[r][5] = p1.y; rows[r][6] = p1.z; rows[r][7] = p1.w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int ky = 0; ky < SM_KMAX; ++ky) {
-                if (ky < kh) {
-                    const float* wt = wl + (ky * g.kw + kx) * (CINB * COUT);
-#pragma unroll
-                    for (int ci = 0; ci < CINB; ++ci) {
-                        float wv[COUT];
-                        if (COUT >= 4) {
-#pragma unroll
-                            for (int q = 0; q < COUT / 4; ++q) {
-                                const float4 w4 = *reinterpret_cast<const float4*>(wt + ci * COUT + 4 * q);
-                                wv[4 * q] = w4.x; wv[4 * q + 1] = w4.y; wv[4 * q + 2] = w4.z; wv[4 * q + 3] = w4.w;
-                            }
-                        } else if (COUT == 2) {
-                            const float2 w2 = *reinterpret_cast<const float2*>(wt + ci * 2);
-                            wv[0] = w2.x; wv[1] = w2.y;
-                        } else {
-                            wv[0] = wt[ci];
-                        }
-#pragma unroll
-                        for (int j = 0; j < SM_RPT; ++j)
-#pragma unroll
-                            for (int co = 0; co < COUT; ++co) acc[j][co] = fmaf(rows[j + ky][ci], wv[co], acc[j][co]);
-                    }
-                }
-            }
-        }
-#if MPG_DIAG_SMALL
-        {   // diagnostic: is this block's LDS still what it wrote?  (foreign writes into the allocation; checked for EVERY
-            // segment right after its sums, before the next segment overwrites the table and the tile)
+        with_chan_bound<CINB>(g.cin, [&](auto csc) {
+            constexpr int CS = decltype(csc)::value;
+            constexpr int LC = CS < 2 ? 2 : CS;      // channels loaded per pixel and plane: 4, 8 or 16 bytes
+            const size_t plane_bytes = (size_t)g.hs * g.ws * 16;
+            const char* base = g.x + ((size_t)b * g.cg_total + g.g_off) * 2 * plane_bytes;
+            const int tw = SM_TW + g.kw - 1, th = SM_TH + g.kh - 1;
+            const int nw = g.kh * g.kw * CS * COUT;
+            TableLoads<CS, COUT> tab;
+            TileLoads<LC, SM_TILE_PASSES> px;
+            tile_issue(px, base, plane_bytes, g.ws, g.up, g.upy, a.h, a.w, y0 - g.pt, x0 - g.pl, tw, tw * th, tid);
+            table_issue(tab, g.w, nw, tid);
+            if (s > 0) __syncthreads();      // the sums of the segment before this one have read the tile and the table
+            table_store<false>(tab, g.w, wl, nw, tid);
+            tile_store<CS>(px, tile, tw * th, tw * th, tid);
             __syncthreads();
-            unsigned bad_w = 0, bad_t = 0;
-            for (int p = tid; p < g.kh * g.kw * CINB * COUT; p += 256) {
-                const int co = p % COUT, ci = (p / COUT) % CINB, tap = p / (COUT * CINB);
-                if (wl[p] != g.w[tap * 64 + ci * 8 + co]) ++bad_w;
-            }
-            for (int p = tid; p < tw * th; p += 256) {
-                const int hy = p / tw, hx = p - hy * tw;
-                const int yy = y0 - g.pt + hy, xx = x0 - g.pl + hx;
-                float v[8];
-                if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) {
-                    g8_load8(base + ((size_t)(yy >> g.upy) * g.ws + (xx >> g.up)) * 16, plane_bytes, v);
-                } else {
-                    for (int q = 0; q < 8; ++q) v[q] = 0.f;
-                }
-                const float4 t0 = tile[p];
-                if (t0.x != v[0] || t0.y != v[1] || t0.z != v[2] || t0.w != v[3]) ++bad_t;
-                if (PL > 1) {
-                    const float4 t1 = tile[th * tw + p];
-                    if (t1.x != v[4] || t1.y != v[5] || t1.z != v[6] || t1.w != v[7]) ++bad_t;
-                }
-            }
-            if (bad_w) atomicAdd(&g_small_diag[0], bad_w);
-            if (bad_t) atomicAdd(&g_small_diag[1], bad_t);
-        }
-#endif
+            small_filter<CS, COUT>(tile, tw, tw * th, yg * SM_RPT, lx, wl, g.kh, g.kw, acc);
+        });
     }
     const int x = x0 + lx;
     if (x >= a.w) return;
     const float unscale = 1.f / mpg::pow2_scale(amax);
-    const size_t plane_px = (size_t)a.h * a.w;
     // the values of the thread's SM_RPT pixels under the launch's activation (the only code that differs between the
     // activations), then the stores
     float o[SM_RPT][8];
@@ -220,29 +346,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
             for (int q = 0; q < 8; ++q)
                 o[j][q] = (q < COUT && q < a.cout) ? mpg::apply_act(acc[j][q < COUT ? q : 0] * unscale + bq[q < COUT ? q : 0], ACT, a.leak) : 0.f;
     });
-#pragma unroll
-    for (int j = 0; j < SM_RPT; ++j) {
-        const int y = y0 + yg * SM_RPT + j;
-        if (y >= a.h) break;
-        const size_t pix = (size_t)y * a.w + x;
-        if (a.y != nullptr) {
-            float* dst = a.y + ((size_t)b * plane_px + pix) * a.cout;
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (q < a.cout) dst[q] = o[j][q];
-        }
-        if (a.y_g8 != nullptr) {
-            half8 hi, lo;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                hi[q] = (_Float16)o[j][q];
-                lo[q] = (_Float16)(o[j][q] - (float)hi[q]);
-            }
-            char* dst = a.y_g8 + ((size_t)b * 2 * plane_px + pix) * 16;
-            *reinterpret_cast<half8*>(dst) = hi;
-            *reinterpret_cast<half8*>(dst + plane_px * 16) = lo;
-        }
-    }
+    small_store(o, a.y, a.y_g8, b, a.h, a.w, a.cout, y0 + yg * SM_RPT, x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -273,56 +377,15 @@ struct PairArgs {
     int x_px, mid_px;              // pixels of the input tile / of the middle tile (LDS plane sizes)
 };
 
-// sums of one filter over a column of SM_RPT pixels: tile = planes of four channels [plane][row][col] (float4), the
-// thread's first row is `row0`, its column `col` (both in tile coordinates of the first tap); wl = [tap][CINB][COUTB]
-template <int CINB, int COUTB>
-__device__ __forceinline__ void small_column(const float4* tile, int tw, int plane_px, int row0, int col, const float* wl,
-                                             int kh, int kw, float (&acc)[SM_RPT][COUTB]) {
-    constexpr int PL = (CINB + 3) / 4, CP = CINB < 4 ? CINB : 4;
-    for (int kx = 0; kx < kw; ++kx) {
-        float rows[SM_RPT + SM_KMAX - 1][CINB];
-#pragma unroll
-        for (int r = 0; r < SM_RPT + SM_KMAX - 1; ++r) {
-            if (r < SM_RPT + kh - 1) {
-                const float4* src = tile + (row0 + r) * tw + col + kx;
-                const float4 p0 = src[0];
-                rows[r][0] = p0.x;
-                if constexpr (CP > 1) rows[r][1] = p0.y;
-                if constexpr (CP > 2) { rows[r][2] = p0.z; rows[r][3] = p0.w; }
-                if constexpr (PL > 1) {
-                    const float4 p1 = src[plane_px];
-                    rows[r][4] = p1.x; rows[r][5] = p1.y; rows[r][6] = p1.z; rows[r][7] = p1.w;
-                }
-            }
-        }
-#pragma unroll
-        for (int ky = 0; ky < SM_KMAX; ++ky) {
-            if (ky < kh) {
-                const float* wt = wl + (ky * kw + kx) * (CINB * COUTB);
-#pragma unroll
-                for (int ci = 0; ci < CINB; ++ci) {
-                    float wv[COUTB];
-#pragma unroll
-                    for (int co = 0; co < COUTB; ++co) wv[co] = wt[ci * COUTB + co];
-#pragma unroll
-                    for (int j = 0; j < SM_RPT; ++j)
-#pragma unroll
-                        for (int co = 0; co < COUTB; ++co) acc[j][co] = fmaf(rows[j + ky][ci], wv[co], acc[j][co]);
-                }
-            }
-        }
-    }
-}
-
 template <int CINB, int CMIDB, int COUTB>
 __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
-    constexpr int PLX = (CINB + 3) / 4, PLM = (CMIDB + 3) / 4;
-    float4* xt = reinterpret_cast<float4*>(small_lds);               // input tile: PLX planes of x_px pixels
-    float4* mt = xt + PLX * a.x_px;                                   // middle tile: PLM planes of mid_px pixels
-    float* wla = reinterpret_cast<float*>(mt + PLM * a.mid_px);       // [tap][CINB][CMIDB]
-    float* wlb = wla + a.kha * a.kwa * CINB * CMIDB;                  // [tap][CMIDB][COUTB]
-    float* wls = wlb + a.khb * a.kwb * CMIDB * COUTB;                 // [tap][CINB][COUTB]
+    const int na = a.kha * a.kwa * CINB * CMIDB, nb = a.khb * a.kwb * CMIDB * COUTB, ns = a.wsc != nullptr ? a.khs * a.kws * CINB * COUTB : 0;
+    float* xt = small_lds;                             // input tile: x_px pixels of CINB channels
+    float* mt = xt + up4(a.x_px * CINB);               // middle tile: mid_px pixels of CMIDB channels
+    float* wla = mt + up4(a.mid_px * CMIDB);           // [tap][CINB][CMIDB]
+    float* wlb = wla + up4(na);                        // [tap][CMIDB][COUTB]
+    float* wls = wlb + up4(nb);                        // [tap][CINB][COUTB]
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * SM_TW, y0 = blockIdx.y * SM_TH, b = blockIdx.z;
     float bqa[CMIDB], bqb[COUTB];
@@ -332,35 +395,22 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
     const int xw = mw + a.kwa - 1, xh = mh + a.kha - 1;               // input tile
     const int mx0 = x0 - a.plb, my0 = y0 - a.ptb;                     // image coordinates of the tiles' first pixels
     const int xx0 = mx0 - a.pla, xy0 = my0 - a.pta;
-    for (int p = tid; p < a.kha * a.kwa * CINB * CMIDB; p += 256) {
-        const int co = p % CMIDB, ci = (p / CMIDB) % CINB, tap = p / (CMIDB * CINB);
-        wla[p] = a.wa[tap * 64 + ci * 8 + co];
-    }
-    for (int p = tid; p < a.khb * a.kwb * CMIDB * COUTB; p += 256) {
-        const int co = p % COUTB, ci = (p / COUTB) % CMIDB, tap = p / (COUTB * CMIDB);
-        wlb[p] = a.wb[tap * 64 + ci * 8 + co];
-    }
-    if (a.wsc != nullptr)
-        for (int p = tid; p < a.khs * a.kws * CINB * COUTB; p += 256) {
-            const int co = p % COUTB, ci = (p / COUTB) % CINB, tap = p / (COUTB * CINB);
-            wls[p] = a.wsc[tap * 64 + ci * 8 + co];
-        }
     {
+        constexpr int LC = CINB < 2 ? 2 : CINB;
         const size_t plane_bytes = (size_t)a.hs * a.ws * 16;
         const char* base = a.x + ((size_t)b * a.cg_total + a.g_off) * 2 * plane_bytes;
-        for (int p = tid; p < xw * xh; p += 256) {
-            const int hy = p / xw, hx = p - hy * xw;
-            const int yy = xy0 + hy, xx = xx0 + hx;
-            float v[8];
-            if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.w) {
-                g8_load8(base + ((size_t)(yy >> a.upy) * a.ws + (xx >> a.up)) * 16, plane_bytes, v);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = 0.f;
-            }
-            xt[p] = make_float4(v[0], v[1], v[2], v[3]);
-            if (PLX > 1) xt[a.x_px + p] = make_float4(v[4], v[5], v[6], v[7]);
-        }
+        TableLoads<CINB, CMIDB> ta;
+        TableLoads<CMIDB, COUTB> tb;
+        TableLoads<CINB, COUTB> ts;
+        TileLoads<LC, SM_PAIR_PASSES> px;
+        table_issue(ta, a.wa, na, tid);
+        table_issue(tb, a.wb, nb, tid);
+        table_issue(ts, a.wsc, ns, tid);
+        tile_issue(px, base, plane_bytes, a.ws, a.up, a.upy, a.h, a.w, xy0, xx0, xw, xw * xh, tid);
+        table_store<false>(ta, a.wa, wla, na, tid);
+        table_store<false>(tb, a.wb, wlb, nb, tid);
+        table_store<true>(ts, a.wsc, wls, ns, tid);
+        tile_store<CINB>(px, xt, a.x_px, xw * xh, tid);
     }
     __syncthreads();
     // ---- stage A on the middle tile: columns of SM_RPT pixels, mw x ceil(mh / SM_RPT) of them ----
@@ -372,7 +422,7 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
         for (int j = 0; j < SM_RPT; ++j)
 #pragma unroll
             for (int c = 0; c < CMIDB; ++c) acc[j][c] = 0.f;
-        small_column<CINB, CMIDB>(xt, xw, a.x_px, rg * SM_RPT, col, wla, a.kha, a.kwa, acc);
+        small_filter<CINB, CMIDB>(xt, xw, a.x_px, rg * SM_RPT, col, wla, a.kha, a.kwa, acc);
         float o[SM_RPT][8];
         with_act(a.act_a, [&](auto actc) {
             constexpr int ACT = decltype(actc)::value;
@@ -382,14 +432,15 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
                 for (int c = 0; c < 8; ++c)
                     o[j][c] = c < CMIDB ? mpg::apply_act(acc[j][c < CMIDB ? c : 0] + bqa[c < CMIDB ? c : 0], ACT, a.leak_a) : 0.f;
         });
+        const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < SM_RPT; ++j) {
             const int row = rg * SM_RPT + j;
             if (row < mh) {
                 const int yy = my0 + row, xx = mx0 + col;
                 const bool in = yy >= 0 && yy < a.h && xx >= 0 && xx < a.w;
-                mt[row * mw + col] = in ? make_float4(o[j][0], o[j][1], o[j][2], o[j][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (PLM > 1) mt[a.mid_px + row * mw + col] = in ? make_float4(o[j][4], o[j][5], o[j][6], o[j][7]) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (in) tile_put<CMIDB>(mt, a.mid_px, row * mw + col, o[j]);
+                else tile_put<CMIDB>(mt, a.mid_px, row * mw + col, zero);
             }
         }
     }
@@ -401,12 +452,11 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
     for (int j = 0; j < SM_RPT; ++j)
 #pragma unroll
         for (int c = 0; c < COUTB; ++c) acc[j][c] = 0.f;
-    small_column<CMIDB, COUTB>(mt, mw, a.mid_px, yg * SM_RPT, lx, wlb, a.khb, a.kwb, acc);
+    small_filter<CMIDB, COUTB>(mt, mw, a.mid_px, yg * SM_RPT, lx, wlb, a.khb, a.kwb, acc);
     if (a.wsc != nullptr)     // the shortcut reads the input tile; its first tap sits at (ptb + pta - pts, plb + pla - pls) of it
-        small_column<CINB, COUTB>(xt, xw, a.x_px, yg * SM_RPT + a.ptb + a.pta - a.pts, lx + a.plb + a.pla - a.pls, wls, a.khs, a.kws, acc);
+        small_filter<CINB, COUTB>(xt, xw, a.x_px, yg * SM_RPT + a.ptb + a.pta - a.pts, lx + a.plb + a.pla - a.pls, wls, a.khs, a.kws, acc);
     const int x = x0 + lx;
     if (x >= a.w) return;
-    const size_t plane_px = (size_t)a.h * a.w;
     float o[SM_RPT][8];
     with_act(a.act_b, [&](auto actc) {
         constexpr int ACT = decltype(actc)::value;
@@ -416,29 +466,7 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
             for (int q = 0; q < 8; ++q)
                 o[j][q] = (q < COUTB && q < a.cout) ? mpg::apply_act(acc[j][q < COUTB ? q : 0] + bqb[q < COUTB ? q : 0], ACT, a.leak_b) : 0.f;
     });
-#pragma unroll
-    for (int j = 0; j < SM_RPT; ++j) {
-        const int y = y0 + yg * SM_RPT + j;
-        if (y >= a.h) break;
-        const size_t pix = (size_t)y * a.w + x;
-        if (a.y != nullptr) {
-            float* dst = a.y + ((size_t)b * plane_px + pix) * a.cout;
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (q < a.cout) dst[q] = o[j][q];
-        }
-        if (a.y_g8 != nullptr) {
-            half8 hi, lo;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                hi[q] = (_Float16)o[j][q];
-                lo[q] = (_Float16)(o[j][q] - (float)hi[q]);
-            }
-            char* dst = a.y_g8 + ((size_t)b * 2 * plane_px + pix) * 16;
-            *reinterpret_cast<half8*>(dst) = hi;
-            *reinterpret_cast<half8*>(dst + plane_px * 16) = lo;
-        }
-    }
+    small_store(o, a.y, a.y_g8, b, a.h, a.w, a.cout, y0 + yg * SM_RPT, x);
 }
 
 }  // namespace
@@ -447,7 +475,8 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
 int mpg::conv::launch_small(hipStream_t stream, const mpg_conv_desc* d) {
     SmallArgs sa;
     sa.n = d->n; sa.h = d->h; sa.w = d->w; sa.cout = d->cout; sa.nseg = d->nseg;
-    int cmax = 1, tmax = 1, tile_px = 0;
+    const int cob = chan_bound(d->cout);
+    int cmax = 1, tile_floats = 0, table_floats = 0;
     for (int s = 0; s < d->nseg; ++s) {
         if (const int rc = check_segment(d, s)) return rc;
         const mpg_conv_seg& g = d->seg[s];
@@ -458,19 +487,18 @@ int mpg::conv::launch_small(hipStream_t stream, const mpg_conv_desc* d) {
         o.pt = pad_before(g.kh, g.pad_hi); o.pl = pad_before(g.kw, g.pad_hi);
         o.hs = d->h >> o.upy; o.ws = d->w >> o.up; o.cin = g.cin;
         cmax = g.cin > cmax ? g.cin : cmax;
-        tmax = g.kh * g.kw > tmax ? g.kh * g.kw : tmax;
-        const int px = (SM_TH + g.kh - 1) * (SM_TW + g.kw - 1);
-        tile_px = px > tile_px ? px : tile_px;
+        tile_floats = std::max(tile_floats, (SM_TH + g.kh - 1) * (SM_TW + g.kw - 1));
+        table_floats = std::max(table_floats, g.kh * g.kw);
     }
     for (int s = d->nseg; s < MPG_MAX_SEG; ++s) sa.seg[s] = sa.seg[0];
     sa.bias = d->bias; sa.in_amax = d->in_amax; sa.act = d->act; sa.leak = d->leak;
     sa.y = d->y; sa.y_g8 = (char*)d->y_g8;
     MPG_REQUIRE((((uintptr_t)d->y_g8) & 15) == 0, "mpg_conv2d_fused: misaligned output");
     const dim3 grid((unsigned)((d->w + SM_TW - 1) / SM_TW), (unsigned)((d->h + SM_TH - 1) / SM_TH), (unsigned)d->n);
-    const int cob = d->cout == 1 ? 1 : d->cout == 2 ? 2 : d->cout <= 4 ? 4 : 8;
-    const int cib = cmax == 1 ? 1 : cmax == 2 ? 2 : cmax <= 4 ? 4 : 8;
-    sa.tile_floats = tile_px * 4 * ((cib + 3) / 4);       // one or two planes of four channels
-    const size_t lds = ((size_t)sa.tile_floats + (size_t)tmax * cib * cob) * sizeof(float) + MPG_SM_PAD;
+    // the LDS holds the largest tile and the largest table at the widest segment's channel bound
+    const int cib = chan_bound(cmax);
+    sa.tile_floats = up4(tile_floats * cib);
+    const size_t lds = ((size_t)sa.tile_floats + (size_t)table_floats * cib * cob) * sizeof(float);
     switch (cob * 16 + cib) {
 #define MPG_SMALL(CO, CI) \
     case CO * 16 + CI: hipLaunchKernelGGL((conv_small_kernel<CO, CI>), grid, dim3(256), lds, stream, sa); break;
@@ -524,8 +552,9 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
     a.mid_px = mw * (mgroups * SM_RPT + a.khb - 1);
     // compile-time channel bounds: cin in {1, 4, 8}, cmid in {2, 8}, cout in {1, 8}
     const int ci = d->cin == 1 ? 1 : d->cin <= 4 ? 4 : 8, cm = d->cmid <= 2 ? 2 : 8, co = d->cout == 1 ? 1 : 8;
-    const size_t lds = ((size_t)((ci + 3) / 4) * a.x_px + (size_t)((cm + 3) / 4) * a.mid_px) * 16 +
-                       ((size_t)a.kha * a.kwa * ci * cm + (size_t)a.khb * a.kwb * cm * co + (size_t)a.khs * a.kws * ci * co) * sizeof(float);
+    // the kernel's carving of the LDS: two tiles, three tables, each rounded up to 16 bytes
+    const size_t lds = ((size_t)up4(a.x_px * ci) + up4(a.mid_px * cm) + up4(a.kha * a.kwa * ci * cm) + up4(a.khb * a.kwb * cm * co) +
+                        up4(d->wpack_s ? a.khs * a.kws * ci * co : 0)) * sizeof(float);
     MPG_REQUIRE(lds <= LDS_MAX, "mpg_conv2d_small_pair: LDS budget %zu exceeds 160 KiB", lds);
     const dim3 grid((unsigned)((d->w + SM_TW - 1) / SM_TW), (unsigned)((d->h + SM_TH - 1) / SM_TH), (unsigned)d->n);
     hipError_t le = hipSuccess;
@@ -541,9 +570,3 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
     if (le != hipSuccess) return mpg::hip_check(le, "mpg_conv2d_small_pair: hipFuncSetAttribute(dynamic LDS)");
     MPG_LAUNCH_CHECK("conv_small_pair_kernel");
 }
-
-#if MPG_DIAG_SMALL
-extern "C" int mpg_debug_small_diag(unsigned* out2) {
-    return hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_small_diag), 8) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -28,10 +28,3 @@ for rep in range(3):
                 idx[:, 2].min(), idx[:, 2].max()))
         else:
             print("rep %d volume %d: identical" % (rep, i))
-import ctypes, os
-if os.environ.get("MPGAN_LIB_OVERRIDE", "").endswith("diag.so"):
-    from mpgan_amd import _lib
-    L = ctypes.CDLL(os.environ["MPGAN_LIB_OVERRIDE"])
-    buf = (ctypes.c_uint * 2)()
-    torch.cuda.synchronize()
-    print("rc", L.mpg_debug_small_diag(buf), "small-kernel LDS check: bad weights %d, bad tile words %d" % (buf[0], buf[1]))

@@ -34,8 +34,3 @@ for rep in range(10):
                 rep, i, i % k, idx.shape[0], float(d.max()), int(idx[:, 0].min()), int(idx[:, 0].max()),
                 int(idx[:, 1].min()), int(idx[:, 1].max()), int(idx[:, 2].min()), int(idx[:, 2].max())))
 print("lanes", k, "mode", mode, "mismatching calls:", bad, "of", 40 * k)
-import ctypes, os
-if os.environ.get("MPGAN_LIB_OVERRIDE", "").endswith("diag.so"):
-    L = ctypes.CDLL(os.environ["MPGAN_LIB_OVERRIDE"])
-    buf = (ctypes.c_uint * 2)()
-    print("rc", L.mpg_debug_small_diag(buf), "small-kernel LDS check: bad weights %d, bad tile words %d" % (buf[0], buf[1]))
