@@ -166,7 +166,9 @@ int mpg_conv2d_fused_window(mpg_stream_t stream, const mpg_conv_desc* desc, int 
  * (resBlock 0 and 3 of gen_resnet, 1 -> 2 -> 8 and 8 -> 2 -> 1 channels: GAN/multipassGAN-4x.py:505-526,560,564).
  * The middle tensor stays in LDS (as two mpg_conv2d_fused launches it made a round trip through HBM).  fp32
  * arithmetic on the exact (hi16 + lo16) inputs whatever `prec` says; wpack_* come from mpg_conv_pack_weights
- * with that `prec` (the fp32 tables of small layers follow the matrix-core image).  Odd filters only. */
+ * with that `prec` (the fp32 tables of small layers follow the matrix-core image).  Odd filters only, each of the
+ * three at most 7x7 (what mpg_conv_pack_weights packs); the shortcut also no larger than kh_a + kh_b - 1 by
+ * kw_a + kw_b - 1, the input tile of the two filters.  Anything else is MPG_ERR_ARG, and nothing is launched. */
 typedef struct mpg_small_pair_desc {
     int32_t n, h, w;          /* output batch / height / width */
     const void* x;            /* G8 input [N][cgroups][2][H>>up_log2][W>>up_log2][8] ([H][W>>up_log2] with up_x_only); one
@@ -179,7 +181,7 @@ typedef struct mpg_small_pair_desc {
     float   leak_a;
     const void* wpack_b;      /* conv_b: kh_b x kw_b, cmid -> cout */
     int32_t kh_b, kw_b;
-    const void* wpack_s;      /* shortcut conv_s: kh_s x kw_s, cin -> cout, or NULL */
+    const void* wpack_s;      /* shortcut conv_s: kh_s x kw_s (odd, 1..7), cin -> cout, or NULL */
     int32_t kh_s, kw_s;
     const float* bias_b;      /* [cout] or NULL (bias of conv_b plus bias of conv_s) */
     int32_t act_b;

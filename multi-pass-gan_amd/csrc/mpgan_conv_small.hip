@@ -107,16 +107,14 @@ __device__ __forceinline__ void table_issue(TableLoads<CI, CO>& t, const float* 
         if (p < n) t.v[i] = table_word<CI, CO>(w, p);
     }
 }
-// MORE: the table may have more than SM_TAPS taps (the shortcut of a pair may be as large as both of its filters together)
-template <bool MORE, int CI, int CO>
-__device__ __forceinline__ void table_store(const TableLoads<CI, CO>& t, const float* w, float* wl, int n, int tid) {
+// (no table has more than SM_TAPS taps: the host code refuses larger filters, the shortcut of a pair included)
+template <int CI, int CO>
+__device__ __forceinline__ void table_store(const TableLoads<CI, CO>& t, float* wl, int n, int tid) {
 #pragma unroll
     for (int i = 0; i < TableLoads<CI, CO>::NPASS; ++i) {
         const int p = tid + 256 * i;
         if (p < n) wl[p] = t.v[i];
     }
-    if constexpr (MORE)
-        for (int p = tid + 256 * TableLoads<CI, CO>::NPASS; p < n; p += 256) wl[p] = table_word<CI, CO>(w, p);
 }
 
 // ---- halo tiles: G8 in memory -> fp32 in LDS ----
@@ -326,7 +324,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(SmallArgs a) {
             tile_issue(px, base, plane_bytes, g.ws, g.up, g.upy, a.h, a.w, y0 - g.pt, x0 - g.pl, tw, tw * th, tid);
             table_issue(tab, g.w, nw, tid);
             if (s > 0) __syncthreads();      // the sums of the segment before this one have read the tile and the table
-            table_store<false>(tab, g.w, wl, nw, tid);
+            table_store(tab, wl, nw, tid);
             tile_store<CS>(px, tile, tw * th, tw * th, tid);
             __syncthreads();
             small_filter<CS, COUT>(tile, tw, tw * th, yg * SM_RPT, lx, wl, g.kh, g.kw, acc);
@@ -407,9 +405,9 @@ __global__ __launch_bounds__(256) void conv_small_pair_kernel(PairArgs a) {
         table_issue(tb, a.wb, nb, tid);
         table_issue(ts, a.wsc, ns, tid);
         tile_issue(px, base, plane_bytes, a.ws, a.up, a.upy, a.h, a.w, xy0, xx0, xw, xw * xh, tid);
-        table_store<false>(ta, a.wa, wla, na, tid);
-        table_store<false>(tb, a.wb, wlb, nb, tid);
-        table_store<true>(ts, a.wsc, wls, ns, tid);
+        table_store(ta, wla, na, tid);
+        table_store(tb, wlb, nb, tid);
+        table_store(ts, wls, ns, tid);
         tile_store<CINB>(px, xt, a.x_px, xw * xh, tid);
     }
     __syncthreads();
@@ -526,6 +524,9 @@ extern "C" int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_d
     MPG_REQUIRE(d->wpack_s == nullptr || (d->kh_s >= 1 && d->kh_s <= d->kh_a + d->kh_b - 1 && d->kw_s >= 1 && d->kw_s <= d->kw_a + d->kw_b - 1 &&
                                           (d->kh_s & 1) && (d->kw_s & 1) && ((d->kh_a + d->kh_b) & 1) == 0 && ((d->kw_a + d->kw_b) & 1) == 0),
                 "mpg_conv2d_small_pair: the shortcut filter must be odd and fit inside the input tile of two odd filters");
+    // (no larger filter can be packed, and the sums run over at most SM_KMAX filter rows)
+    MPG_REQUIRE(d->wpack_s == nullptr || (d->kh_s <= SM_KMAX && d->kw_s <= SM_KMAX), "mpg_conv2d_small_pair: shortcut filter %d x %d (1..7)",
+                d->kh_s, d->kw_s);
     MPG_REQUIRE(d->g_off >= 0 && d->g_off < d->cgroups, "mpg_conv2d_small_pair: channel-group range");
     MPG_REQUIRE(d->up_x_only == 0 || d->up_x_only == 1, "mpg_conv2d_small_pair: up_x_only %d (0 or 1)", d->up_x_only);
     MPG_REQUIRE(d->up_log2 >= 0 && d->up_log2 <= 4 && (d->up_x_only || (d->h % (1 << d->up_log2)) == 0) && (d->w % (1 << d->up_log2)) == 0,
