@@ -551,8 +551,13 @@ int mpg_maccormack(mpg_stream_t stream, const float* source, const float* forwar
  *     is applied to the interpolated channels (vector components rotate / scale with the grid, :700-760,846-856).
  *   mpg_tile_orient: crop [off, off + size) of src, axes permuted / reversed (the composed np.rot90 / np.flip of
  *     :762-806), channels permuted / negated (chan_map, chan_sign: the vector components follow the turn).
+ *   Both take 1 <= c <= MPG_TILE_MAX_CHANNELS packed channels (more: MPG_ERR_ARG, nothing launched).  The widest tile
+ *     the drivers cut is 'd,vx,vy,vz,d,d' x 3 coherent frames = 18 (the first 8x network with useVelocities and
+ *     add_adj_idcs); 24 leaves room for a seventh and eighth channel per frame, and the c x c mix, passed by value,
+ *     keeps resample_kernel's arguments at 2.4 KiB of the 4 KiB a kernel may take.
  *   mpg_semilagr_positions: getSemiLagrPosBatch (:1345-1378), 2D: vel [n_batch,h,w,3] (MAC, x,y,z), dt [n_batch] ->
  *     pos [n_batch, n_out, n_out, 2] = (y, x) - v dt. */
+#define MPG_TILE_MAX_CHANNELS 24
 int mpg_tile_gather(mpg_stream_t stream, const float* frames, int n_frames, int z, int y, int x, int cf,
                     const int* table, int n_tiles, int tz, int ty, int tx, int c, float* out);
 int mpg_resample_affine(mpg_stream_t stream, const float* src, int zs, int ys, int xs, int c, float* dst, int zd, int yd,

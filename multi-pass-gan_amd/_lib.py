@@ -19,6 +19,7 @@ G8_F16 = 0
 MAX_SEG = 4
 WGRAD_PLAN_INTS, WGRAD_FORM_ROW, WGRAD_FORM_RING = 24, 0, 1                # MPG_WGRAD_* of include/mpgan.h
 DEFLATE_UNIT, DEFLATE_SLOT, DEFLATE_SLAB = 32768, 32768 + 16, 64 << 20    # MPG_DEFLATE_* of include/mpgan.h
+TILE_MAX_CHANNELS = 24                                                     # MPG_TILE_MAX_CHANNELS of include/mpgan.h
 
 _ACT_IDS = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH}
 

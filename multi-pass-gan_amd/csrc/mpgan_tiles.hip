@@ -31,9 +31,10 @@ struct ResampleArgs {
     int zs, ys, xs, c;          // source [zs,ys,xs,c]
     int zd, yd, xd;             // destination
     double m[9], off[3];        // source coordinate = m * (z,y,x)_dst + off   (float64, like scipy)
-    float mix[12 * 12];         // out channel i = sum_k mix[i*c + k] * interpolated channel k
+    float mix[MPG_TILE_MAX_CHANNELS * MPG_TILE_MAX_CHANNELS];   // out channel i = sum_k mix[i*c + k] * interpolated channel k
     int use_mix;
 };
+static_assert(sizeof(ResampleArgs) + 2 * sizeof(void*) <= 4096, "resample_kernel: more than 4 KiB of kernel arguments");
 
 // scipy.ndimage order-1 interpolation with mode 'constant', cval 0: a destination element whose source coordinate leaves
 // [0, n-1] on any axis is 0 (no tolerance -- scipy.ndimage.zoom itself zeroes its last row when (n-1)/(N-1) * (N-1)
@@ -59,7 +60,7 @@ __global__ void resample_kernel(const float* __restrict__ src, ResampleArgs a, f
         i1[k] = min(i0[k] + 1, dims[k] - 1);
         w[k] = (float)(cc - fl);
     }
-    float val[12];
+    float val[MPG_TILE_MAX_CHANNELS];
     for (int c = 0; c < a.c; ++c) val[c] = 0.f;
     if (inside) {
 #pragma unroll
@@ -91,8 +92,8 @@ struct OrientArgs {
     int perm[3];                // output axis k runs along source axis perm[k] of the CROPPED, not yet turned array
     int flip[3];                // ... backwards if flip[k]
     int cz, cy, cx;             // crop size in source axis order
-    int cmap[12];
-    float csign[12];
+    int cmap[MPG_TILE_MAX_CHANNELS];
+    float csign[MPG_TILE_MAX_CHANNELS];
 };
 
 // the final crop of a tile, followed by the composed quarter turns / flips (an axis permutation with reversals) and the
@@ -179,14 +180,15 @@ extern "C" int mpg_tile_gather(mpg_stream_t stream, const float* frames, int n_f
 extern "C" int mpg_resample_affine(mpg_stream_t stream, const float* src, int zs, int ys, int xs, int c, float* dst, int zd, int yd,
                                    int xd, const double* matrix9, const double* offset3, const float* channel_mix) {
     MPG_REQUIRE(src && dst && matrix9 && offset3, "mpg_resample_affine: null pointer");
-    MPG_REQUIRE(zs >= 1 && ys >= 1 && xs >= 1 && zd >= 1 && yd >= 1 && xd >= 1 && c >= 1 && c <= 12,
-                "mpg_resample_affine: bad shape (1..12 channels)");
+    MPG_REQUIRE(zs >= 1 && ys >= 1 && xs >= 1 && zd >= 1 && yd >= 1 && xd >= 1 && c >= 1 &&
+                    c <= MPG_TILE_MAX_CHANNELS, "mpg_resample_affine: bad shape (1..%d channels)", MPG_TILE_MAX_CHANNELS);
     ResampleArgs a;
     a.zs = zs; a.ys = ys; a.xs = xs; a.c = c; a.zd = zd; a.yd = yd; a.xd = xd;
     for (int i = 0; i < 9; ++i) a.m[i] = matrix9[i];
     for (int i = 0; i < 3; ++i) a.off[i] = offset3[i];
     a.use_mix = channel_mix != nullptr;
-    for (int i = 0; i < 144; ++i) a.mix[i] = (channel_mix != nullptr && i < c * c) ? channel_mix[i] : 0.f;
+    for (int i = 0; i < MPG_TILE_MAX_CHANNELS * MPG_TILE_MAX_CHANNELS; ++i)
+        a.mix[i] = (channel_mix != nullptr && i < c * c) ? channel_mix[i] : 0.f;
     const size_t total = (size_t)zd * yd * xd;
     hipLaunchKernelGGL(resample_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, src, a, dst);
     MPG_LAUNCH_CHECK("resample_kernel");
@@ -196,7 +198,7 @@ extern "C" int mpg_tile_orient(mpg_stream_t stream, const float* src, int zs, in
                                const int* crop_size3, const int* perm3, const int* flip3, const int* chan_map,
                                const float* chan_sign, float* dst) {
     MPG_REQUIRE(src && dst && crop_off3 && crop_size3 && perm3 && flip3, "mpg_tile_orient: null pointer");
-    MPG_REQUIRE(c >= 1 && c <= 12, "mpg_tile_orient: 1..12 channels");
+    MPG_REQUIRE(c >= 1 && c <= MPG_TILE_MAX_CHANNELS, "mpg_tile_orient: 1..%d channels", MPG_TILE_MAX_CHANNELS);
     OrientArgs a;
     a.zs = zs; a.ys = ys; a.xs = xs; a.c = c;
     a.z0 = crop_off3[0]; a.y0 = crop_off3[1]; a.x0 = crop_off3[2];
@@ -211,7 +213,7 @@ extern "C" int mpg_tile_orient(mpg_stream_t stream, const float* src, int zs, in
                 "mpg_tile_orient: crop leaves the source");
     const int csz[3] = {a.cz, a.cy, a.cx};
     a.dz = csz[a.perm[0]]; a.dy = csz[a.perm[1]]; a.dx = csz[a.perm[2]];
-    for (int k = 0; k < 12; ++k) {
+    for (int k = 0; k < MPG_TILE_MAX_CHANNELS; ++k) {
         a.cmap[k] = (chan_map != nullptr && k < c) ? chan_map[k] : k;
         a.csign[k] = (chan_sign != nullptr && k < c) ? chan_sign[k] : 1.f;
         if (k < c) MPG_REQUIRE(a.cmap[k] >= 0 && a.cmap[k] < c, "mpg_tile_orient: chan_map[%d]", k);

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/tile_golden.npz by importing the reference's TileCreator
+"""Generates tests/golden/tile_golden.npz and tile_golden_t3.npz (tile_scenarios.FIXTURE_OF says which scenario goes
+where; tile_golden.npz comes out byte for byte as committed) by importing the reference's TileCreator
 (/root/reference/tools_wscale/tilecreator_t.py, TensorFlow-free) and running it on small seeded
 frames.  Run in the build container only:
 
@@ -24,21 +25,23 @@ sys.path.insert(0, "/root/reference/tools_wscale")
 warnings.simplefilter("ignore")
 
 import tilecreator_t as REF  # noqa: E402
-from tile_scenarios import SCENARIOS, make_frames, run_scenario  # noqa: E402
+from tile_scenarios import FIXTURE_OF, FIXTURES, SCENARIOS, make_frames, run_scenario  # noqa: E402
 
 
 def main():
-    out = {}
+    out = {f: {} for f in FIXTURES}
     for name, sc in SCENARIOS.items():
         low, high = make_frames(sc)
-        out[name + "/low"], out[name + "/high"] = low, high
+        dst = out[FIXTURE_OF[name]]
+        dst[name + "/low"], dst[name + "/high"] = low, high
         with contextlib.redirect_stdout(io.StringIO()):
             res = run_scenario(REF, sc, low, high, random, np)
         for k, v in res.items():
-            out[name + "/" + k] = v
+            dst[name + "/" + k] = v
         print(name, {k: np.asarray(v).shape for k, v in res.items()})
-    np.savez_compressed(os.path.join(HERE, "tile_golden.npz"), **out)
-    print("wrote", os.path.join(HERE, "tile_golden.npz"), os.path.getsize(os.path.join(HERE, "tile_golden.npz")), "bytes")
+    for f in FIXTURES:
+        np.savez_compressed(os.path.join(HERE, f), **out[f])
+        print("wrote", os.path.join(HERE, f), os.path.getsize(os.path.join(HERE, f)), "bytes")
 
 
 if __name__ == "__main__":

@@ -26,6 +26,37 @@ SCENARIOS = {
                       dens_min=0.02, sparse=False, calls=("batch",)),
 }
 
+# Augmented coherent frames (tile_t = dim_t > 1) with a free rotation and a scaling: what getTempoinput / gettempo of
+# the training drivers draw.  Vector channels of both signs; sim 16 holds the oversized crop ceil(8 * 1.5 / 0.85) = 15.
+# These batches live in tile_golden_t3.npz (FIXTURE_OF), the earlier ones stay in tile_golden.npz.
+_AUG_T3 = dict(dim=2, tile=8, sim=16, upres=2, dim_t=3, frames=3, dens_min=0.02, sparse=False, signed=True,
+               aug=dict(rot=2, minScale=0.85, maxScale=1.15, flip=True), calls=("aug_t3", "tempo_aug"))
+SCENARIOS.update({
+    "tc2d_t3_aug": dict(_AUG_T3, low="d,vx,vy,vz", high="d"),
+    # 6 channels x 3 frames = 18 packed channels: the first 8x network with useVelocities 1 add_adj_idcs 1 ...
+    "tc2d_t3_aug18": dict(_AUG_T3, low="d,vx,vy,vz,d,d", high="d"),
+    # ... and the later 8x networks
+    "tc2d_t3_aug18_hh": dict(_AUG_T3, low="d,vx,vy,vz,d,d", high="d,d"),
+    # vectors on the high side too (tempo needs a scalar high layout: tiles only)
+    "tc2d_t3_aug_vhigh": dict(_AUG_T3, low="d,vx,vy,vz", high="d,vx,vy,vz", calls=("aug_t3",)),
+    # 3D coherent pairs: the only case where the rotation of the vector components is a full 3x3 quaternion rotation
+    "tc3d_t2_aug": dict(dim=3, tile=4, sim=8, upres=2, dim_t=2, frames=3, low="d,vx,vy,vz", high="d", dens_min=0.02,
+                        sparse=False, signed=True, aug=dict(rot=2, minScale=0.9, maxScale=1.1, flip=True),
+                        calls=("aug_t2_3d",)),
+})
+FIXTURE_OF = {name: "tile_golden_t3.npz" if sc.get("signed") else "tile_golden.npz" for name, sc in SCENARIOS.items()}
+FIXTURES = sorted(set(FIXTURE_OF.values()))
+
+
+def load_golden(here):
+    """every entry of the fixture files as one dict"""
+    import os
+    gold = {}
+    for f in FIXTURES:
+        with np.load(os.path.join(here, f)) as z:
+            gold.update({k: z[k] for k in z.files})
+    return gold
+
 
 def make_frames(sc):
     rng = np.random.default_rng(abs(hash_name(sc)) % (2 ** 31))
@@ -39,6 +70,13 @@ def make_frames(sc):
     high = rng.random((sc["frames"], zh, s * upv[1], s * upv[2], ch)).astype(np.float32)
     if sc["sparse"]:
         low[:, :, :, : s // 2, 0::4] *= 0.05
+    if sc.get("signed"):        # vector components in [-1, 1); scenarios without the flag keep their bytes
+        for arr, layout in ((low, sc["low"]), (high, sc["high"])):
+            keys = layout.split(",")
+            for f in range(sc["dim_t"]):
+                for i, k in enumerate(keys):
+                    if k[0] in "vx":
+                        arr[..., f * len(keys) + i] = arr[..., f * len(keys) + i] * np.float32(2) - np.float32(1)
     return low, high
 
 
@@ -84,4 +122,11 @@ def run_scenario(mod, sc, low, high, py_random, np_mod):
             out["aug_low"], out["aug_high"] = tc.selectRandomTiles(4, isTraining=True, augment=True)
         elif call == "aug_t":
             out["aug_t_low"], out["aug_t_high"] = tc.selectRandomTiles(4, isTraining=True, augment=True, tile_t=2)
+        elif call == "aug_t3":
+            out["aug_t3_low"], out["aug_t3_high"] = tc.selectRandomTiles(4, isTraining=True, augment=True, tile_t=3)
+        elif call == "aug_t2_3d":
+            out["aug_t2_3d_low"], out["aug_t2_3d_high"] = tc.selectRandomTiles(3, isTraining=True, augment=True, tile_t=2)
+        elif call == "tempo_aug":
+            a, b, c = tc.selectRandomTempoTiles(6, isTraining=True, augment=True, n_t=3, dt=0.5)
+            out["tempo_aug_low"], out["tempo_aug_high"], out["tempo_aug_pos"] = a, b, c
     return out

@@ -1,6 +1,9 @@
 """f2: the device tile pipeline (multi-pass-gan_amd/tiles_device.py + csrc/mpgan_tiles.hip) against the host TileCreator
 under identical seeds -- which itself reproduces the reference's batches bit for bit (tests/test_tilecreator.py).
-Plain batches must be bit-equal; augmented ones agree to float32 interpolation rounding."""
+Plain batches must be bit-equal; augmented ones agree to float32 interpolation rounding.  The augmented coherent
+frames (tile_t = dim_t = 3 with rotation, scaling and flip: the temporal batch of the training drivers, up to 18 packed
+channels) are the tc2d_t3_aug* / tc3d_t2_aug scenarios and, for quarter turns, ROT90_SCENARIOS below.  The kernels
+themselves are pinned bit for bit by test_tiles_kernels_gpu.py."""
 import contextlib
 import io
 import os
@@ -38,14 +41,29 @@ def _seed(i):
     np.random.seed(200 + i)
 
 
-@pytest.mark.parametrize("name", sorted(SCENARIOS))
-def test_device_tiles_match_host(name):
-    sc = SCENARIOS[name]
+def _streams_equal(state):
+    """the random streams were consumed identically"""
+    return random.getstate() == state[0] and all(np.array_equal(a, b) for a, b in zip(np.random.get_state(), state[1]) if isinstance(a, np.ndarray))
+
+
+def _report(name, call, pairs):
+    """largest deviation of an interpolated batch, and that deviation in units of the bound atol + rtol |host|"""
+    line = []
+    for what, got, want in pairs:
+        rtol, atol = (1e-5, 1e-5) if what == "pos" else (2e-5, 2e-6)
+        err = np.abs(got.astype(np.float64) - want)
+        line.append("%s max abs %.3e (%.2f of the bound)" % (what, float(err.max()), float((err / (atol + rtol * np.abs(want))).max())))
+    print("\ndevice tiles %s/%s: %s" % (name, call, ", ".join(line)))
+
+
+def _compare(name, sc, capsys):
     low, high = make_frames(sc)
     host, dev = _pair(sc, low, high)
     calls = {"batch": dict(n=5, tr=True, aug=False, t=1), "batch_test": dict(n=3, tr=False, aug=False, t=1),
              "batch_t": dict(n=4, tr=True, aug=False, t=2), "aug": dict(n=4, tr=True, aug=True, t=1),
-             "aug_t": dict(n=4, tr=True, aug=True, t=2)}
+             "aug_t": dict(n=4, tr=True, aug=True, t=2), "aug_t3": dict(n=4, tr=True, aug=True, t=3),
+             "aug_t2_3d": dict(n=3, tr=True, aug=True, t=2)}
+    interpolated = "aug" in sc and (sc["aug"]["rot"] == 2 or sc["aug"]["minScale"] != 1)
     for i, call in enumerate(sc["calls"]):
         if call in calls:
             c = calls[call]
@@ -54,11 +72,12 @@ def test_device_tiles_match_host(name):
             state = (random.getstate(), np.random.get_state())
             _seed(i)
             dl, dh = dev.selectRandomTilesDevice(c["n"], isTraining=c["tr"], augment=c["aug"], tile_t=c["t"])
-            # the random streams were consumed identically
-            assert random.getstate() == state[0] and all(np.array_equal(a, b) for a, b in zip(np.random.get_state(), state[1]) if isinstance(a, np.ndarray))
+            assert _streams_equal(state)
             dl, dh = dl.cpu().numpy(), dh.cpu().numpy()
             assert dl.shape == hl.shape and dh.shape == hh.shape, (call, dl.shape, hl.shape)
-            if c["aug"] and (sc["aug"]["rot"] == 2 or sc["aug"]["minScale"] != 1):
+            if c["aug"] and interpolated:
+                with capsys.disabled():
+                    _report(name, call, (("low", dl, hl), ("high", dh, hh)))
                 np.testing.assert_allclose(dl, hl, rtol=2e-5, atol=2e-6, err_msg=call)
                 np.testing.assert_allclose(dh, hh, rtol=2e-5, atol=2e-6, err_msg=call)
             else:
@@ -70,6 +89,50 @@ def test_device_tiles_match_host(name):
             da, db, dp = dev.selectRandomTempoTilesDevice(6, isTraining=True, augment=False, n_t=3, dt=0.5)
             assert np.array_equal(da.cpu().numpy(), a) and np.array_equal(db.cpu().numpy(), b)
             np.testing.assert_allclose(dp.cpu().numpy(), p, rtol=1e-5, atol=1e-5)
+        elif call == "tempo_aug":
+            # what getTempoinput / gettempo of the drivers draw: three packed coherent frames, augmented
+            _seed(i)
+            a, b, p = host.selectRandomTempoTiles(6, isTraining=True, augment=True, n_t=3, dt=0.5)
+            state = (random.getstate(), np.random.get_state())
+            _seed(i)
+            da, db, dp = dev.selectRandomTempoTilesDevice(6, isTraining=True, augment=True, n_t=3, dt=0.5)
+            assert _streams_equal(state)
+            da, db, dp = da.cpu().numpy(), db.cpu().numpy(), dp.cpu().numpy()
+            assert da.shape == a.shape and db.shape == b.shape and dp.shape == p.shape
+            if interpolated:
+                with capsys.disabled():
+                    _report(name, call, (("low", da, a), ("high", db, b), ("pos", dp, p)))
+                np.testing.assert_allclose(da, a, rtol=2e-5, atol=2e-6, err_msg=call)
+                np.testing.assert_allclose(db, b, rtol=2e-5, atol=2e-6, err_msg=call)
+            else:
+                assert np.array_equal(da, a.astype(np.float32)) and np.array_equal(db, b.astype(np.float32)), call
+            np.testing.assert_allclose(dp, p, rtol=1e-5, atol=1e-5)
+        else:
+            assert call == "tiles", call        # host-only calls of the fixture (getDatum, createTiles, concatTiles)
+
+
+@pytest.mark.parametrize("name", sorted(SCENARIOS))
+def test_device_tiles_match_host(name, capsys):
+    """tc3d_t2_aug is the one scenario whose vector mix is a full 3x3 (quaternion) rotation; the reference runs it, so
+    its batches are in the fixture too (tests/test_tilecreator.py holds the host class to them)"""
+    _compare(name, SCENARIOS[name], capsys)
+
+
+# rot=1 (quarter turns) cannot be generated by the reference on numpy >= 1.24 (test_tilecreator.py:
+# test_rot90_draws_by_index), so these rows are device against host only.  The second one is the reference's first example
+# training command (dataAugmentation 1 rot 1 add_adj_idcs 1 useVelocities 1): 18 packed channels.
+_ROT90 = dict(dim=2, tile=8, sim=16, upres=2, dim_t=3, frames=3, low="d,vx,vy,vz,d,d", high="d", dens_min=0.02, sparse=False,
+              signed=True, calls=("aug_t3", "tempo_aug"))
+ROT90_SCENARIOS = {
+    # no interpolation: bit-equal, which pins the sign and permutation bookkeeping of packed frames through _generate_tile_device
+    "rot90_flip": dict(_ROT90, aug=dict(rot=1, minScale=1, maxScale=1, flip=True)),
+    "rot90_scale_flip": dict(_ROT90, aug=dict(rot=1, minScale=0.85, maxScale=1.15, flip=True)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(ROT90_SCENARIOS))
+def test_device_tiles_match_host_rot90(name, capsys):
+    _compare(name, ROT90_SCENARIOS[name], capsys)
 
 
 def test_rot90_and_flip_orientation_bookkeeping():
