@@ -55,9 +55,22 @@ const char* mpg_version(void);
 /* ------------------------------------------------------------------------
  * "G8" activation tensors: what fused convolutions exchange.
  *     [N][CG = ceil(C/8)][2 planes: hi, lo][H][W][8 x fp16],   value = hi + lo
- * (two fp16 numbers per value, exact to 2^-22; channels beyond C are zero).
+ * (two fp16 numbers per value; channels beyond C are +0 in both planes).
  * Channel-group-major, so a tile row of one group is a contiguous run of
  * 16-byte pixels that LDS-DMA can stream.
+ *
+ * The value contract.  Every producer in this library (mpg_f32_to_g8*, the G8 outputs of the convolutions,
+ * mpg_pixel_norm_g8, mpg_bn_infer_act) stores the CANONICAL split of the fp32 value v it holds:
+ *     hi = fp16(v)                  correctly rounded: IEEE round to nearest even with gradual underflow,
+ *     lo = fp16(fp32(v) - fp32(hi)) of the hi that is stored (the fp32 difference is exact),
+ * so a consumer that reads the hi plane alone (MPG_PREC_F16X1) reads the correctly rounded fp16 of v, and two
+ * producers that hold the same v store the same bytes.  The contract covers finite v with |v| <= 65504 (for the
+ * scaled conversion: |v * scale| <= 65504); beyond it hi is +-inf (the value hi + lo is then NaN: lo is the opposite infinity, NaN for an infinite v), and a NaN v
+ * gives NaN in both planes.
+ * Accuracy: |v - (hi + lo)| <= 2^-22 |v| for 2^-3 <= |v| <= 65504.  Below 2^-3 lo reaches the fp16 subnormal
+ * range (spacing 2^-24) and the error is bounded absolutely instead: |v - (hi + lo)| <= 2^-25 (tests/test_g8_host.py holds both
+ * bounds against a numpy restatement and shows values just below 2^-3 that miss the relative one).  Tensors of small
+ * magnitude -- gradients -- therefore go through the scaled conversion (mpg_f32_to_g8_scaled).
  * ------------------------------------------------------------------------ */
 size_t mpg_g8_bytes(int n, int h, int w, int c);
 /* fp32 NHWC x[..., c_off : c_off+cin] -> G8 (flavour MPG_G8_*) with ceil(cin/8) groups */
@@ -194,8 +207,18 @@ typedef struct mpg_small_pair_desc {
 } mpg_small_pair_desc;
 int mpg_conv2d_small_pair(mpg_stream_t stream, const mpg_small_pair_desc* desc);
 
-/* out[0] = max |x_i| (device float).  mpg_f32_to_g8_scaled converts x * 2^k with 2^k = the power of two that brings
- * that maximum into [2^8, 2^9); a convolution over such an input takes the same pointer in desc.in_amax. */
+/* out[0] = max |x_i| over the elements that are not NaN (device float; whatever out held is overwritten): +0 for n = 0,
+ * for a tensor of NaNs and for a tensor of zeros of either sign, +inf when an element is +-inf.  NaN elements are
+ * skipped, never propagated: the scale of a tensor with a NaN in it is that of its other elements, and the NaN itself
+ * arrives in the G8 tensor as NaN.  x needs no alignment (16-byte loads are used when it has it).
+ * mpg_f32_to_g8_scaled converts x * 2^k (amax == NULL: k = 0, mpg_f32_to_g8).  With *amax = m 2^e, m in [0.5, 1):
+ *     k = min(9 - e, 126)      for 0 < *amax < 3.0e38,
+ *     k = 0                    for *amax <= 0, NaN, and *amax >= 3.0e38 (inf included).
+ * 2^(9 - e) brings the maximum into [2^8, 2^9); the cap bites for *amax < 2^-118 (fp32 subnormals included), where the
+ * scaled maximum is smaller than that but 2^k and its reciprocal stay normal fp32 numbers: a tensor of any magnitude
+ * converts without inf or NaN, and x 2^k is exact.  A convolution over such an input takes the same pointer in
+ * desc.in_amax and multiplies its sums by 2^-k; the weight gradient multiplies by 2^-(kx + kd) in two steps, so the
+ * result is right wherever it is a normal fp32 number. */
 int mpg_absmax(mpg_stream_t stream, const float* x, size_t n, float* out);
 int mpg_f32_to_g8_scaled(mpg_stream_t stream, const float* x, int n, int h, int w, int c, int c_off, int cin,
                          int flavour, const float* amax, void* out);
@@ -245,8 +268,9 @@ int mpg_avg_pool2(mpg_stream_t stream, const float* x, int n, int h, int w, int 
 int mpg_pixel_norm(mpg_stream_t stream, const float* x, size_t npix, int c, float eps, float* y);
 /* GAN.pixel_norm of a G8 tensor (MPG_G8_F16, c <= 512 channels) in place, behind the window launches of a wide layer
  * (ops.conv2d_fused_wide): x = hi + lo, y = x * rsqrt(mean_c(x^2) + eps) accumulated in fp32, written back as hi / lo
- * planes and, when y is not NULL, as fp32 NHWC [n,h,w,c] too.  The padding channels of the last group do not enter
- * the mean (the divisor is c) and stay zero. */
+ * planes and, when y is not NULL, as fp32 NHWC [n,h,w,c] too.  The planes are the canonical split of exactly the fp32
+ * values y receives, with or without y.  The padding channels of the last group are not read into the mean (the
+ * divisor is c; whatever they held) and are written as zero.  n <= 65535; g8 and y 16-byte aligned. */
 int mpg_pixel_norm_g8(mpg_stream_t stream, void* g8, int n, int h, int w, int c, float eps, float* y);
 /* GAN.minibatch_stddev_layer (GAN.py:476-488): y[n,h,w,c+1] = concat(x, s[n % M]) with s[m] the mean over
  * (h,w,c) of the standard deviation over the G = min(group_size, n) members {g*M + m} of group m, M = n / G.

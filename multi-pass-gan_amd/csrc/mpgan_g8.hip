@@ -155,11 +155,16 @@ __global__ __launch_bounds__(PN_PX * S) void pixel_norm_g8_kernel(_Float16* __re
         if (cg < cg_n) {
             // lo is the rest behind the hi that is STORED: the compiler is kept from forming hi a second time for the
             // subtraction (it folds the scaling into the conversion, v_fma_mixlo_f16, whose rounding of the product
-            // need not be that of v_cvt_pk_f16_f32 on the rounded product: a pair off by an fp16 ulp now and then)
+            // need not be that of v_cvt_pk_f16_f32 on the rounded product: a pair off by an fp16 ulp now and then).
+            // The product itself is pinned too: hi, lo and y32 are all taken from the ROUNDED fp32 product.  Left alone
+            // the compiler contracts the subtraction below with the multiply, lo = fp16(fma(x, sc, -hi)) of the
+            // unrounded product, and one lo in eleven was an ulp off the canonical split of the y32 beside it
+            // (tests/test_g8_gpu.py: test_pixel_norm_g8_planes).
             half8 hi, lo;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 v[k][j] *= sc;
+                asm volatile("" : "+v"(v[k][j]));
                 hi[j] = (_Float16)v[k][j];
             }
             asm volatile("" : "+v"(hi));

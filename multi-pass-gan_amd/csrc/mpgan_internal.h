@@ -46,14 +46,18 @@ __device__ __forceinline__ float apply_act(float v, int act, float leak) {
     return v;
 }
 
-// power-of-two scale that brings a tensor with absolute maximum `amax` into [2^8, 2^9): fp16 hi/lo splits of
-// gradients (1e-4 .. 1e-8 in magnitude) would otherwise land in the fp16 subnormal range
-__device__ __forceinline__ float pow2_scale(float amax) {
-    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
+// power-of-two scale 2^k that brings a tensor with absolute maximum `amax` into [2^8, 2^9): fp16 hi/lo splits of
+// gradients (1e-4 .. 1e-8 in magnitude) would otherwise land in the fp16 subnormal range.  amax = m 2^e with m in
+// [0.5, 1) gives k = min(9 - e, 126): the cap (it bites below 2^-118, where the scaled maximum stays under 2^8) keeps
+// 2^k and its reciprocal normal fp32 numbers -- 2^(9 - e) is inf from amax < 2^-119 on, which turned zeros into NaN
+// (0 * inf) and every unscaled sum into 0 (1 / inf).  k is 0 (scale 1) for amax <= 0, NaN and amax >= 3.0e38 (inf).
+__device__ __forceinline__ int pow2_scale_exp(float amax) {
+    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 0;
     int e;
     frexpf(amax, &e);
-    return ldexpf(1.f, 9 - e);
+    return 9 - e < 126 ? 9 - e : 126;
 }
+__device__ __forceinline__ float pow2_scale(float amax) { return ldexpf(1.f, pow2_scale_exp(amax)); }
 
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): hipFuncSetAttribute is a driver call and the
 // value never has to shrink, so a launch only pays for it the first time a size above the recorded one is asked.

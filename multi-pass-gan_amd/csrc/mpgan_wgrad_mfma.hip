@@ -39,7 +39,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BLK = 256;
 
-using mpg::pow2_scale;
 
 __global__ void absmax_kernel(const float* __restrict__ x, size_t n, unsigned int* __restrict__ out) {
     __shared__ float red[BLK];
@@ -156,14 +155,23 @@ __device__ __forceinline__ half8 shifted(const u32x2 (&w)[6]) {
     }
     return __builtin_bit_cast(half8, f);
 }
-// wscale over the scales the two G8 tensors carry
-__device__ __forceinline__ float wg_unscale(const WgTensors& t) {
-    return t.wscale / ((t.x_amax ? pow2_scale(*t.x_amax) : 1.f) * (t.d_amax ? pow2_scale(*t.d_amax) : 1.f));
+// wscale over the scales 2^kx, 2^kd the two G8 tensors carry, as two factors a = wscale 2^(t/2), b = 2^(t - t/2) with
+// t = -(kx + kd), applied one after the other: the product 2^(kx + kd) is inf in fp32 from kx + kd = 128 on (x around
+// 2^-55 with dy around 2^-60) and its reciprocal 0, which made a representable gradient exactly 0.  |t| <= 252, so both
+// powers of two are normal numbers, and val * a lies between val and the result in magnitude: where both of those are
+// normal no rounding happens that val * (a b) would not have had (powers of two scale exactly).
+struct WgUnscale {
+    float a, b;
+};
+__device__ __forceinline__ WgUnscale wg_unscale(const WgTensors& t) {
+    const int e = -((t.x_amax ? mpg::pow2_scale_exp(*t.x_amax) : 0) + (t.d_amax ? mpg::pow2_scale_exp(*t.d_amax) : 0));
+    const int ea = e / 2;
+    return {t.wscale * ldexpf(1.f, ea), ldexpf(1.f, e - ea)};
 }
 // Epilogue of one accumulator tile: filter tap `tap`, ci tile `cit` of the window [ci0, ci0 + cin), cout tile `cot` of
 // the window [co0, co0 + cout).  D row (v&3) + 8*(v>>2) + 4*(lane>>5) is the input channel, column lane&31 the output
 // channel; zeros (channels a tile has beyond the tensor, empty ranges) are not sent to memory.
-__device__ __forceinline__ void add_tile(const WgTensors& t, const f32x16& acc, float unscale, int tap, int ci0, int cin, int cit,
+__device__ __forceinline__ void add_tile(const WgTensors& t, const f32x16& acc, const WgUnscale unscale, int tap, int ci0, int cin, int cit,
                                          int co0, int cout, int cot, int lane) {
     const int co = cot * 32 + (lane & 31);
     if (co >= cout) return;
@@ -172,7 +180,7 @@ __device__ __forceinline__ void add_tile(const WgTensors& t, const f32x16& acc, 
         const int ci = cit * 32 + (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5);
         const float val = acc[v];
         if (ci < cin && val != 0.f)
-            atomicAdd(t.dw + ((size_t)tap * t.cin_total + ci0 + ci) * t.cout_total + co0 + co, val * unscale);
+            atomicAdd(t.dw + ((size_t)tap * t.cin_total + ci0 + ci) * t.cout_total + co0 + co, val * unscale.a * unscale.b);
     }
 }
 
@@ -403,7 +411,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_mfma_kernel(WgArgs a) {
         __syncthreads();
     }
 
-    const float unscale = wg_unscale(a.t);
+    const WgUnscale unscale = wg_unscale(a.t);
 #pragma unroll
     for (int kx = 0; kx < KW; ++kx)
 #pragma unroll
@@ -652,7 +660,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_ring_kernel(WrArgs a) {
         base = base + 1 >= RX ? 0 : base + 1;
     }
 
-    const float unscale = wg_unscale(a.t);
+    const WgUnscale unscale = wg_unscale(a.t);
     const int p0 = wave * NP / WG_WAVES, p1 = (wave + 1) * NP / WG_WAVES;
 #pragma unroll
     for (int s = 0; s < MAXP; ++s) {
