@@ -495,6 +495,39 @@ int mpg_act_bwd(mpg_stream_t stream, const float* dy, const float* y, size_t n, 
 /* gradient of GAN.pixel_norm (GAN.py:472-474) */
 int mpg_pixel_norm_bwd(mpg_stream_t stream, const float* dy, const float* x, size_t npix, int c, float eps,
                        float* dx);
+/* Second-order companions of mpg_act_bwd, mpg_pixel_norm_bwd and mpg_max_pool_bwd: what a gradient penalty (a gradient
+ * of a gradient) through tanh, GAN.pixel_norm and GAN.max_pool needs.  Each takes a cotangent g of the first backward's
+ * output.  The derivative with respect to the first backward's dy is that backward itself applied to g (all three are
+ * linear in dy) and has no entry of its own; these are the remaining terms.  64-bit offsets, no atomics, every element of
+ * the output is written, the same input gives the same bits.  Null pointers and bad shapes are refused (MPG_ERR_ARG)
+ * before anything is launched.
+ *
+ * mpg_act_bwd2: mpg_act_bwd's dx = dy * (1 - y^2) (MPG_ACT_TANH) differentiated in y, n elements:
+ *     d_y = ((-2 * y) * dy) * g          two rounded float32 products (-2 * y is exact), in that order.
+ *   16-byte accesses when dy, y, g and d_y are all 16-byte aligned, scalar ones otherwise; n == 0 launches nothing.  Every
+ *   other act is MPG_ERR_ARG: relu and lrelu are piecewise linear, their derivative in y is zero and the caller passes
+ *   nothing on; `leak` is ignored.
+ *
+ * mpg_pixel_norm_bwd2: mpg_pixel_norm_bwd's dx = r dy - r^3 s x differentiated in x ([npix, c] each, npix, c >= 1):
+ *     r = rsqrt(mean_c(x^2) + eps), s = mean_c(x dy), t = mean_c(x g), u = mean_c(dy g)
+ *     d_x = -r^3 (u x + s g + t dy) + 3 r^5 s t x
+ *   in float32 in this order: lanes = the largest power of two <= min(c, 64) lanes share a pixel; each of the four sums is
+ *   an fmaf chain from 0 over the lane's channels l, l + lanes, ..., folded by a xor tree from lanes / 2 down to 1 and
+ *   divided by (float)c; m = Sxx / c + eps, r = rsqrtf(m), r2 = r r, r3 = r2 r, k = (((3 r3) r2) s) t,
+ *   p_i = fmaf(t, dy_i, fmaf(s, g_i, u x_i)), d_x_i = fmaf(k, x_i, -(r3 p_i)).  A pixel of zeros gives zeros.  No alignment
+ *   is asked of any pointer.  More than (2^31 - 1) * 256 / lanes pixels are refused.
+ *
+ * mpg_max_pool_gather: the adjoint of mpg_max_pool_bwd, with its geometry (g [n,h,w,c]; arg and out [n,oh,ow,c],
+ *   oh = (h - k) / s + 1, ow = (w - k) / s + 1; n, c >= 1, 1 <= k <= 15, s >= 1, h, w >= k, else MPG_ERR_ARG):
+ *     out[b,oy,ox,ch] = g[b, s oy + a / k, s ox + a % k, ch],  a = arg[b,oy,ox,ch]
+ *   a copy, bit for bit.  arg is the plane mpg_max_pool writes (a < k k); a byte outside the window reads nothing and
+ *   gives 0. */
+int mpg_act_bwd2(mpg_stream_t stream, const float* dy, const float* y, const float* g, size_t n, int act, float leak,
+                 float* d_y);
+int mpg_pixel_norm_bwd2(mpg_stream_t stream, const float* dy, const float* x, const float* g, size_t npix, int c, float eps,
+                        float* d_x);
+int mpg_max_pool_gather(mpg_stream_t stream, const float* g, const unsigned char* arg, int n, int h, int w, int c, int k,
+                        int s, float* out);
 /* gradient of the nearest upsample by integer factors (GAN.py:517; dy is [n,oh,ow,c]) */
 int mpg_resize_nearest_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx,
                            int h, int w);

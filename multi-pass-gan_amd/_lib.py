@@ -159,6 +159,9 @@ PROTOTYPES = {
     "mpg_bn_train_bwd2_ordered": (_I, [_P, _P, _P, _Z, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _Z]),
     "mpg_act_bwd": (_I, [_P, _P, _P, _Z, _I, _F, _P, _P]),
     "mpg_pixel_norm_bwd": (_I, [_P, _P, _P, _Z, _I, _F, _P]),
+    "mpg_act_bwd2": (_I, [_P, _P, _P, _P, _Z, _I, _F, _P]),
+    "mpg_pixel_norm_bwd2": (_I, [_P, _P, _P, _P, _Z, _I, _F, _P]),
+    "mpg_max_pool_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mpg_resize_nearest_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I]),
     "mpg_resize_bilinear_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "mpg_resize_bicubic_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),

@@ -3,13 +3,17 @@
 // sums, the backward of the backward pass of the minibatch-stddev layer (WGAN-GP), and what held-out evaluation adds: the
 // six means of a critic's logits and the 8-bit grey mosaics of test tiles.  Entries: mpg_act_bwd, mpg_pixel_norm_bwd,
 // mpg_resize_nearest_bwd, mpg_resize_bilinear_bwd, mpg_resize_bicubic_bwd, mpg_avg_pool2_bwd, mpg_lerp, mpg_pair_reduce,
-// mpg_minibatch_stddev_bwd2, mpg_logit_stats, mpg_tiles_to_gray8.
+// mpg_minibatch_stddev_bwd2, mpg_logit_stats, mpg_tiles_to_gray8; and the second-order companions of tanh, pixel norm and
+// max pool (a gradient penalty through them): mpg_act_bwd2, mpg_pixel_norm_bwd2, mpg_max_pool_gather.
 #include "mpgan_resize.h"
 #include "mpgan_valu.h"
 
 using namespace mpg::valu;
 
 namespace {
+
+// act_bwd2_tanh_kernel runs grid-stride: at most this many blocks, each thread then takes several float4
+constexpr size_t ACT_BWD2_GRID = 1u << 16;
 
 // ---------------------------------------------------------------- elementwise backward
 // derivative expressed through the activation OUTPUT y (relu: y>0; lrelu: slope 1 / leak by sign of y,
@@ -37,6 +41,23 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __rest
     if (amax != nullptr) block_absmax_to(m, amax);
 }
 
+// The derivative of act_bwd_kernel's dx = dy * (1 - y^2) (tanh) in y for a cotangent g of dx: d_y = ((-2 y) dy) g.  -2 y is
+// exact, so an element is two rounded products and there is no sum for the compiler to contract.
+__global__ void act_bwd2_tanh_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ g,
+                                     size_t n, float* __restrict__ d_y) {
+    auto one = [](float d, float o, float u) { return ((-2.f * o) * d) * u; };
+    const bool vec = ((((uintptr_t)dy) | ((uintptr_t)y) | ((uintptr_t)g) | ((uintptr_t)d_y)) & 15) == 0;
+    const size_t n4 = vec ? n / 4 : 0;
+    for (size_t i = (size_t)blockIdx.x * BLK + threadIdx.x; i < n4; i += (size_t)gridDim.x * BLK) {
+        const float4 d = reinterpret_cast<const float4*>(dy)[i], o = reinterpret_cast<const float4*>(y)[i],
+                     u = reinterpret_cast<const float4*>(g)[i];
+        reinterpret_cast<float4*>(d_y)[i] = make_float4(one(d.x, o.x, u.x), one(d.y, o.y, u.y), one(d.z, o.z, u.z),
+                                                        one(d.w, o.w, u.w));
+    }
+    for (size_t idx = n4 * 4 + (size_t)blockIdx.x * BLK + threadIdx.x; idx < n; idx += (size_t)gridDim.x * BLK)
+        d_y[idx] = one(dy[idx], y[idx], g[idx]);
+}
+
 // y = x * r, r = rsqrt(mean_c x^2 + eps);  dx = r * (dy - y * mean_c(dy * y)); `lanes` consecutive lanes per pixel
 __global__ void pixel_norm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, size_t npix, int c,
                                       int lanes, float eps, float* __restrict__ dx) {
@@ -54,6 +75,83 @@ __global__ void pixel_norm_bwd_kernel(const float* __restrict__ dy, const float*
     const float r = rsqrtf(ss / c + eps);
     const float k = dot * r * r / c;
     for (int i = l; i < c; i += lanes) dx[pix * c + i] = r * (dp[i] - xp[i] * k);
+}
+
+// The derivative of pixel_norm_bwd_kernel's dx = r dy - r^3 s x (s = mean_c(x dy)) in x, for a cotangent g of dx:
+//   phi = g . dx = C (r u - r^3 s t),  t = mean_c(x g),  u = mean_c(dy g);  dr/dx_j = -r^3 x_j / C,  ds/dx_j = dy_j / C,
+//   dt/dx_j = g_j / C   =>   d_x = -r^3 (u x + s g + t dy) + 3 r^5 s t x.
+// The work split of pixel_norm_bwd_kernel: `lanes` consecutive lanes per pixel.  Every sum is an fmaf chain over the lane's
+// channels l, l + lanes, ... from 0.f, then the xor tree from lanes / 2 down to 1, then one division by (float)c; every
+// addition of the output is an explicit fmaf too, so nothing is left for the compiler to contract and the bits are those of
+//   m = Sxx / c + eps, r = rsqrtf(m), s = Sxd / c, t = Sxg / c, u = Sdg / c, r2 = r r, r3 = r2 r, k = (((3 r3) r2) s) t,
+//   p_i = fmaf(t, dy_i, fmaf(s, g_i, u x_i)),  d_x_i = fmaf(k, x_i, -(r3 p_i)).
+// x, dy and g come from HBM once, for the sums; the second read, for the output, hits the cache.
+// Error bound (tests/second_order_ref.py: pixel_norm_bwd2_bound), e = 2^-24, first order in e.  A sum has
+// E = ceil(c / lanes) + log2(lanes) + 1 roundings (chain, tree, division): |s^ - s| <= E e S with S = mean_c |x dy|, the
+// same for t (T = mean_c |x g|) and u (U = mean_c |dy g|); m has positive terms only and one more rounding, rsqrtf is within
+// 1 ulp = 2 e, so r is off by rho = ((E + 1) / 2 + 2) e relative, r2 by 2 rho + e, r3 by 3 rho + 2 e.  With
+// P = U |x| + S |g| + T |dy| >= |p| and every partial sum of p: |p^ - p| <= (E + 3) e P (E e per mean, one rounding each for
+// the product and the two fmaf), and r3 p adds 3 rho + 3 e: (2.5 E + 13.5) e r^3 P.  k has four rounded products, r3 r2 is off
+// by 5 rho + 3 e, s and t by E e of S and T: (4.5 E + 19.5) e K with K = 3 r^5 S T >= |k|.  The last fmaf rounds once at a
+// magnitude of at most K |x| + r^3 P.  Together |error| <= (4.5 E + 20.5) e (r^3 P + K |x|); the test holds the kernel to
+// (2.25 E + 10.5) 2^-23 (r^3 (U |x| + S |g| + T |dy|) + 3 r^5 S T |x|), the quarter added for the second-order terms.
+__global__ void pixel_norm_bwd2_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ g,
+                                       size_t npix, int c, int lanes, float eps, float* __restrict__ d_x) {
+    const size_t gid = (size_t)blockIdx.x * BLK + threadIdx.x;
+    const size_t pix = gid / lanes;
+    const int l = (int)(gid % lanes);
+    const bool ok = pix < npix;
+    const size_t base = (ok ? pix : 0) * (size_t)c;
+    const float* xp = x + base;
+    const float* dp = dy + base;
+    const float* gp = g + base;
+    float sxx = 0.f, sxd = 0.f, sxg = 0.f, sdg = 0.f;
+    if (ok)
+        for (int i = l; i < c; i += lanes) {
+            const float xv = xp[i], dv = dp[i], gv = gp[i];
+            sxx = fmaf(xv, xv, sxx);
+            sxd = fmaf(xv, dv, sxd);
+            sxg = fmaf(xv, gv, sxg);
+            sdg = fmaf(dv, gv, sdg);
+        }
+    // all 64 lanes of the wave take part, those past the last pixel with zeros: a lane group never crosses a wave
+    for (int m = lanes >> 1; m > 0; m >>= 1) {
+        sxx += __shfl_xor(sxx, m);
+        sxd += __shfl_xor(sxd, m);
+        sxg += __shfl_xor(sxg, m);
+        sdg += __shfl_xor(sdg, m);
+    }
+    if (!ok) return;
+    const float fc = (float)c;
+    const float r = rsqrtf(sxx / fc + eps);
+    const float s = sxd / fc, t = sxg / fc, u = sdg / fc;
+    const float r2 = r * r;
+    const float r3 = r2 * r;
+    const float k = (((3.f * r3) * r2) * s) * t;
+    for (int i = l; i < c; i += lanes) {
+        const float xv = xp[i];
+        const float p = fmaf(t, dp[i], fmaf(s, gp[i], u * xv));
+        d_x[base + i] = fmaf(k, xv, -(r3 * p));
+    }
+}
+
+// The adjoint of max_pool_bwd_kernel (mpgan_elem.hip), which sends dy[b,oy,ox,ch] to position arg of its window: every
+// output element reads the g at its arg position, out = g[b, s oy + a / k, s ox + a % k, ch].  A copy: no arithmetic on the
+// value, no atomics, one thread per output element.  An arg byte outside the window (mpg_max_pool writes none) has no
+// element to read and gives 0.
+__global__ void max_pool_gather_kernel(const float* __restrict__ g, const unsigned char* __restrict__ arg, int n, int h, int w,
+                                       int c, int k, int s, float* __restrict__ out) {
+    const int oh = (h - k) / s + 1, ow = (w - k) / s + 1;
+    const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+    const size_t total = (size_t)n * oh * ow * c;
+    if (idx >= total) return;
+    const int ch = idx % c;
+    size_t p = idx / c;
+    const int ox = p % ow; p /= ow;
+    const int oy = p % oh;
+    const int b = p / oh;
+    const int at = arg[idx];
+    out[idx] = at < k * k ? g[(((size_t)b * h + (size_t)s * oy + at / k) * w + (size_t)s * ox + at % k) * c + ch] : 0.f;
 }
 
 // nearest upsample by integer factors: dx[iy,ix] = sum of the fy x fx block of dy
@@ -332,6 +430,41 @@ extern "C" int mpg_pixel_norm_bwd(mpg_stream_t stream, const float* dy, const fl
     hipLaunchKernelGGL(pixel_norm_bwd_kernel, dim3(grid_for(npix * lanes)), dim3(BLK), 0, (hipStream_t)stream, dy, x, npix,
                        c, lanes, eps, dx);
     MPG_LAUNCH_CHECK("pixel_norm_bwd_kernel");
+}
+
+extern "C" int mpg_act_bwd2(mpg_stream_t stream, const float* dy, const float* y, const float* g, size_t n, int act,
+                            float leak, float* d_y) {
+    (void)leak;
+    MPG_REQUIRE(dy && y && g && d_y, "mpg_act_bwd2: null pointer");
+    MPG_REQUIRE(act == MPG_ACT_TANH, "mpg_act_bwd2: activation %d has no second derivative in y (tanh only)", act);
+    if (n == 0) return MPG_OK;
+    size_t blocks = ((n + 3) / 4 + BLK - 1) / BLK;
+    if (blocks > ACT_BWD2_GRID) blocks = ACT_BWD2_GRID;
+    hipLaunchKernelGGL(act_bwd2_tanh_kernel, dim3((unsigned)blocks), dim3(BLK), 0, (hipStream_t)stream, dy, y, g, n, d_y);
+    MPG_LAUNCH_CHECK("act_bwd2_tanh_kernel");
+}
+
+extern "C" int mpg_pixel_norm_bwd2(mpg_stream_t stream, const float* dy, const float* x, const float* g, size_t npix, int c,
+                                   float eps, float* d_x) {
+    MPG_REQUIRE(dy && x && g && d_x, "mpg_pixel_norm_bwd2: null pointer");
+    MPG_REQUIRE(npix >= 1 && c >= 1, "mpg_pixel_norm_bwd2: bad shape");
+    int lanes = 1;
+    while (lanes * 2 <= c && lanes < 64) lanes <<= 1;
+    MPG_REQUIRE(npix <= ((size_t)0x7fffffff * BLK) / lanes, "mpg_pixel_norm_bwd2: %zu pixels are more than one grid takes", npix);
+    hipLaunchKernelGGL(pixel_norm_bwd2_kernel, dim3(grid_for(npix * lanes)), dim3(BLK), 0, (hipStream_t)stream, dy, x, g, npix,
+                       c, lanes, eps, d_x);
+    MPG_LAUNCH_CHECK("pixel_norm_bwd2_kernel");
+}
+
+extern "C" int mpg_max_pool_gather(mpg_stream_t stream, const float* g, const unsigned char* arg, int n, int h, int w, int c,
+                                   int k, int s, float* out) {
+    MPG_REQUIRE(g && arg && out, "mpg_max_pool_gather: null pointer");
+    MPG_REQUIRE(n >= 1 && c >= 1 && k >= 1 && k <= 15 && s >= 1 && h >= k && w >= k, "mpg_max_pool_gather: bad shape");
+    const size_t total = (size_t)n * ((h - k) / s + 1) * ((w - k) / s + 1) * c;
+    MPG_REQUIRE(total <= (size_t)0x7fffffff * BLK, "mpg_max_pool_gather: %zu outputs are more than one grid takes", total);
+    hipLaunchKernelGGL(max_pool_gather_kernel, dim3(grid_for(total)), dim3(BLK), 0, (hipStream_t)stream, g, arg, n, h, w, c, k,
+                       s, out);
+    MPG_LAUNCH_CHECK("max_pool_gather_kernel");
 }
 
 extern "C" int mpg_resize_nearest_bwd(mpg_stream_t stream, const float* dy, int n, int oh, int ow, int c, float* dx,

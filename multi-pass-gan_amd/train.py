@@ -334,20 +334,38 @@ class ActFn(torch.autograd.Function):
 
 class ActBwdFn(torch.autograd.Function):
     """dx = dy * act'(.) with the mask taken from the activation output: linear in dy.  relu / lrelu are piecewise linear
-    (the second derivative is zero almost everywhere); tanh is not, and has no lowering for the derivative in y"""
+    (the second derivative is zero almost everywhere: nothing goes to y); tanh is not: dx = dy (1 - y^2) sends
+    -2 y dy g to y (TanhBwd2Fn), for which dy is kept too"""
 
     @staticmethod
     def forward(ctx, dy, y, act, leak):
-        ctx.save_for_backward(y)
+        if act == "tanh":
+            ctx.save_for_backward(y, dy)
+        else:
+            ctx.save_for_backward(y)
         ctx.act, ctx.leak = act, leak
         return train_ops.act_bwd(dy.detach(), y.detach(), act, leak)
 
     @staticmethod
     def backward(ctx, g):
+        y = ctx.saved_tensors[0]
+        d_y = None
         if ctx.act == "tanh" and ctx.needs_input_grad[1]:
-            raise NotImplementedError("second-order gradient through tanh (d/dy of dy * (1 - y^2) has no kernel)")
-        (y,) = ctx.saved_tensors
-        return ActBwdFn.apply(g, y, ctx.act, ctx.leak), None, None, None
+            d_y = TanhBwd2Fn.apply(ctx.saved_tensors[1], y, g)
+        return ActBwdFn.apply(g, y, ctx.act, ctx.leak), d_y, None, None
+
+
+class TanhBwd2Fn(torch.autograd.Function):
+    """d_y = -2 y dy g (mpg_act_bwd2): the term of ActBwdFn's backward that goes to the tanh output.  A derivative of it
+    would be a third derivative of tanh, which has no kernel: it raises instead of reading as zero"""
+
+    @staticmethod
+    def forward(ctx, dy, y, g):
+        return train_ops.act_bwd2(dy.detach(), y.detach(), g.detach(), "tanh")
+
+    @staticmethod
+    def backward(ctx, gg):
+        raise NotImplementedError("third-order gradient through tanh")
 
 
 class AvgPoolFn(torch.autograd.Function):
@@ -548,8 +566,11 @@ def strided4_as_3x3(w):
     return wp.reshape(3, 2, 3, 2, c, co).permute(0, 2, 1, 3, 4, 5).reshape(3, 3, 4 * c, co)
 
 
-# First-order only: a second derivative through these raises (once_differentiable) instead of reading as zero.
 class MaxPoolFn(torch.autograd.Function):
+    """tf.nn.max_pool VALID.  The index plane fixes a selection, so the backward is linear in dy: MaxPoolBwdFn scatters with
+    it, MaxPoolGatherFn is that scatter's adjoint, and the two are each other's backward to any order (as TensorFlow's
+    MaxPoolGrad / MaxPoolGradGrad, the second derivative in x is zero)"""
+
     @staticmethod
     def forward(ctx, x, k, s):
         x = x.contiguous()
@@ -559,12 +580,74 @@ class MaxPoolFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, dy):
         (arg,) = ctx.saved_tensors
-        return train_ops.max_pool_bwd(dy, arg, *ctx.geom), None, None
+        return MaxPoolBwdFn.apply(dy, arg, ctx.geom), None, None
 
 
+class MaxPoolBwdFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dy, arg, geom):
+        ctx.save_for_backward(arg)
+        ctx.geom = geom
+        return train_ops.max_pool_bwd(dy.detach(), arg, *geom)
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        return MaxPoolGatherFn.apply(g, arg, ctx.geom), None, None
+
+
+class MaxPoolGatherFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, arg, geom):
+        ctx.save_for_backward(arg)
+        ctx.geom = geom
+        return train_ops.max_pool_gather(g.detach(), arg, geom[2], geom[3])
+
+    @staticmethod
+    def backward(ctx, d):
+        (arg,) = ctx.saved_tensors
+        return MaxPoolBwdFn.apply(d, arg, ctx.geom), None, None
+
+
+class PixelNorm2Fn(torch.autograd.Function):
+    """GAN.pixel_norm inside higher_order_scopes: the kernels of PixelNormFn, differentiable twice (the backward is
+    PixelNormBwdFn); as with BNTrain2Fn the first-order Function stays what the first-order step runs"""
+
+    @staticmethod
+    def forward(ctx, x, eps):
+        ctx.save_for_backward(x)            # the input itself: PixelNormBwdFn sends its second-order term back through it
+        ctx.eps = eps
+        return ops.pixel_norm(x.detach().contiguous(), eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return PixelNormBwdFn.apply(dy, x, ctx.eps), None
+
+
+class PixelNormBwdFn(torch.autograd.Function):
+    """dx = r dy - r^3 mean_c(x dy) x, a symmetric linear operator on dy: its derivative in dy is itself applied to g, the one
+    in x is mpg_pixel_norm_bwd2.  Both are kernel calls without a tape, so a third derivative raises (once_differentiable)
+    instead of reading as zero"""
+
+    @staticmethod
+    def forward(ctx, dy, x, eps):
+        ctx.save_for_backward(dy, x)
+        ctx.eps = eps
+        return train_ops.pixel_norm_bwd(dy.detach(), x.detach(), eps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        dy, x = ctx.saved_tensors
+        g_dy = train_ops.pixel_norm_bwd(g, x, ctx.eps) if ctx.needs_input_grad[0] else None
+        g_x = train_ops.pixel_norm_bwd2(dy, x, g, ctx.eps) if ctx.needs_input_grad[1] else None
+        return g_dy, g_x, None
+
+
+# First-order only: a second derivative through these raises (once_differentiable) instead of reading as zero.
 class PixelNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps):
@@ -634,7 +717,7 @@ class TrainSession(object):
     """Eager, differentiable evaluation of ``graph`` nodes; parameters are leaf tensors keyed by
     the TF variable path.  ``run(fetches, feeds)`` returns torch tensors that carry the tape."""
 
-    def __init__(self, variables, graph=None, prec=ops.PREC_F16X3, bn_decay=0.999, device="cuda:0"):
+    def __init__(self, variables, graph=None, prec=ops.PREC_F16X3, bn_decay=0.999, device="cuda:0", higher_order_scopes=()):
         self.graph = graph or G.get_default_graph()
         self.vars = variables
         if prec not in (ops.PREC_F16X3, ops.PREC_F16X1, ops.PREC_F16F6):
@@ -645,7 +728,7 @@ class TrainSession(object):
         self.bn_decay = bn_decay
         self.device = torch.device(device)
         # variable-name prefixes whose layers must support gradients of gradients (the WGAN-GP discriminators)
-        self.higher_order_scopes = ()
+        self.higher_order_scopes = tuple(higher_order_scopes)
         self.params = {}
         self._scalar_feeds = {}
         self._noise_gen = {}     # random_normal node id -> its generator
@@ -759,7 +842,8 @@ class TrainSession(object):
             x = ev(n.inputs[0])
             return x.reshape(x.shape[0], -1)[:, :n.attrs["count"]]
         if op == "pixel_norm":
-            return PixelNormFn.apply(ev(n.inputs[0]), n.attrs["eps"])
+            fn = PixelNorm2Fn if self._higher(n) else PixelNormFn
+            return fn.apply(ev(n.inputs[0]), n.attrs["eps"])
         if op == "avg_pool":
             return AvgPoolFn.apply(ev(n.inputs[0]))
         if op == "lerp":
@@ -779,8 +863,6 @@ class TrainSession(object):
             noise = seeded_normal(self._noise_gen, n, x, self._noise_seed(n)) * (s * math.sqrt(x.shape[-1]))
             return ActFn.apply(x, noise, None, 0.2)
         if op == "max_pool":
-            if self._higher(n):
-                raise NotImplementedError("second-order gradient through max_pool (no reference network uses it)")
             if self.eval_mode:                          # no argmax plane: nothing runs backward
                 return ops.max_pool(ev(n.inputs[0]).contiguous(), n.attrs["k"], n.attrs["s"])
             return MaxPoolFn.apply(ev(n.inputs[0]), n.attrs["k"], n.attrs["s"])
@@ -860,8 +942,6 @@ class TrainSession(object):
                         "moving": (self.params[bn.inputs[3].attrs["var"]], self.params[bn.inputs[4].attrs["var"]])}
                 y = BNTrain2Fn.apply(y, self.params[bn.inputs[1].attrs["var"]], self.params[bn.inputs[2].attrs["var"]], bcfg)
             if act is not None:
-                if act == "tanh":
-                    raise G.GraphError("tanh has no higher-order lowering")
                 y = ActFn.apply(y, None, act, leak)
             return y.reshape(y.shape[0], -1) if is_fc else y
         gamma = beta = None

@@ -202,6 +202,19 @@ def act_bwd(dy, y, act, leak=0.2, want_amax=False):
     return (dx, amax) if want_amax else dx
 
 
+def act_bwd2(dy, y, g, act, leak=0.2):
+    """the derivative of act_bwd's dx in y for a cotangent g of dx: tanh, d_y = ((-2 y) dy) g; any other activation is
+    refused by the entry (relu / lrelu: the derivative is zero, pass None on instead)"""
+    lib = _lib.load()
+    dy, y, g = _cont(dy, "dy"), _cont(y, "y"), _cont(g, "g")
+    if dy.shape != y.shape or g.shape != y.shape:
+        raise _lib.MpgError("act_bwd2: dy %s, y %s and g %s differ in shape" % (tuple(dy.shape), tuple(y.shape), tuple(g.shape)))
+    d_y = torch.empty_like(y)
+    _lib.check(lib.mpg_act_bwd2(_stream(), _ptr(dy), _ptr(y), _ptr(g), y.numel(), _lib.act_id(act), leak, _ptr(d_y)),
+               "mpg_act_bwd2")
+    return d_y
+
+
 def pixel_norm_bwd(dy, x, eps=1e-8):
     lib = _lib.load()
     dy, x = _cont(dy, "dy"), _cont(x, "x")
@@ -210,6 +223,20 @@ def pixel_norm_bwd(dy, x, eps=1e-8):
     _lib.check(lib.mpg_pixel_norm_bwd(_stream(), _ptr(dy), _ptr(x), x.numel() // c, c, float(eps), _ptr(dx)),
                "mpg_pixel_norm_bwd")
     return dx
+
+
+def pixel_norm_bwd2(dy, x, g, eps=1e-8):
+    """the derivative of pixel_norm_bwd(dy, x) in x for a cotangent g of its dx (mpg_pixel_norm_bwd2); the derivative in dy
+    is pixel_norm_bwd(g, x)"""
+    lib = _lib.load()
+    dy, x, g = _cont(dy, "dy"), _cont(x, "x"), _cont(g, "g")
+    if dy.shape != x.shape or g.shape != x.shape:
+        raise _lib.MpgError("pixel_norm_bwd2: dy %s, x %s and g %s differ in shape" % (tuple(dy.shape), tuple(x.shape), tuple(g.shape)))
+    c = x.shape[-1]
+    d_x = torch.empty_like(x)
+    _lib.check(lib.mpg_pixel_norm_bwd2(_stream(), _ptr(dy), _ptr(x), _ptr(g), x.numel() // c, c, float(eps), _ptr(d_x)),
+               "mpg_pixel_norm_bwd2")
+    return d_x
 
 
 def resize_nearest_bwd(dy, h, w):
@@ -250,6 +277,19 @@ def max_pool_bwd(dy, arg, h, w, k, s):
     dx = torch.empty((n, h, w, c), dtype=torch.float32, device=dy.device)
     _lib.check(lib.mpg_max_pool_bwd(_stream(), _ptr(dy), _ptr(arg), n, h, w, c, k, s, _ptr(dx)), "mpg_max_pool_bwd")
     return dx
+
+
+def max_pool_gather(g, arg, k, s):
+    """the adjoint of max_pool_bwd: g [n,h,w,c] -> [n,oh,ow,c], every output its window's element at the arg position"""
+    lib = _lib.load()
+    g, arg = _cont(g, "g"), _dev(arg.contiguous(), "arg", torch.uint8)
+    n, h, w, c = g.shape
+    if k < 1 or s < 1 or tuple(arg.shape) != (n, (h - k) // s + 1, (w - k) // s + 1, c):
+        raise _lib.MpgError("max_pool_gather: arg %s does not match g %s with window %d stride %d"
+                            % (tuple(arg.shape), tuple(g.shape), k, s))
+    out = torch.empty(arg.shape, dtype=torch.float32, device=g.device)
+    _lib.check(lib.mpg_max_pool_gather(_stream(), _ptr(g), _ptr(arg), n, h, w, c, k, s, _ptr(out)), "mpg_max_pool_gather")
+    return out
 
 
 def avg_pool2_bwd(dy, h, w):
@@ -392,7 +432,9 @@ class _MacCormackFn(torch.autograd.Function):
     """order 2 of GAN.advect on one channel.  TensorFlow differentiates the op graph of GAN.py:206-343 branch by branch:
     the min / max clamp and the flag test only select, so with keep = (correction survived)
         out = fwd + keep * strength/2 * (source - bwd),  fwd = SL(source, +v),  bwd = SL(fwd, -v)
-    and d source = g + SL^T(+v)[dy - SL^T(-v)[g]] with g = keep * strength/2 * dy."""
+    and d source = g + SL^T(+v)[dy - SL^T(-v)[g]] with g = keep * strength/2 * dy.
+    First-order only: the backward is kernel calls without a tape, and a second derivative through it raises
+    (once_differentiable) instead of reading as zero."""
 
     @staticmethod
     def forward(ctx, source, vel_c, flags, strength):
