@@ -16,6 +16,13 @@ and the pipeline in which nothing is zoomed along z and the second network upsam
   upsamplingMode 2, upsampleFirst 0 : the simSize slices along z       -> density_low_2x2x1_%04d.uni
   upsamplingMode 0, upsampledData 1 : planes (y, z_low) along x        -> density_low_1x1x1_%04d.uni
 
+The shape of the low-res volume comes from the files (``[Z, Y, X]``, any three sizes, for modes 2 with upsampleFirst 1,
+1 and 3): each invocation builds its generator for the plane of its pass (``multipass.pass_planes_4x``) and the written
+header carries ``dimX = X * upRes``, ``dimY = Y * upRes``, ``dimZ = Z * upRes``.  ``simSize`` is what the shape is
+expected to be -- one line names the shape taken when it differs -- and the cube size of training (``out 0``:
+"training takes simSize cubes").  A non-cubic volume with ``previews 1``, ``upsamplingMode 0`` or ``upsampleFirst 0``
+exits with ``ERROR:`` and status 1 before a model is loaded.
+
 One deviation: the reference stamps dimZ = simSizeHigh on every file it writes (:1151-1154), also on the ``2x2x1`` one,
 which holds only simSize slices, and its own reader cannot reshape such a file.  Here the header's dimZ is the number
 of slices in the file.
@@ -182,6 +189,11 @@ def train_main():
         tiCr.initDataAugmentation(rot=int(P["rot"]), minScale=float(P["minScale"]), maxScale=float(P["maxScale"]),
                                   flip=int(P["flip"]))
     x, y, _ = fl.get()
+    side_x = simSizeHigh if mode == 1 else simSizeLow
+    if tuple(x.shape[1:3]) != (side_x, side_x) or tuple(y.shape[1:3]) != (simSizeHigh, simSizeHigh):
+        print("ERROR: training takes simSize cubes: simSize %d, the files hold slices of %s (input) and %s (target)"
+              % (simSizeLow, tuple(x.shape[1:3]), tuple(y.shape[1:3])))
+        exit(1)
     if mode == 1:
         _, x_2, _ = fl2.get()
         x = x.reshape(-1, 1, simSizeHigh, simSizeHigh, n_ch * n_t)    # :292-297
@@ -340,7 +352,6 @@ uni_index, device_read = int(P["uniIndex"]), int(P["deviceRead"])
 if uni_index and not int(P["uniCodec"]):
     print("ERROR: uniIndex 1 needs the device codec (uniCodec 1 or 2)")
     exit(1)
-simSizeHigh = simSizeLow * upRes
 n_ch = 4 if useVelocities else 1
 device = "cuda:0"
 
@@ -350,6 +361,20 @@ floader = FDL.FluidDataLoader(print_info=1, base_path=packedSimPath, base_path_y
                               filename_y=None, filename_index_max=frame_max, indices=[fromSim], data_fraction=1.0,
                               multi_file_list=mfl, multi_file_list_y=["density"])
 x, _, _ = floader.get()
+# the volume's shape comes from the files ([frame, Z, Y, X, C]); simSize is only what it is expected to be
+vol_shape = tuple(int(v) for v in x.shape[1:4])
+if vol_shape != (simSizeLow,) * 3:
+    print("simSize %d: the files hold %d x %d x %d (z, y, x) volumes, which is the shape taken" % ((simSizeLow,) + vol_shape))
+if not multipass.is_cube(vol_shape):
+    for refused, why in ((int(P["previews"]), "previews 1 (the projections stack three sums of equal width)"),
+                         (upsampling_mode == 0, "upsamplingMode 0"), (not upsample_first, "upsampleFirst 0")):
+        if refused:
+            print("ERROR: %s takes cubic volumes, not %d x %d x %d" % ((why,) + vol_shape))
+            exit(1)
+    tile_low = multipass.pass_planes_4x(vol_shape)[{2: 0, 1: 1, 3: 2}[upsampling_mode]]
+else:
+    tile_low = vol_shape[0]
+simZ, simY, simX = vol_shape
 x_2 = None
 prev_name = {3: "density_low_1x1_%04d.uni", 0: "density_low_2x2x1_%04d.uni"}.get(upsampling_mode, "density_low_2x2_%04d.uni")
 if upsampled_data and not device_read:
@@ -369,12 +394,12 @@ except FileNotFoundError as e:
         print("ERROR: %s" % e)
         exit(1)
     params = None
-gen = multipass.Generator("gen_resnet", dict(tile_low=simSizeLow, up_res=upRes, channels=n_ch,
+gen = multipass.Generator("gen_resnet", dict(tile_low=tile_low, up_res=upRes, channels=n_ch,
                                              upsampling_mode=upsampling_mode, batch_norm=batch_norm,
                                              vorticity=useVorticities),
                           params, prec=ops.parse_prec(P["prec"]), device=device, seed=int(P["randSeed"]))
 print('*****OUTPUT ONLY*****')
-s = simSizeHigh
+s = simZ * upRes
 previews = int(P["previews"])                # extension: 1 = source_%04d.png per frame into test_path (4x.py:1134,1146)
 pictures = 0
 
@@ -395,13 +420,13 @@ for layerno in range(frame_min, frame_max):
     i = layerno - frame_min
     start = time.time()
     low = torch.as_tensor(np.ascontiguousarray(x[i])).to(device)
-    slices = simSizeHigh
+    slices = simZ * upRes
     sink = preview.PreviewSink(test_path, layerno, int(P["tileSize"]) * upRes) if previews else None
     if upsampling_mode == 2 and not upsample_first:
         # (the reference writes no picture in this branch, 4x.py:1135-1136)
         vol = multipass.plane_pass_4x(gen, low, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni))
         name = 'density_low_2x2x1_%04d.uni'
-        slices = simSizeLow
+        slices = simZ
     elif upsampling_mode == 0:
         v1 = previous_volume(i, layerno)
         vol = multipass.upsample_pass_4x(gen, low, v1, upRes, batch=8, vel_scale=velScale, apply_cutoff=bool(generateUni),
@@ -428,7 +453,7 @@ for layerno in range(frame_min, frame_max):
         pictures += len(sink.written)
     if generateUni:
         head, _ = uniio.readUni(packedSimPath + "sim_%04d/density_low_%04d.uni" % (fromSim, layerno))
-        head['dimX'] = head['dimY'] = simSizeHigh
+        head['dimX'], head['dimY'] = simX * upRes, simY * upRes
         head['dimZ'] = slices                                                # 2x2x1: the slices the file holds (see above)
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/' % fromSim + name % layerno, head, vol,
                                  codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"), unit_index=bool(uni_index))

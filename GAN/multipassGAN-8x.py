@@ -99,7 +99,12 @@ def output_main():
                                           upsamples z itself -> density_low_t%04d_1x1x1_%04d.uni
     (multipass.plane_pass_8x / upsample_pass_8x, whose docstrings name the two places where the reference cannot run as
     written).  upsampleFirst 0 slices along z (transposeAxis 0); upsamplingMode 0 needs useVelocities 1 (the channel swap
-    of :1637-1639 and the residual's channel 4) and has no vorticity channels, like the 4x driver."""
+    of :1637-1639 and the residual's channel 4) and has no vorticity channels, like the 4x driver.
+    The shape of the low-res volume comes from the files ([Z, Y, X], any three sizes, for modes 2 / 1 / 3 and every
+    transposeAxis): the generator is built for the plane of the pass (multipass.single_pass_plane_8x) and the written header
+    carries the shape times upRes.  simSize is what the shape is expected to be (one line names the shape taken when it
+    differs) and the cube size of training.  A non-cubic volume with previews 1, upsamplingMode 0 or upsampleFirst 0 exits
+    with ERROR: and status 1 before a model is loaded."""
     from mpgan_amd import multipass, ops, uniio
     mode, upsampled = int(P["upsamplingMode"]), int(P["upsampledData"])
     up_first = int(P["upsampleFirst"]) > 0
@@ -125,7 +130,6 @@ def output_main():
     if uni_index and not int(P["uniCodec"]):
         fail("uniIndex 1 needs the device codec (uniCodec 1 or 2)")
     up, sim = int(P["upRes"]), int(P["simSize"])
-    s = sim * up
     base, sims = P["basePath"], P["packedSimPath"]
     from_sim, f0, f1 = int(P["fromSim"]), int(P["frame_min"]), int(P["frame_max"])
     vel = int(P["useVelocities"]) > 0
@@ -139,6 +143,18 @@ def output_main():
                              multi_file_list_y=["density"])
     x_3d, _, _ = fl.get()
     x_3d[:, :, :, :, 1:4] = float(P["velScale"]) * x_3d[:, :, :, :, 1:4]                     # :361
+    # the volume's shape comes from the files ([frame, Z, Y, X, C]); simSize is only what it is expected to be
+    vol_shape = tuple(int(v) for v in x_3d.shape[1:4])
+    if vol_shape != (sim,) * 3:
+        print("simSize %d: the files hold %d x %d x %d (z, y, x) volumes, which is the shape taken" % ((sim,) + vol_shape))
+    if not multipass.is_cube(vol_shape):
+        for refused, why in ((int(P["previews"]), "previews 1 (the projections stack three sums of equal width)"),
+                             (mode == 0, "upsamplingMode 0"), (not up_first, "upsampleFirst 0")):
+            if refused:
+                fail("%s takes cubic volumes, not %d x %d x %d" % ((why,) + vol_shape))
+        tile_low = multipass.single_pass_plane_8x(vol_shape, ta)[0]
+    else:
+        tile_low = vol_shape[0]
     x_2 = None
     prev_name = {1: "density_low_t%04d_2x2", 0: "density_low_t%04d_2x2x1"}.get(mode, "density_low_t%04d_1x1") % int(
         P["outNNTestNo"]) + "_%04d.uni"                                                       # :231-238
@@ -147,7 +163,7 @@ def output_main():
                                   filename_index_min=f0, oldNamingScheme=False, filename_index_max=f1, indices=[from_sim],
                                   data_fraction=1.0, multi_file_list=["density"])
         x_2, _, _ = fl2.get()
-    cfg = dict(tile_low=sim, up_res=up, channels=n_ch, first_gen=first, upsampling_mode=mode, filter_size=int(P["filterSize"]),
+    cfg = dict(tile_low=tile_low, up_res=up, channels=n_ch, first_gen=first, upsampling_mode=mode, filter_size=int(P["filterSize"]),
                start_fms=int(P["startFms"]), max_fms=int(P["maxFms"]), add_adj=int(P["add_adj_idcs"]) > 0 and first,
                first_nn_arch=int(P["firstNNArch"]) > 0 and first, use_res_net=int(P["use_res_net"]) > 0,
                pixel_norm=int(P["pixelNorm"]) > 0, batch_norm=int(P["batchNorm"]) > 0, upsample_mode=int(P["upsampleMode"]),
@@ -194,9 +210,9 @@ def output_main():
         print("time for network: {0:.6f}".format(time.time() - t0))
         if gen_uni:
             head = dict(head_0)
-            head['dimX'] = head['dimY'] = head['dimZ'] = s
+            head['dimZ'], head['dimY'], head['dimX'] = (n * up for n in vol_shape)
             if not up_first:
-                head['dimZ'] = sim                                                           # :1763-1764
+                head['dimZ'] = vol_shape[0]                                                           # :1763-1764
             uniio.writeUniFromDevice(sims + '/sim_%04d/' % from_sim + out_name % layerno, head, vol,
                                      codec={0: "host", 2: "device_dynamic"}.get(int(P["uniCodec"]), "device"),
                                      unit_index=bool(uni_index))
@@ -310,6 +326,10 @@ def load_stage(currentUpres, first):
     if later_net:
         _, x_2, _ = fl2.get()
     simSizeHigh = simSizeLow * upRes
+    side_y = simSizeHigh if later_net else simSizeLow * currentUpres
+    if tuple(x.shape[1:3]) != (simSizeLow, simSizeLow) or tuple(y.shape[1:3]) != (side_y, side_y):
+        fail("training takes simSize cubes: simSize %d, the files hold slices of %s (input) and %s (target)"
+             % (simSizeLow, tuple(x.shape[1:3]), tuple(y.shape[1:3])))
     if not later_net:
         x = x.reshape(-1, 1, simSizeLow, simSizeLow, n_tileChannels * 3)
         y = y.reshape(-1, 1, simSizeLow * currentUpres, simSizeLow * currentUpres, 3)

@@ -17,6 +17,12 @@ axes of the passes exactly as :397-547 do, including what is broken there: the t
 transposeAxis 2 raises the reference's IndexError (:542); ``add_adj_idcs2/3`` are ignored (the
 reference's code for them writes past the array it allocates, :488-500).
 
+The shape of the low-res volume comes from the files (``[Z, Y, X]``, any three sizes, with ``transposeAxis 0``): the
+networks are built for the planes of their passes (``multipass.pass_planes_8x``: (Y, X), (Y, Z), (Z, X)) and the written
+header carries the shape times ``upRes``.  ``simSize`` is what the shape is expected to be; one line names the shape taken
+when it differs.  A non-cubic volume with ``previews 1`` or ``transposeAxis`` 1..3 (the reference's regroupings,
+:534-535, are defined for cubes) exits with ``ERROR:`` and status 1 before a model is loaded.
+
 ``useVorticities 1`` (the tempoGAN vorticity input; the switch is global, so every loaded network gets it): each network
 takes three more input channels behind all others (:148), and every pass computes them on its low-res slice batch exactly
 as the network receives it (mpg_vorticity_append through ``mpgan_amd/vorticity.py``; the later networks then resize them
@@ -94,7 +100,6 @@ if transposeAxis not in (0, 1, 2, 3):
     exit(1)
 os.environ.setdefault("HIP_VISIBLE_DEVICES", str(gpu))
 device = "cuda:0"
-simSizeHigh = simSizeLow * upRes
 n_ch = 4 if useVelocities else 1
 
 mfl = ["density"] + (["velocity"] if useVelocities else [])
@@ -104,6 +109,20 @@ floader = FDL.FluidDataLoader(print_info=3, base_path=packedSimPath, base_path_y
                               multi_file_list=mfl, multi_file_list_y=["density"])
 x_3d, _, _ = floader.get()
 x_3d[:, :, :, :, 1:4] = velScale * x_3d[:, :, :, :, 1:4]       # out.py:138
+# the volume's shape comes from the files ([frame, Z, Y, X, C]); simSize is only what it is expected to be
+vol_shape = tuple(int(v) for v in x_3d.shape[1:4])
+if vol_shape != (simSizeLow,) * 3:
+    print("simSize %d: the files hold %d x %d x %d (z, y, x) volumes, which is the shape taken" % ((simSizeLow,) + vol_shape))
+if not multipass.is_cube(vol_shape):
+    for refused, why in ((previews, "previews 1 (the projections stack three sums of equal width)"),
+                         (transposeAxis != 0, "transposeAxis %d (the reference's regroupings, out.py:534-535, are only "
+                                              "defined for cubes)" % transposeAxis)):
+        if refused:
+            print("ERROR: %s takes cubic volumes, not %d x %d x %d" % ((why,) + vol_shape))
+            exit(1)
+    tiles_low = multipass.pass_planes_8x(vol_shape)
+else:
+    tiles_low = (vol_shape[0],) * 3
 
 gens = []
 test_path = None
@@ -118,7 +137,7 @@ for k, n in enumerate(nets):
         os.makedirs(basePath + 'test_%04d/' % n["load_model_test"], exist_ok=True)
     if os.path.isdir(basePath + 'test_%04d/' % n["load_model_test"]):
         test_path, _ = ph.getNextGenericPath(prefix, 0, basePath + 'test_%04d/' % n["load_model_test"])
-    cfg = dict(tile_low=simSizeLow, up_res=upRes, channels=n_ch, first_gen=(k == 0), filter_size=n["filter_size"],
+    cfg = dict(tile_low=tiles_low[len(gens)], up_res=upRes, channels=n_ch, first_gen=(k == 0), filter_size=n["filter_size"],
                start_fms=n["start_fms"], max_fms=n["max_fms"], add_adj=n["add_adj"] and k == 0,
                first_nn_arch=bool(firstNNArch) and k == 0, use_res_net=n["use_res_net"], pixel_norm=pixel_norm,
                batch_norm=batch_norm, upsample_mode=upsampleMode, add_bicubic=bool(addBicubicUpsample),
@@ -156,7 +175,7 @@ for layerno in range(frame_min, frame_max):
         pictures += len(sink.written)
     if generateUni:
         head = dict(head_0)
-        head['dimX'] = head['dimY'] = head['dimZ'] = simSizeHigh
+        head['dimZ'], head['dimY'], head['dimX'] = (n * upRes for n in vol_shape)
         uniio.writeUniFromDevice(packedSimPath + '/sim_%04d/source_%04d.uni' % (fromSim, layerno), head, vol,
                                  codec={0: "host", 2: "device_dynamic"}.get(uniCodec, "device"))
         print('stored .uni file')

@@ -26,6 +26,15 @@ def log2_int(v):
     return int(round(math.log(v, 2)))
 
 
+def plane_hw(tile):
+    """(rows, cols) of a tile size given as one int (a square) or as a pair"""
+    if isinstance(tile, (tuple, list)):
+        if len(tile) != 2:
+            raise ValueError("tile size %r: an int or a pair (rows, cols)" % (tile,))
+        return int(tile[0]), int(tile[1])
+    return int(tile), int(tile)
+
+
 # =====================================================================================================
 # tables
 # =====================================================================================================
@@ -127,11 +136,14 @@ class _Emit(object):
 # ---------------------------------------------------------------------------------------------- 4x
 def gen_resnet(_in, tileSizeLow, upRes, n_inputChannels, upsampling_mode=2, reuse=False, use_batch_norm=False,
                train=False):
-    """-4x.py:528-569.  _in: flat placeholder [None, n_input]; returns [None, tileSizeHigh^2]."""
-    high = tileSizeLow * upRes
+    """-4x.py:528-569.  _in: flat placeholder [None, n_input]; returns [None, rows_high * cols_high].
+    tileSizeLow: an int (the reference's square tile) or a pair (rows, cols) of the low plane; the network's own plane
+    is the low one times upRes along every axis its first layer does not repeat."""
+    low_r, low_c = plane_hw(tileSizeLow)
+    high_r, high_c = low_r * upRes, low_c * upRes
     with tf.variable_scope("generator", reuse=reuse):
-        rows = {2: tileSizeLow, 1: high, 3: high, 0: high}[upsampling_mode]
-        cols = tileSizeLow if upsampling_mode in (2, 0) else high
+        rows = {2: low_r, 1: high_r, 3: high_r, 0: high_r}[upsampling_mode]
+        cols = low_c if upsampling_mode in (2, 0) else high_c
         x = tf.reshape(_in, shape=[-1, rows, cols, n_inputChannels])
         gan = GAN(x)
         if upsampling_mode == 2:
@@ -141,7 +153,7 @@ def gen_resnet(_in, tileSizeLow, upRes, n_inputChannels, upsampling_mode=2, reus
         em = _Emit(gan, 5, False, reuse, train)
         for unit, bn in gen_resnet_table(n_inputChannels):
             x = em.unit(x, unit, use_batch_norm and bn)
-        return tf.reshape(x, shape=[-1, high * high])
+        return tf.reshape(x, shape=[-1, high_r * high_c])
 
 
 def _disc4(x, p, reuse, use_batch_norm, train, bn_decay):
@@ -188,14 +200,24 @@ def disc_binclass_cond_tempo(in_high, tileSizeLow, upRes, n_t_channels=3, reuse=
 
 # ---------------------------------------------------------------------------------------------- 8x
 class Cfg8x(object):
-    """the module-level flags of multipassGAN-8x.py / -out.py that the model functions read"""
+    """the module-level flags of multipassGAN-8x.py / -out.py that the model functions read.
+    tileSizeLow: an int, or a pair (rows, cols) of the low plane for the inference generators (upsampling_mode 1..3);
+    low_hw / high_hw hold the planes either way.  The critics, the training form and upsampling_mode 0 take the int."""
 
     def __init__(self, tileSizeLow=16, upRes=8, n_inputChannels=4, upsampling_mode=2, upsampleMode=1, filterSize=3,
                  start_fms=256, max_fms=256, first_nn_arch=True, use_res_net=True, pixel_norm=True,
                  addBicubicUpsample=True, use_mb_stddev=False, useVelInTDisc=False, bn_decay=0.999, usePixelShuffle=False,
                  gDrop=False):
-        self.tileSizeLow, self.upRes = tileSizeLow, upRes
-        self.tileSizeHigh = tileSizeLow * upRes
+        self.upRes = upRes
+        self.low_hw = plane_hw(tileSizeLow)
+        self.high_hw = (self.low_hw[0] * upRes, self.low_hw[1] * upRes)
+        if isinstance(tileSizeLow, (tuple, list)):
+            if upsampling_mode == 0:
+                raise ValueError("upsampling_mode 0 takes one tileSizeLow (planes [tileSizeHigh, tileSizeLow]), not the "
+                                 "pair %r" % (tuple(tileSizeLow),))
+            self.tileSizeLow, self.tileSizeHigh = self.low_hw, self.high_hw
+        else:
+            self.tileSizeLow, self.tileSizeHigh = tileSizeLow, tileSizeLow * upRes
         self.n_inputChannels = n_inputChannels
         self.upsampling_mode, self.upsampleMode = upsampling_mode, upsampleMode
         self.filterSize, self.start_fms, self.max_fms = filterSize, start_fms, max_fms
@@ -214,8 +236,14 @@ class Cfg8x(object):
                                  "= %d < 5" % (n_inputChannels + 1))
             self.n_input = self.tileSizeHigh * tileSizeLow * (n_inputChannels + 1)
         else:
-            self.n_input = tileSizeLow ** 2 * n_inputChannels        # -8x.py:402-416 (modes 1, 2, 3)
-        self.n_output = self.tileSizeHigh ** 2
+            self.n_input = self.low_hw[0] * self.low_hw[1] * n_inputChannels        # -8x.py:402-416 (modes 1, 2, 3)
+        self.n_output = self.high_hw[0] * self.high_hw[1]
+
+    def square(self, what):
+        """the scalar tile sizes, for the graphs that are built on squares only"""
+        if self.low_hw[0] != self.low_hw[1]:
+            raise ValueError("%s takes square tiles, not %d x %d" % ((what,) + self.low_hw))
+        return self.low_hw[0], self.high_hw[0]
 
     @property
     def first_gen(self):
@@ -228,16 +256,18 @@ class Cfg8x(object):
 
 
 def second_gen_input(x, y, tileSizeLow, tileSizeHigh, n_inputChannels):
-    """x_in_2 of -out.py:357: concat(previous pass slice, nearest-resized low-res slice)."""
-    up = tf.resize_images(tf.reshape(x, shape=[-1, tileSizeLow, tileSizeLow, n_inputChannels]),
-                          [tileSizeHigh, tileSizeHigh], method=1)
-    return tf.concat((tf.reshape(y, shape=[-1, tileSizeHigh, tileSizeHigh, 1]), up), axis=3)
+    """x_in_2 of -out.py:357: concat(previous pass slice, nearest-resized low-res slice).
+    tileSizeLow / tileSizeHigh: ints or pairs (rows, cols)."""
+    (lr, lc), (hr, hc) = plane_hw(tileSizeLow), plane_hw(tileSizeHigh)
+    up = tf.resize_images(tf.reshape(x, shape=[-1, lr, lc, n_inputChannels]), [hr, hc], method=1)
+    return tf.concat((tf.reshape(y, shape=[-1, hr, hc, 1]), up), axis=3)
 
 
 def later_network_input(x, y2, cfg):
     """x_in of the second / third network in training (-8x.py:1041-1044): channel 1 of the two-channel `y`
     (the previous pass's output; channel 0 is the target) next to the nearest-resized low-res input"""
     c = cfg
+    c.square("later_network_input (training)")
     y4 = tf.reshape(y2, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, 2])
     up = tf.resize_images(tf.reshape(x, shape=[-1, c.tileSizeLow, c.tileSizeLow, c.n_inputChannels]),
                           [c.tileSizeHigh, c.tileSizeHigh], method=1)
@@ -276,11 +306,11 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
     stem, blocks = growing_gen_table(c.start_fms, c.max_fms, levels, c.first_nn_arch, c.use_res_net)
     with tf.variable_scope("generator", reuse=reuse):
         if c.first_gen:
-            x_in = tf.reshape(_in, shape=[-1, c.tileSizeLow, c.tileSizeLow, c.n_inputChannels])
+            x_in = tf.reshape(_in, shape=[-1, c.low_hw[0], c.low_hw[1], c.n_inputChannels])
         elif c.axis_gen:
             x_in = tf.reshape(_in, shape=[-1, c.tileSizeHigh, c.tileSizeLow, c.n_inputChannels + 1])
         else:
-            x_in = tf.reshape(_in, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, c.n_inputChannels + 1])
+            x_in = tf.reshape(_in, shape=[-1, c.high_hw[0], c.high_hw[1], c.n_inputChannels + 1])
         gan = GAN(x_in, bn_decay=c.bn_decay if not output else 0.0)
         em = _Emit(gan, c.filterSize, c.pixel_norm, reuse, train)
         # the stem's residual units never use batch norm (-out.py:308-309), its conv pair does (:311-314)
@@ -309,10 +339,10 @@ def growing_gen(_in, cfg, percentage=None, reuse=False, use_batch_norm=False, tr
                     base = tf.slice_channels(x_in, 0, 1)
                     dens = dens + (GAN(base).avg_depool(mode=2, scale=[up]) if c.first_gen else base)
             if not output:
-                size = c.tileSizeLow * up if c.first_gen else c.tileSizeHigh
+                rows, cols = (c.low_hw[0] * up, c.low_hw[1] * up) if c.first_gen else c.high_hw
                 if c.first_gen:
                     old = GAN(old).avg_depool(mode=1)
-                old = tf.reshape(tf.lerp(old, dens, percentage - (j - 1)), shape=[-1, size, size, 1])
+                old = tf.reshape(tf.lerp(old, dens, percentage - (j - 1)), shape=[-1, rows, cols, 1])
             elif last:
                 old = dens
         rows, cols = int(old.get_shape()[1]), int(old.get_shape()[2])
@@ -373,6 +403,7 @@ def growing_disc(in_high_, in_low_, percentage, cfg, reuse=False, use_batch_norm
                  gstr=None):
     """-8x.py:783-863.  Returns (score [N,1], feature_layers).  gstr: gDrop noise strength (``Scalar``; None = 0.0)"""
     c = cfg
+    c.square("growing_disc")
     with tf.variable_scope("spatial-disc", reuse=reuse):
         high = tf.reshape(in_high_, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, 1])
         # every mode slices channel 0 of a [tileSizeLow, tileSizeLow, C] view and resizes it by upRes (:797-809)
@@ -389,6 +420,7 @@ def growing_disc_tempo(in_high_, percentage, cfg, n_t_channels=3, reuse=True, us
     mpg_tempo_vel_pack writes (frames and scaled velocity in the reference's order, :1204-1208), read as [N, H, W, 12]
     (:878), and the growing blocks use [filterSize + 2, filterSize] filters (:754-755).  gstr: gDrop noise strength"""
     c = cfg
+    c.square("growing_disc_tempo")
     with tf.variable_scope("tempo-disc", reuse=reuse):
         x = tf.reshape(in_high_, shape=[-1, c.tileSizeHigh, c.tileSizeHigh, 12 if c.useVelInTDisc else 3])
         return _critic(x, "t", percentage, c, reuse, use_batch_norm, train, currentUpres, 1, gstr)[0]

@@ -10,6 +10,8 @@ transposes, velocity channel swaps and the cutoff are HIP kernels
 Every pass shards over its slice axis: rank r of R evaluates slices
 ``[r*S/R, (r+1)*S/R)`` and an all-gather reassembles the volume before the next
 pass (``dist.Comm``); with one rank this degenerates to the plain loop.
+The low-res volume ``[Z, Y, X, C]`` need not be a cube: every pass has its own slice
+count S and plane (``pass_planes_4x`` / ``pass_planes_8x`` / ``single_pass_plane_8x``).
 The ``backend`` argument is the operator module (default: the HIP ``ops``).
 """
 import os
@@ -41,10 +43,10 @@ def _check_exchange(exchange):
 
 
 def _hand_over(comm, out, s, perm, a2a, backend):
-    """Pass p produced `out` = this rank's slab [S/R, S, S] of a volume V; pass p+1 slices Y = transpose(V, perm) along
-    its axis 0 and this rank evaluates Y[lo:hi].  Returns (Y_local, V_full or None):
-    all-gather: every rank receives all of V (S^3 elements) and keeps its rows of the transposed volume;
-    all-to-all: only the [S/R, S, S/R] blocks that end up in Y[lo:hi] travel (S^3 / R elements per rank), V is never whole.
+    """Pass p produced `out` = this rank's slab [S_p/R, A, B] of a volume V; pass p+1 slices Y = transpose(V, perm) along
+    its axis 0 -- `s` slices, the next pass's count -- and this rank evaluates Y[lo:hi].  Returns (Y_local, V_full or None):
+    all-gather: every rank receives all of V and keeps its rows of the transposed volume;
+    all-to-all: only the blocks that end up in Y[lo:hi] travel (1/R of V per rank), V is never whole.
     (multipassGAN-out.py:459,521; multipassGAN-4x.py:1113)"""
     return _finish_hand_over(_start_hand_over(comm, out, s, perm, a2a), backend)
 
@@ -52,7 +54,7 @@ def _hand_over(comm, out, s, perm, a2a, backend):
 def _start_hand_over(comm, out, s, perm, a2a):
     if a2a and comm.world > 1 and perm[0] != 0:
         return ("a2a", comm.all_to_all_blocks_start(out, perm[0]), comm, s, perm)
-    return ("gather", _start_gather(comm, out, s), comm, s, perm)
+    return ("gather", _start_gather(comm, out, out.shape[0] * comm.world), comm, s, perm)
 
 
 def _finish_hand_over(h, backend):
@@ -66,12 +68,74 @@ def _finish_hand_over(h, backend):
     return y[lo:hi], full
 
 
-def slice_range(total, comm):
-    """contiguous slice range of this rank; ``total`` must divide by the world size"""
+def slice_range(total, comm, what=None):
+    """contiguous slice range of this rank; ``total``, the slice count of the pass `what`, must divide by the world size"""
     if total % comm.world:
-        raise ValueError("slice count %d does not divide over %d ranks" % (total, comm.world))
+        raise ValueError("%sslice count %d does not divide over %d ranks" % (what + ": " if what else "", total, comm.world))
     per = total // comm.world
     return comm.rank * per, (comm.rank + 1) * per
+
+
+# ----------------------------------------------------------------------------
+# volume shapes: low is [Z, Y, X, C], a pass's plane is (rows, cols) of its network's low input
+# ----------------------------------------------------------------------------
+def volume_shape(low):
+    return tuple(int(v) for v in low.shape[:3])
+
+
+def is_cube(shape):
+    return shape[0] == shape[1] == shape[2]
+
+
+def pass_planes_4x(shape):
+    """low planes (tile_low) of the 4x networks on a (Z, Y, X) volume: upsamplingMode 2 runs the z slices, mode 1 the
+    (z, y) planes along x, mode 3 the (z, x) planes along y.  Modes 1 / 3 are fed at up_res times the plane."""
+    z, y, x = shape
+    return (y, x), (z, y), (z, x)
+
+
+def pass_counts_4x(shape, up_res):
+    """slices of the three passes: along z, x, y of the high-res volume"""
+    z, y, x = shape
+    return z * up_res, x * up_res, y * up_res
+
+
+def pass_planes_8x(shape):
+    """low planes of the one to three networks of multipass_8x (transpose_axis 0): z slices, then the (y, z) planes along
+    x (dim_output.transpose(2, 1, 0), out.py:459), then the (z, x) planes along y (.transpose(1, 2, 0), :521)"""
+    z, y, x = shape
+    return (y, x), (y, z), (z, x)
+
+
+pass_counts_8x = pass_counts_4x
+
+
+def single_pass_plane_8x(shape, transpose_axis):
+    """(low plane, slice count per unit of up_res) of one single_pass_8x call: what _SINGLE_PASS yields"""
+    z, y, x = shape
+    return {0: ((y, x), z), 1: ((z, x), y), 2: ((y, z), x), 3: ((z, y), x)}[transpose_axis]
+
+
+_MODE0_CUBES = "the upsamplingMode 0 pipelines (plane_pass_*, upsample_pass_*, two_pass_*_axis) take simSize cubes"
+
+
+def _require_cube(low, what, why):
+    shape = volume_shape(low)
+    if not is_cube(shape):
+        raise ValueError("%s: the %d x %d x %d volume is not a cube; %s" % ((what,) + shape + (why,)))
+
+
+def _check_passes(comm, what, gens, planes, counts, up_res):
+    """before anything is launched: every pass's slice count divides over the ranks, and every generator that tells its
+    planes (Generator.out_hw) was built for the plane its pass runs on"""
+    for i, (gen, plane, count) in enumerate(zip(gens, planes, counts)):
+        name = "%s pass %d" % (what, i + 1) if len(planes) > 1 else what
+        slice_range(count, comm, name)
+        want = (plane[0] * up_res, plane[1] * up_res)
+        have = getattr(gen, "out_hw", None)
+        if have is not None and tuple(have) != want:
+            raise ValueError("%s runs planes of %d x %d (low %d x %d): its generator was built for %d x %d (tile_low %r)"
+                             % ((name,) + want + tuple(plane) + tuple(have) + ((getattr(gen, "cfg", None) or {}).get("tile_low"),)))
 
 
 # ----------------------------------------------------------------------------
@@ -80,6 +144,9 @@ def slice_range(total, comm):
 class Generator(object):
     """One generator network: private graph + session.  Call with device tensors
     x [N,h,w,C] (and y [N,H,W] for the later 8x generators); returns [N,H,W].
+    cfg["tile_low"]: an int (the reference's square tile) or a pair (rows, cols) of the low plane; for gen_resnet modes
+    1 / 3 and the later 8x networks the network's own plane is that times up_res.  in_hw / y_hw / out_hw: the planes of
+    x, y and the result; a batch given with another plane raises ValueError before anything is launched.
     gen_resnet with upsampling_mode 0 takes planes x [N, high, low, C]: its first layer repeats the columns only.
     growing_gen with cfg["upsampling_mode"] 0 takes planes x [N, high, low, C + 1] (previous pass first) and no y: every
     block repeats the columns once (arch.growing_gen).
@@ -98,13 +165,23 @@ class Generator(object):
             vort = vorticity.CHANNELS if c.get("vorticity") else 0
             if vort and nch < 4:
                 raise ValueError("vorticity channels are computed from the velocity channels 1 and 2: channels %d < 4" % nch)
-            self.high = low * up
+            low_r, low_c = arch.plane_hw(low)
+            self.out_hw = (low_r * up, low_c * up)           # plane of the result
+            self.y_hw = None                                 # plane of y (the later 8x generators)
+            if isinstance(low, (tuple, list)):
+                low = (low_r, low_c)
+                if c.get("upsampling_mode") == 0:
+                    raise ValueError("upsampling_mode 0 takes one tile_low (planes [high, low]), not the pair %r" % (low,))
+                self.high = None
+            else:
+                self.high = low * up
             self.y = None
             if kind == "gen_resnet":
                 mode = c.get("upsampling_mode", 2)
-                rows = low if mode == 2 else self.high
-                cols = low if mode in (2, 0) else self.high
+                rows = low_r if mode == 2 else self.out_hw[0]
+                cols = low_c if mode in (2, 0) else self.out_hw[1]
                 nch += vort                                  # 4x.py:344
+                self.in_hw = (rows, cols)                    # plane of x
                 self.x = G.placeholder([None, rows * cols * nch], name="x")
                 self.sampler = arch.gen_resnet(self.x, low, up, nch, mode, use_batch_norm=c.get("batch_norm", True))
             elif kind == "growing_gen":
@@ -117,13 +194,16 @@ class Generator(object):
                 n_in = nch + (2 if c.get("add_adj", False) else 0) + vort     # 8x.py:350, out.py:148
                 nch += vort
                 if mode == 0:          # planes [high, low] of (previous pass, low-res channels): 8x.py:404-405,413-414
+                    self.in_hw = (self.high, low)
                     self.x = G.placeholder([None, self.high * low * (nch + 1)], name="x")
                 else:
-                    self.x = G.placeholder([None, low * low * n_in], name="x")
+                    self.in_hw = (low_r, low_c)
+                    self.x = G.placeholder([None, low_r * low_c * n_in], name="x")
                 src = self.x
                 if mode in (1, 3):
+                    self.y_hw = self.out_hw
                     self.y = G.placeholder([None, None], name="y")
-                    src = arch.second_gen_input(self.x, self.y, low, self.high, nch)
+                    src = arch.second_gen_input(self.x, self.y, low, self.out_hw, nch)
                 acfg = arch.Cfg8x(tileSizeLow=low, upRes=up, n_inputChannels=n_in if first else nch,
                                   upsampling_mode=mode if mode in (0, 2) else 1, upsampleMode=c.get("upsample_mode", 1),
                                   filterSize=c["filter_size"], start_fms=c["start_fms"], max_fms=c["max_fms"],
@@ -167,12 +247,21 @@ class Generator(object):
         return g
 
     def __call__(self, x, y=None, out=None):
-        """out: where the [n, high, high] result goes (a slice of the pass's volume), else a new tensor"""
+        """out: where the [n, H, W] result goes (a slice of the pass's volume), else a new tensor; (H, W) = out_hw"""
         n = x.shape[0]
+        # a batch given with its plane must have the plane the graph was built for: the flat feed would otherwise be
+        # regrouped silently (equal element counts) or fail in a reshape inside the pass
+        if x.dim() == 4 and tuple(x.shape[1:3]) != self.in_hw:
+            raise ValueError("generator built for input planes %d x %d (tile_low %r, output %d x %d): batch %s has planes "
+                             "%d x %d" % (self.in_hw + (self.cfg["tile_low"],) + self.out_hw + (tuple(x.shape),)
+                                          + tuple(x.shape[1:3])))
+        if self.y is not None and y is not None and y.dim() >= 3 and tuple(y.shape[1:3]) != self.y_hw:
+            raise ValueError("generator built for previous-pass planes %d x %d (tile_low %r): batch %s has planes %d x %d"
+                             % (self.y_hw + (self.cfg["tile_low"], tuple(y.shape)) + tuple(y.shape[1:3])))
         feeds = {self.x: x.reshape(n, -1)}
         if self.y is not None:
             feeds[self.y] = y.reshape(n, -1)
-        return self.sess.run_device(self.sampler, feeds, out=out).reshape(n, self.high, self.high)
+        return self.sess.run_device(self.sampler, feeds, out=out).reshape(n, *self.out_hw)
 
 
 # HIP streams the slice batches of one pass are dealt to (the batches are independent).  1 = the plain loop.
@@ -207,7 +296,8 @@ def _run_pass(gen, xs, ys, lo, hi, batch, out=None):
         res = [gen(xs[j:min(j + batch, hi)], ys[j:min(j + batch, hi)] if ys is not None else None) for j in range(lo, hi, batch)]
         return res[0] if len(res) == 1 else torch.cat(res, dim=0)
     # every batch writes its slices of the pass's volume itself: no concatenation pass behind the generator calls
-    full = torch.empty((hi - lo, gen.high, gen.high), dtype=torch.float32, device=xs.device)
+    out_hw = getattr(gen, "out_hw", None) or (gen.high, gen.high)
+    full = torch.empty((hi - lo,) + tuple(out_hw), dtype=torch.float32, device=xs.device)
     if lanes <= 1:
         for j in range(lo, hi, batch):
             k = min(j + batch, hi)
@@ -258,25 +348,25 @@ def _pass1_4x(gen1, low, up_res, batch, comm, backend, vel_scale, a2a=False):
     """pass 1 of one volume: upsamplingMode 2 -- zoom z, slices along z (4x.py:1103,1126-1133); the
     hand-over of the slabs to pass 2 is started, not awaited"""
     nch = low.shape[3]
-    s = low.shape[0] * up_res
+    sz, sx, _ = pass_counts_4x(volume_shape(low), up_res)
     low1 = low
     if nch > 1 and vel_scale != 1.0:                                 # 4x.py:283, first run: vx,vy,vz
         low1 = backend.channel_gather(low, None, list(range(nch)), [1.0] + [vel_scale] * 3 + [1.0] * (nch - 4))
-    xs = backend.axis_zoom_linear(low1, 0, up_res)                   # [s, sim, sim, C]
-    lo, hi = slice_range(s, comm)
+    xs = backend.axis_zoom_linear(low1, 0, up_res)                   # [uZ, Y, X, C]
+    lo, hi = slice_range(sz, comm, "4x pass 1")
     if _wants_vorticity(gen1):
         xs, lo, hi = _with_vorticity(gen1, xs[lo:hi]), 0, hi - lo
-    out1 = _run_pass(gen1, xs, None, lo, hi, batch)                  # [hi-lo, s, s] = (z, y, x)
+    out1 = _run_pass(gen1, xs, None, lo, hi, batch)                  # [hi-lo, uY, uX] = (z, y, x)
     out1 = backend.cutoff(out1, CUTOFF)                              # 4x.py:1156-1157
-    return _start_hand_over(comm, out1, s, (2, 0, 1), a2a)
+    return _start_hand_over(comm, out1, sx, (2, 0, 1), a2a)
 
 
 def _pass2_4x(gen2, low, hand, up_res, batch, comm, backend, vel_scale):
     """pass 2: upsamplingMode 1 -- slices along x of (z, y) planes (4x.py:1113-1119).  `hand`: the started hand-over of
     pass 1's volume (_start_hand_over with perm (2, 0, 1)).  Returns (started all-gather of the output, v1 or None)."""
     nch = low.shape[3]
-    s = low.shape[0] * up_res
-    lo, hi = slice_range(s, comm)
+    sz, sx, sy = pass_counts_4x(volume_shape(low), up_res)
+    lo, hi = slice_range(sx, comm, "4x pass 2")
     ys, v1 = _finish_hand_over(hand, backend)                        # [hi-lo][z][y]: this rank's x planes of pass 1
     if nch > 1:
         vel = _scaled_velocities(low, up_res, vel_scale, backend)
@@ -284,11 +374,11 @@ def _pass2_4x(gen2, low, hand, up_res, batch, comm, backend, vel_scale):
             vel = backend.axis_zoom_linear(vel, ax, up_res)
         # transpose(0,3,1,2,4) then the two channel swaps (d,vx,vy,vz) -> (d,vy,vz,vx); only this rank's x range
         velx = backend.volume_transpose(vel[:, :, lo:hi].contiguous(), (2, 0, 1), chan_map=[1, 2, 0])
-        xin = backend.channel_gather(ys.reshape(hi - lo, s, s, 1), velx, [0, 1, 2, 3])
+        xin = backend.channel_gather(ys.reshape(hi - lo, sz, sy, 1), velx, [0, 1, 2, 3])
     else:
-        xin = ys.reshape(hi - lo, s, s, 1)
+        xin = ys.reshape(hi - lo, sz, sy, 1)
     out2 = _run_pass(gen2, _with_vorticity(gen2, xin), None, 0, hi - lo, batch)   # [x-range][z][y]
-    return _start_gather(comm, out2, s), v1
+    return _start_gather(comm, out2, sx), v1
 
 
 def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend=ops, vel_scale=1.0, apply_cutoff=True,
@@ -297,9 +387,15 @@ def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend
     upsamplingMode 3: planes (z,x) along y, :1121-1124,1144).  prev: the [z,y,x] volume of the previous network.
     Returns the [z,y,x] volume the reference writes (cutoff :1156-1157).  previews: a preview.PreviewSink that receives
     the volume where the reference calls save_img_3d (:1146), before the cutoff."""
-    comm = _preview_comm(comm, previews)
+    comm = _preview_comm(comm, previews, low)
     nch = low.shape[3]
-    s = low.shape[0] * up_res
+    shape = volume_shape(low)
+    sz, sx, sy = pass_counts_4x(shape, up_res)
+    s = sx if mode == 1 else sy
+    _check_passes(comm, "refine_pass_4x (upsamplingMode %d)" % mode, [gen], [pass_planes_4x(shape)[1 if mode == 1 else 2]],
+                  [s], up_res)
+    if prev.numel() != sz * sy * sx:
+        raise ValueError("refine_pass_4x: previous volume %s, expected %s" % (tuple(prev.shape), (sz, sy, sx)))
     lo, hi = slice_range(s, comm)
     # mode 1: transpose(0,3,1,2,4) + swaps 2<->3, 3<->1; mode 3: transpose(0,2,1,3,4) + swap 2<->3
     perm, cmap, back = ((2, 0, 1), [0, 2, 3, 1], (1, 2, 0)) if mode == 1 else ((1, 0, 2), [0, 1, 3, 2], (1, 0, 2))
@@ -307,9 +403,10 @@ def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend
         vel = _scaled_velocities(low, up_res, vel_scale, backend)
         for ax in range(3):                                          # 4x.py:1095
             vel = backend.axis_zoom_linear(vel, ax, up_res)
-        xin = backend.volume_transpose(backend.channel_gather(prev.reshape(s, s, s, 1), vel, [0, 1, 2, 3]), perm, chan_map=cmap)
+        xin = backend.volume_transpose(backend.channel_gather(prev.reshape(sz, sy, sx, 1), vel, [0, 1, 2, 3]), perm, chan_map=cmap)
     else:
-        xin = backend.volume_transpose(prev.reshape(s, s, s), perm).reshape(s, s, s, 1)
+        xin = backend.volume_transpose(prev.reshape(sz, sy, sx), perm)
+        xin = xin.reshape(tuple(xin.shape) + (1,))
     if _wants_vorticity(gen):
         xin, lo, hi = _with_vorticity(gen, xin[lo:hi]), 0, hi - lo
     out = _run_pass(gen, xin, None, lo, hi, batch)
@@ -319,11 +416,13 @@ def refine_pass_4x(gen, low, prev, up_res=4, mode=1, batch=8, comm=None, backend
     return backend.volume_transpose(vol, back, cutoff=CUTOFF if apply_cutoff else 0.0)
 
 
-def _preview_comm(comm, previews):
-    """the communicator of a pass; a preview sink wants the whole pass volume in this process"""
+def _preview_comm(comm, previews, low=None):
+    """the communicator of a pass; a preview sink wants the whole pass volume in this process, and a cube"""
     comm = comm or LocalComm()
     if previews is not None:
         previews.check_comm(comm)
+        if low is not None:
+            _require_cube(low, "previews", "projection_image stacks three sums of equal width")
     return comm
 
 
@@ -339,6 +438,7 @@ def plane_pass_4x(gen1, low, up_res=4, batch=8, comm=None, backend=ops, vel_scal
     low-res array as they are, nothing is zoomed.  low: [z_low, y, x, C]; returns [z_low, Y, X] (density_low_2x2x1).
     The velocities are scaled as in pass 1 of two_pass_4x (4x.py:283, first run)."""
     _single_process(comm, "plane_pass_4x")
+    _require_cube(low, "plane_pass_4x", _MODE0_CUBES)
     nch = low.shape[3]
     low1 = low
     if nch > 1 and vel_scale != 1.0:
@@ -359,6 +459,7 @@ def upsample_pass_4x(gen0, low, prev, up_res=4, batch=8, comm=None, backend=ops,
     volume (density_low_1x1x1) is what the reference stores, not a [z, y, x] one.  previews: a preview.PreviewSink
     that receives the volume where the reference calls save_img_3d (:1146), before the cutoff."""
     _preview_comm(_single_process(comm, "upsample_pass_4x"), previews)
+    _require_cube(low, "upsample_pass_4x", _MODE0_CUBES)
     if _wants_vorticity(gen0):
         raise ValueError("upsample_pass_4x (upsamplingMode 0) has no vorticity channels: no training path produces such a "
                          "network (its planes [x][y][z_low] are not the slices the stencil is defined on)")
@@ -386,6 +487,7 @@ def two_pass_4x_axis(gen1, gen0, low, up_res=4, batch=8, comm=None, backend=ops,
     generator slices instead of 2 * sim * upRes).  Returns (final volume as upsample_pass_4x leaves it, pass-1 volume
     [z_low, Y, X]), both with the cutoff of the files the reference writes."""
     _single_process(comm, "two_pass_4x_axis")
+    _require_cube(low, "two_pass_4x_axis", _MODE0_CUBES)
     v1 = plane_pass_4x(gen1, low, up_res, batch, None, backend, vel_scale)
     return upsample_pass_4x(gen0, low, v1, up_res, batch, None, backend, vel_scale), v1
 
@@ -396,10 +498,16 @@ def two_pass_4x(gen1, gen2, low, up_res=4, batch=8, comm=None, backend=ops, vel_
     pass 2 on several ranks ("all_gather": the whole volume to every rank; "all_to_all": only the blocks each rank's
     planes need -- the pass-1 volume is then never assembled and the second result is None)."""
     comm = comm or LocalComm()
+    _check_two_pass_4x(comm, gen1, gen2, low, up_res)
     hand = _pass1_4x(gen1, low, up_res, batch, comm, backend, vel_scale, _check_exchange(exchange))
     g2, v1 = _pass2_4x(gen2, low, hand, up_res, batch, comm, backend, vel_scale)
     final = backend.volume_transpose(g2.wait(), (1, 2, 0), cutoff=CUTOFF)   # [x, z, y] -> [z, y, x]: 4x.py:1142,1156
     return final, v1
+
+
+def _check_two_pass_4x(comm, gen1, gen2, low, up_res):
+    shape = volume_shape(low)
+    _check_passes(comm, "two_pass_4x", [gen1, gen2], pass_planes_4x(shape)[:2], pass_counts_4x(shape, up_res)[:2], up_res)
 
 
 def _two_pass_4x_steps(gen1, gen2, lows, finals, where, up_res, batch, comm, backend, vel_scale, a2a=False):
@@ -435,6 +543,9 @@ def two_pass_4x_batch(gen1, gen2, lows, up_res=4, batch=8, comm=None, backend=op
     n = len(lows)
     finals = [None] * n
     pairs = [(gen1, gen2)] + list(lanes or [])
+    for low in lows:
+        for ga, gb in pairs:
+            _check_two_pass_4x(comm, ga, gb, low, up_res)
     if len(pairs) == 1 or n < 2 or not lows[0].is_cuda:
         for _ in _two_pass_4x_steps(gen1, gen2, lows, finals, list(range(n)), up_res, batch, comm, backend, vel_scale, a2a):
             pass
@@ -496,7 +607,9 @@ SLICE_PREP = {
 
 
 def slice_batch_8x(low, up_res, pass_no, transpose_axis, backend=ops):
-    """[S, sim, sim, C] low-res slice batch of one pass (before the add_adj_idcs channels)"""
+    """[S, rows, cols, C] low-res slice batch of one pass (before the add_adj_idcs channels).  A cube is regrouped
+    into sim x sim planes as the reference does (which matters for pass 3 of transposeAxis 3); any other volume keeps
+    the planes its transpose left, and only transposeAxis 0 is defined for it (multipass_8x)"""
     sim, nch = low.shape[0], low.shape[3]
     try:
         axis, perm, cmap = SLICE_PREP[pass_no][transpose_axis]
@@ -508,7 +621,7 @@ def slice_batch_8x(low, up_res, pass_no, transpose_axis, backend=ops):
     xs = backend.axis_zoom_linear(low, axis, up_res)
     if perm is not None:
         xs = backend.volume_transpose(xs, perm, chan_map=cmap if nch >= 4 else None)
-    return xs.reshape(-1, sim, sim, nch)
+    return xs.reshape(-1, sim, sim, nch) if is_cube(volume_shape(low)) else xs
 
 
 def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops, apply_cutoff=True, transpose_axis=0,
@@ -518,11 +631,16 @@ def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops,
     axis restore (:587-590): [z,y,x] for transposeAxis 0.  previews: a preview.PreviewSink that receives every pass's
     volume where the reference calls save_img_3d (:461,523,585) and the last one where its slice loop runs (:592-604),
     all before the cutoff, each with the permutation that makes it the reference's dim_output at that line."""
-    comm = _preview_comm(comm, previews)
+    comm = _preview_comm(comm, previews, low)
     a2a = _check_exchange(exchange)
-    sim = low.shape[0]
-    s = sim * up_res
-    lo, hi = slice_range(s, comm)
+    shape = volume_shape(low)
+    if transpose_axis != 0:
+        _require_cube(low, "multipass_8x with transposeAxis %r" % (transpose_axis,),
+                      "SLICE_PREP regroups planes as the reference does (multipassGAN-out.py:534-535), which is only "
+                      "defined for cubes: use transposeAxis 0")
+    counts = pass_counts_8x(shape, up_res)[:len(gens)]
+    _check_passes(comm, "multipass_8x", gens, pass_planes_8x(shape)[:len(gens)], counts, up_res)
+    lo, hi = slice_range(counts[0], comm)
     # pass 1 (397-461): slices along the zoomed axis, add_adj_idcs channels
     xs = slice_batch_8x(low, up_res, 1, transpose_axis, backend)
     if gens[0].cfg.get("add_adj", False):
@@ -536,19 +654,21 @@ def multipass_8x(gens, low, up_res=8, batches=(8, 2, 2), comm=None, backend=ops,
         previews.projection("1st", out, (2, 1, 0))                   # :459-461
     if len(gens) > 1:
         # pass 2 (463-523): conditioned on planes of dim_output.transpose(2,1,0) (:459)
-        ys, _ = _hand_over(comm, out, s, (2, 1, 0), a2a, backend)
+        lo, hi = slice_range(counts[1], comm)
+        ys, _ = _hand_over(comm, out, counts[1], (2, 1, 0), a2a, backend)
         xl = slice_batch_8x(low, up_res, 2, transpose_axis, backend)
         out = _run_pass(gens[1], _with_vorticity(gens[1], xl[lo:hi]), ys, 0, hi - lo, batches[1])   # on the low-res slice
         if previews is not None:
             previews.projection("2nd", out, (1, 2, 0))               # :521-523
     if len(gens) > 2:
         # pass 3 (525-585): conditioned on the previous result .transpose(1,2,0) (:521)
-        ys, _ = _hand_over(comm, out, s, (1, 2, 0), a2a, backend)
+        lo, hi = slice_range(counts[2], comm)
+        ys, _ = _hand_over(comm, out, counts[2], (1, 2, 0), a2a, backend)
         xl = slice_batch_8x(low, up_res, 3, transpose_axis, backend)
         out = _run_pass(gens[2], _with_vorticity(gens[2], xl[lo:hi]), ys, 0, hi - lo, batches[2])
         if previews is not None:
             previews.projection("3rd", out, (0, 1, 2))               # :583-585
-    vol = comm.all_gather_slabs(out, s)
+    vol = comm.all_gather_slabs(out, counts[-1])
     # the transposes the reference applies to its last dim_output, composed (459 / 521 / 583, then 587-590)
     perm = {1: (0, 1, 2), 2: (2, 1, 0), 3: (1, 0, 2)}[len(gens)]
     if previews is not None:
@@ -584,6 +704,7 @@ def plane_pass_8x(gen1, low, up_res=8, batch=2, comm=None, backend=ops, apply_cu
     reference's transposeAxis branches (:1644-1666, 1720-1725) would leave a volume whose header no reader of the 2x2x1
     file expects, and upsample_pass_8x takes [z_low, Y, X]."""
     _preview_comm(_single_process(comm, "plane_pass_8x"), previews)
+    _require_cube(low, "plane_pass_8x", _MODE0_CUBES)
     zl = low.shape[0]
     if (getattr(gen1, "cfg", None) or {}).get("add_adj", False):
         xs = backend.add_adjacent(low, 0, zl)                        # :1671-1685
@@ -613,6 +734,7 @@ def upsample_pass_8x(gen0, low, prev, up_res=8, transpose_axis=0, batch=2, comm=
     the default, the stored volume (density_low_t%04d_1x1x1) keeps the axes (x, y, z); transposeAxis 2 makes it
     [z, y, x].  previews: a preview.PreviewSink that receives the stack where the reference calls save_img_3d (:1718)."""
     _preview_comm(_single_process(comm, "upsample_pass_8x"), previews)
+    _require_cube(low, "upsample_pass_8x", _MODE0_CUBES)
     if _wants_vorticity(gen0):
         raise ValueError("upsample_pass_8x (upsamplingMode 0) has no vorticity channels: no training path produces such a "
                          "network (its planes [x][y][z_low] are not the slices the stencil is defined on)")
@@ -642,6 +764,7 @@ def two_pass_8x_axis(gen1, gen0, low, up_res=8, batches=(2, 2), transpose_axis=0
     Returns (final volume as upsample_pass_8x leaves it, pass-1 volume [z_low, Y, X]), both with the cutoff of the files
     the reference writes."""
     _single_process(comm, "two_pass_8x_axis")
+    _require_cube(low, "two_pass_8x_axis", _MODE0_CUBES)
     v1 = plane_pass_8x(gen1, low, up_res, batches[0], None, backend)
     return upsample_pass_8x(gen0, low, v1, up_res, transpose_axis, batches[1], None, backend), v1
 
@@ -664,18 +787,23 @@ def single_pass_8x(gen, low, prev=None, up_res=8, transpose_axis=0, batch=2, com
             raise ValueError("single_pass_8x: upsampleFirst 0 belongs to the first network (no previous volume) and "
                              "slices along z (transposeAxis 0)")
         return plane_pass_8x(gen, low, up_res, batch, comm, backend, apply_cutoff, previews)
-    comm = _preview_comm(comm, previews)
-    sim, nch = low.shape[0], low.shape[3]
-    s = sim * up_res
+    comm = _preview_comm(comm, previews, low)
+    nch = low.shape[3]
+    shape = volume_shape(low)
+    plane, count = single_pass_plane_8x(shape, transpose_axis)
+    s = count * up_res
+    _check_passes(comm, "single_pass_8x (transposeAxis %d)" % transpose_axis, [gen], [plane], [s], up_res)
+    hi_shape = tuple(v * up_res for v in shape)
+    if prev is not None and prev.numel() != hi_shape[0] * hi_shape[1] * hi_shape[2]:
+        raise ValueError("single_pass_8x: previous volume %s, expected %s" % (tuple(prev.shape), hi_shape))
     lo, hi = slice_range(s, comm)
     perm, cmap, _ = _SINGLE_PASS[transpose_axis]
     xs = backend.axis_zoom_linear(low, _ZOOM_AXIS[transpose_axis], up_res)           # :1606-1613, 1624-1631
     if perm is not None:
         xs = backend.volume_transpose(xs, perm, chan_map=cmap if nch >= 4 else None)  # :1644-1664
-    xs = xs.reshape(-1, sim, sim, nch)
     ys = None
     if prev is not None:
-        ys = prev.reshape(s, s, s)
+        ys = prev.reshape(hi_shape)
         if perm is not None:
             ys = backend.volume_transpose(ys, perm)                                  # :1650,1657,1666
     if gen.cfg.get("add_adj", False):
